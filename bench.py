@@ -8,7 +8,12 @@ map = the reference's only shipped HDR (P4/HDR/peppermint_powerplant_4k.hdr, 102
 full render of that frame (64 spp) through libezrt_hip.so; scene, env map and the frame buffer are resident in HBM
 before the timed region.  ray := one hitBVH call, counted by the kernels.
 
-The N = 1 line also carries (round 4):
+A plain run (the default) does only what the headline needs: set up, W warm-up steps, the timed steps, `--dump-outputs`
+if given, one JSON line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the timing block.
+Everything below that is not the headline -- lone-call and per-launch timings, parity, roofline, the extra fields, the scaling
+model, the BASELINE configs, the CPU baselines -- runs only under `--full`.
+
+Under `--full` the N = 1 line also carries (round 4):
   * `parity`: the frame the TIMED loop left (cloned right after the windows) compared on the bits with the frame of the
     instrumented route (binary unpruned in-order kernel) and, in `cpu_baseline`, with the CPU oracle's complete frame;
   * `configs`: BASELINE.json configs[2..4] (C3 / C4 / C5) timed at THEIR stated spp (128 / 256 / 512) -- one warm-up +
@@ -23,19 +28,19 @@ the C2 frame is cut into 16x16 tiles dealt round-robin to the ranks, the scene i
 spp of its tiles and ONE gather of the packed tiles to rank 0 over RCCL closes the frame.  Default "scaling": "strong"
 (round 4: the metric reads "at fixed spp" -- the fixed 64-spp frame is split N ways; a weak run, spp x N, is
 near-linear by construction and is reported as the extra field `weak_variant`); `--scaling weak` makes the weak run
-the headline instead.  Extra fields report per-rank render times, the gather time, the imbalance, the same frame
+the headline instead.  Under `--full`, extra fields report per-rank render times, the gather time, the imbalance, the same frame
 rendered by rank 0 alone with a bitwise comparison (so the line carries its own 1-GPU reference), and BASELINE.json
 configs[3] (C4: P5 scene, integrator 51 = env importance sampling + MIS, 2 bounces, 1024x1024, 256 spp) as a FIXED
 frame split N ways (`c4_strong_variant`).  `--workload c2|c4` picks the main workload for any N.
 
-Timing (VERDICT r2 / SURVEY 8(d) "median of >= 5 runs"): after W warm-up steps the script times `--windows` (default 7)
-windows of EXACTLY K steps, each bracketed by barrier + synchronize on both sides and reduced with MAX over ranks;
-`value` and `ms_per_step` come from the MEDIAN window, every window is in the line (`timing.window_ms`), and so are the
+Timing (VERDICT r2 / SURVEY 8(d) "median of >= 5 runs"): after W warm-up steps the script times `--windows` (default 1, so
+that `--steps` K is the number of timed steps; 7 for a median of seven) windows of EXACTLY K steps, each bracketed by
+barrier + synchronize on both sides and reduced with MAX over ranks; `value` and `ms_per_step` come from the MEDIAN window, every window is in the line (`timing.window_ms`), and so are the
 per-step GPU times of the slowest window (stream events, no host synchronisation inside a window), the host-side
 enqueue time per step and `wall_over_gpu`, so that a host-side stall or a clock ramp is visible instead of averaged in.
 
-Prints one JSON line on rank 0 (contract in the task statement) with `roofline` and, at N = 1, `cpu_baseline`
-(the CPU oracle timed on a bounded sample of the same workload).
+Prints one JSON line on rank 0; under `--full` with `roofline` and, at N = 1, `cpu_baseline` (the CPU oracle timed on a
+bounded sample of the same workload).
 """
 import argparse
 import ctypes
@@ -195,6 +200,26 @@ def same_bits_nan_ok(a, b):
     import numpy as np
     ua, ub = np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32)
     return bool(((ua == ub) | (np.isnan(a) & np.isnan(b))).all())
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame the last timed step left (H x W x 4 float32, what render_device hands its caller) as
+    out_dir/frame.npy.  A frame over 64 MiB is written as a fixed sample instead: frame_sample.npy holds the RGBA of
+    pixels drawn with seed 0 and frame_sample_index.npy (float64) their flat indices y * W + x."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_MAX_BYTES // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
 
 
 def build_config_scene(name, env):
@@ -385,13 +410,20 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1 -- strong (default: the metric reads 'at fixed spp'): the fixed frame is split N ways; "
                          "weak: spp x N, so every GPU keeps the 1-GPU number of pixel-samples")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: lone-call and per-launch timings, parity, roofline, "
+                         "extras, scaling model, BASELINE configs, CPU baselines (off: the headline alone)")
     ap.add_argument("--configs", default="C3,C4,C5",
-                    help="N = 1: BASELINE configs timed after the headline at their stated spp (comma list of C3,C4,C5; 'none' skips)")
+                    help="--full, N = 1: BASELINE configs timed after the headline at their stated spp (comma list of C3,C4,C5; 'none' skips)")
     ap.add_argument("--config-spp", type=int, default=0, help="override the spp of --configs (tests; 0 = BASELINE's 128 / 256 / 512)")
-    ap.add_argument("--model", type=int, default=1, help="N = 1: 0 skips the single-GPU scaling model")
-    ap.add_argument("--windows", type=int, default=7, help="timed windows of --steps steps each; value = the median window")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0: skip the extra fields (second camera, 1-GPU reference, weak variant)")
+    ap.add_argument("--model", type=int, default=1, help="--full, N = 1: 0 skips the single-GPU scaling model")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps steps each (default 1: exactly --steps timed steps); value = the median window")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline sample time (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="--full: 0 skips the extra fields (second camera, 1-GPU reference, weak variant)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the frame the last one left as DIR/frame.npy (float32, H x W x 4; "
+                         "a fixed sample of it above 64 MiB)")
     ap.add_argument("--save-png", default="")
     args = ap.parse_args()
 
@@ -507,7 +539,8 @@ def main():
             dist.all_reduce(wt, op=dist.ReduceOp.MAX)
         return [float(x) for x in wt], gpu_ms, host_ms, last
 
-    step = make_step(sc, p, accum, plan, gather_ev)
+    # (--full only: the gather's stream events inside the timed steps feed multi_gpu's gather time)
+    step = make_step(sc, p, accum, plan, gather_ev if args.full else None)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -518,40 +551,43 @@ def main():
     # the frame the TIMED loop left, before anything else renders: every later pass (launch events, the instrumented route,
     # the extras) writes into `scratch`, so `final` is what the parity fields below compare
     final = final.clone()
-    scratch = torch.zeros_like(accum)
     gather_s = [a.elapsed_time(b) * 1e-3 for a, b in gather_ev]
     rays_timed = sc.counters()["rays"]          # over all windows (the workload is deterministic: the same rays every step)
-    # per-step GPU times with a timing-event pair around every trace launch (hipEvents on the launch stream; reading them
-    # synchronises and each record costs the stream ~5 us, so this is a separate, untimed pass of the same step):
-    # median of 7 -- (all kernels, the trace launches, number of trace launches)
-    step_ms = []
-    sc.set_option("launch_events", 1)
-    for _ in range(7):
-        sc.render_device(p, scratch.data_ptr(), stream)
-        step_ms.append(sc.last_render_ms())
-    sc.set_option("launch_events", 0)
-    # ... and ONE call at a time without any per-launch event: a call between two synchronisations, nothing to overlap with
-    # (the headline windows queue their steps back to back, so a chunk's late stages run under the next chunk's primary stage:
-    # `value` is that steady-state rate, `value_lone_call` the rate of a host that waits for every frame; VERDICT r4 #5c)
-    lone_ms = []
-    e_l0, e_l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(9):
-        torch.cuda.synchronize()
-        e_l0.record()
-        sc.render_device(p, scratch.data_ptr(), stream)
-        e_l1.record()
-        torch.cuda.synchronize()
-        lone_ms.append(e_l0.elapsed_time(e_l1))
-    lone_ms_med = statistics.median(lone_ms)
+    if args.full:
+        scratch = torch.zeros_like(accum)
+        # per-step GPU times with a timing-event pair around every trace launch (hipEvents on the launch stream; reading them
+        # synchronises and each record costs the stream ~5 us, so this is a separate, untimed pass of the same step):
+        # median of 7 -- (all kernels, the trace launches, number of trace launches)
+        step_ms = []
+        sc.set_option("launch_events", 1)
+        for _ in range(7):
+            sc.render_device(p, scratch.data_ptr(), stream)
+            step_ms.append(sc.last_render_ms())
+        sc.set_option("launch_events", 0)
+        # ... and ONE call at a time without any per-launch event: a call between two synchronisations, nothing to overlap with
+        # (the headline windows queue their steps back to back, so a chunk's late stages run under the next chunk's primary stage:
+        # `value` is that steady-state rate, `value_lone_call` the rate of a host that waits for every frame; VERDICT r4 #5c)
+        lone_ms = []
+        e_l0, e_l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(9):
+            torch.cuda.synchronize()
+            e_l0.record()
+            sc.render_device(p, scratch.data_ptr(), stream)
+            e_l1.record()
+            torch.cuda.synchronize()
+            lone_ms.append(e_l0.elapsed_time(e_l1))
+        lone_ms_med = statistics.median(lone_ms)
 
     tt = torch.tensor([float(rays_timed)], dtype=torch.float64, device=tdev)
-    rank_ms = torch.tensor([statistics.median(m[0] for m in step_ms)], dtype=torch.float64, device=tdev)
-    all_rank_ms = [float(rank_ms[0])]
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
-        bufs = [torch.zeros_like(rank_ms) for _ in range(world)]
-        dist.all_gather(bufs, rank_ms)
-        all_rank_ms = [float(b[0]) for b in bufs]
+    if args.full:
+        rank_ms = torch.tensor([statistics.median(m[0] for m in step_ms)], dtype=torch.float64, device=tdev)
+        all_rank_ms = [float(rank_ms[0])]
+        if world > 1:
+            bufs = [torch.zeros_like(rank_ms) for _ in range(world)]
+            dist.all_gather(bufs, rank_ms)
+            all_rank_ms = [float(b[0]) for b in bufs]
     rays_per_step = float(tt[0]) / max(1, args.steps * n_windows)
     order = sorted(range(n_windows), key=lambda i: win_s[i])
     i_med, i_slow = order[(n_windows - 1) // 2], order[-1]      # (lower median for an even count)
@@ -579,10 +615,6 @@ def main():
         "metric": "Mrays/s at fixed spp (Bunny ~70k tris, %s)" % bounce_txt,
         "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "value_lone_call": round(rays_per_step / world / (lone_ms_med * 1e-3) / 1e6, 3) if world == 1 else None,
-        "ms_per_step_lone_call": round(lone_ms_med, 4),
-        "value_note": "value = steps queued back to back (chunks of consecutive calls overlap: pipeline_calls); value_lone_call = one call "
-                      "between two synchronisations, no per-launch events (this rank's shard at N > 1: ms only)",
         "scaling": "n/a" if world == 1 else ("weak" if weak else "strong"),
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s (%d tris, %d BVH nodes, SAH leaf 8), %dx%d, camera rot %g up %g r %g, integrator %d, %d bounces, "
@@ -592,12 +624,17 @@ def main():
                                   env_name),
                    "rays_per_step": int(rays_per_step), "ray_definition": "one hitBVH call",
                    "parallelism": "tiles%dx%d round-robin over %d GPU(s), 1 RCCL gather/frame" % (args.tile, args.tile, world),
-                   "scene_build_s": round(t_build, 3),
-                   "median_gpu_ms_per_step": round(statistics.median(m[0] for m in step_ms), 4)},
+                   "scene_build_s": round(t_build, 3)},
         "timing": timing,
     }
+    if args.full:
+        out["value_lone_call"] = round(rays_per_step / world / (lone_ms_med * 1e-3) / 1e6, 3) if world == 1 else None
+        out["ms_per_step_lone_call"] = round(lone_ms_med, 4)
+        out["value_note"] = ("value = steps queued back to back (chunks of consecutive calls overlap: pipeline_calls); value_lone_call = one call "
+                             "between two synchronisations, no per-launch events (this rank's shard at N > 1: ms only)")
+        out["config"]["median_gpu_ms_per_step"] = round(statistics.median(m[0] for m in step_ms), 4)
 
-    if world > 1:
+    if args.full and world > 1:
         # ---- what the N-GPU frame cost where (rank 0 prints; every rank takes part in the collectives above)
         mg = {"tiles_total": plan.n_tiles, "tiles_per_rank": [len(range(r, plan.n_tiles, world)) for r in range(world)],
               "render_ms_per_rank_median": [round(x, 4) for x in all_rank_ms],
@@ -690,7 +727,7 @@ def main():
             mg["c4_strong_variant"] = c4v
         out["multi_gpu"] = mg
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---- roofline of the dominant kernel
         sc.set_instrumentation(1)
         sc.counters_reset()
@@ -923,6 +960,8 @@ def main():
                 out["cpu_baseline"]["reference_shader"] = {"skipped": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final.detach().cpu().numpy())
         if args.save_png:
             from ezrt_amd import imageio
             rgb = hip.tonemap(final.detach().cpu().numpy().reshape(-1, 4)).reshape(H, W, 3)

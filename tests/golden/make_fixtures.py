@@ -21,12 +21,18 @@ Writes
   tests/golden/hdr_probe.json
         size, a few texels, checksums of that map AS DECODED BY THE REFERENCE'S HDRLoader::load and
         of calculateHdrCache's output AS COMPUTED BY THE REFERENCE (P5/main.cpp:592-689).
+  tests/golden/ref_digests.json
+        sha256 digests of reference data the tests would otherwise read from /root/reference: chapter 5's Sobol
+        literal (shaders/fshader.fsh, V[8*32]) and chapter 3's scene built by the host library from the reference's
+        OBJ files (write_digests(); the recipes are sobol_literal() and p3_scene_from_obj_files()).
   tests/golden/ref_scene_p3.json
         what chapter 3's main() uploads when run headless (counts + checksums of both arrays).
 """
 import ctypes
+import hashlib
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -34,6 +40,8 @@ import numpy as np
 REF = "/root/reference"
 P3 = os.path.join(REF, "part 3 -- OpenGL Raytracing", "source code")
 P4 = os.path.join(REF, "part 4 -- Disney Principle BRDF", "source code")
+P3_MODELS = os.path.join(P3, "models")
+P5_FSH = os.path.join(REF, "part 5 -- Importance Sampling & Low Discrepancy Sequence", "source code", "shaders", "fshader.fsh")
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 ASSETS = os.path.join(ROOT, "ezrt_amd", "assets")
@@ -97,6 +105,44 @@ def bits_sum(a):
     return int(np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64).sum() & np.uint64(0xFFFFFFFFFFFFFFFF))
 
 
+def sha256(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def sobol_literal(path=P5_FSH):
+    """the `const uint V[8*32]` literal of chapter 5's fragment shader, as a list of ints"""
+    m = re.search(r"const uint V\[8\*32\] = \{\s*([0-9u,\s]+)\};", open(path).read())
+    return [int(x.strip().rstrip("u")) for x in m.group(1).split(",") if x.strip()]
+
+
+def p3_scene_from_obj_files(models=P3_MODELS):
+    """chapter 3's scene (P3/main.cpp:690-701, P4/P5 material defaults) built by the host library from the reference's
+    OBJ files: (tri, nodes)"""
+    from ezrt_amd import scene as S
+    hs = S.HostScene()
+    mk = S.Material.disney
+    hs.readObj(os.path.join(models, "Stanford Bunny.obj"), mk(baseColor=(1, 1, 1)),
+               S.getTransformMatrix((0, 0, 0), (0.3, -1.6, 0), (1.5, 1.5, 1.5)), True)
+    hs.readObj(os.path.join(models, "quad.obj"), mk(baseColor=(0.725, 0.71, 0.68)),
+               S.getTransformMatrix((0, 0, 0), (0, -1.4, 0), (18.83, 0.01, 18.83)), False)
+    hs.readObj(os.path.join(models, "sphere.obj"), mk(baseColor=(1, 1, 1), emissive=(30, 20, 10)),
+               S.getTransformMatrix((0, 0, 0), (0.0, 0.9, -0.0), (1, 1, 1)), False)
+    hs.buildBVHwithSAH(8)
+    return hs.encode()
+
+
+def write_digests():
+    tri, nodes = p3_scene_from_obj_files()
+    d = {"produced_by": "tests/golden/make_fixtures.py write_digests(), from the reference's own files",
+         "p5_sobol_literal_sha256": sha256(np.array(sobol_literal(), np.uint32)),
+         "p3_obj_scene_shape": [int(tri.shape[0]), int(nodes.shape[0])],
+         "p3_obj_scene_tri_sha256": sha256(tri), "p3_obj_scene_nodes_sha256": sha256(nodes)}
+    with open(os.path.join(HERE, "ref_digests.json"), "w") as f:
+        json.dump(d, f, indent=1)
+        f.write("\n")
+    print(d)
+
+
 def main():
     from oracle import ref as R
     os.makedirs(ASSETS, exist_ok=True)
@@ -148,6 +194,7 @@ def main():
     with open(os.path.join(HERE, "ref_scene_p3.json"), "w") as f:
         json.dump(scene, f, indent=1)
     print(scene["nTriangles"], scene["nNodes"])
+    write_digests()
 
 
 if __name__ == "__main__":

@@ -60,3 +60,23 @@ def test_the_rccl_floor_file_the_scaling_model_reads_is_parseable():
     assert set(d["payloads"]) == {"0.5MiB", "2MiB", "8MiB"}
     for v in d["payloads"].values():
         assert 0.001 < v["rccl_floor_ms"] < 0.1 and v["mgpu_rccl_loopback_gather_ms"]["median"] > v["rccl_floor_ms"]
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path):
+    """--dump-outputs: a frame within the size cap is written whole (float32); a larger one as a seeded sample of its pixels
+    with their flat indices, the same sample every run, within the cap."""
+    import numpy as np
+    b = _bench()
+    frame = np.random.default_rng(1).random((8, 16, 4)).astype(np.float32)
+    b.dump_outputs(str(tmp_path / "a"), frame)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    b.DUMP_MAX_BYTES = 240
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), frame)
+    px = np.load(tmp_path / "b" / "frame_sample.npy")
+    idx = np.load(tmp_path / "b" / "frame_sample_index.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and px.shape == (10, 4) and px.nbytes + idx.nbytes <= 240
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_sample_index.npy"))
+    assert not (tmp_path / "b" / "frame.npy").exists()

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 def _run(scaling, port, ranks=2, spp=8):
     env = dict(os.environ, EZRT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--windows", "3",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--windows", "3",
            "--spp", str(spp), "--cpu-seconds", "0"] + (["--scaling", scaling] if scaling else [])
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -68,7 +68,7 @@ def test_bench_single_gpu_line_carries_parity_configs_and_model():
     """The N = 1 line at reduced sizes (the driver's run uses the defaults): the timed frame equals the instrumented route's
     frame and the CPU oracle's; C3 / C4 / C5 are timed with a crop of the timed frame equal to the oracle's; the scaling
     model has C2 and C4 for 2 / 4 / 8 shards; both VALU peaks are printed; the reference's compiled shader is timed."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--windows", "3", "--spp", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--windows", "3", "--spp", "3",
            "--config-spp", "2", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -94,3 +94,32 @@ def test_bench_single_gpu_line_carries_parity_configs_and_model():
         sh = out["scaling_model"][k]["shards"]
         assert set(sh) == {"2", "4", "8"} and all(v["predicted_speedup"] > 0 for v in sh.values())
         assert len(sh["8"]["render_ms_per_shard"]) == 8
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_the_timed_frame(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps steps in one window, prints the headline fields and nothing that needs
+    runs of its own, and --dump-outputs writes the frame the last timed step left: on the bits the CPU oracle's frame."""
+    import numpy as np
+    from ezrt_amd import scene as S, scenes, trace
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "64", "--height", "64",
+           "--spp", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["unit"] == "Mrays/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["value"] > 0
+    assert out["steps"] == 3 and len(out["timing"]["window_ms"]) == 1
+    assert abs(out["ms_per_step"] * 3 - out["timing"]["window_ms"][0]) < 1e-2
+    for k in ("parity", "roofline", "configs", "cpu_baseline", "scaling_model", "value_lone_call", "multi_gpu"):
+        assert k not in out, k
+    got = np.load(tmp_path / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 64, 4)
+    cfg = scenes.CONFIGS["C2"]
+    bs = scenes.bunny_scene(subdiv=2, want_cache=False, hdr="shipped")
+    eye, cam = S.camera(*cfg["camera"])
+    so = bs.upload(oracle)
+    want = so.render(trace.make_params(64, 64, eye, cam, cfg["integrator"], cfg["max_bounce"], spp=2))
+    so.close()
+    ua, ub = got.view(np.uint32), np.ascontiguousarray(want, np.float32).view(np.uint32)
+    assert ((ua == ub) | (np.isnan(got) & np.isnan(want))).all()

@@ -3,7 +3,7 @@
 for r in 1 2; do
   for n in default "$@"; do
     L=""; [ "$n" != default ] && L="EZRT_HIP_LIB=$PWD/ezrt_amd/lib/ab/libezrt_hip_$n.so"
-    echo -n "[$n]  "; env $L python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --extras 0 --configs none --model 0 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print(d['value'], d['ms_per_step'], d['roofline']['trace_ms_per_step'])"
+    echo -n "[$n]  "; env $L python bench.py --full --windows 7 --steps 20 --warmup 5 --cpu-seconds 0 --extras 0 --configs none --model 0 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print(d['value'], d['ms_per_step'], d['roofline']['trace_ms_per_step'])"
   done
 done
 for c in C3 C4 C5; do

@@ -5,7 +5,7 @@
 RND=${1:-r6}
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/final; mkdir -p $O; cd $R
 (time python -m pytest tests -m gpu -x -q) > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_before_profile.json 2> $O/bench_n1.err
+python bench.py --full --windows 7 --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_before_profile.json 2> $O/bench_n1.err
 bash tools/profile.sh $RND > $O/profile.log 2>&1
 python tools/summarize_profile.py gpurun_out/prof_$RND $O/final > $O/summarize.log 2>&1; tail -3 $O/summarize.log
 mkdir -p profiles/$RND; cp $O/final_kernel_stats.csv $O/final_pmc.json $O/pmc_summary.json profiles/$RND/ 2>/dev/null
@@ -14,10 +14,10 @@ mkdir -p profiles/$RND; cp $O/final_kernel_stats.csv $O/final_pmc.json $O/pmc_su
 bash tools/profile_configs.sh C3 C4 C5 > $O/profile_configs.log 2>&1; tail -6 $O/profile_configs.log
 cp gpurun_out/profcfg_summary/c?_kernel_stats.csv gpurun_out/profcfg_summary/c?_pmc_summary.json profiles/$RND/ 2>/dev/null
 (hipcc --offload-arch=gfx950 -O2 -o /tmp/exp_valu tools/exp_valu_issue.hip && timeout 300 /tmp/exp_valu quick) > $O/valu_issue_microbench.txt 2>&1; cp $O/valu_issue_microbench.txt profiles/$RND/ 2>/dev/null
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1b.err
+python bench.py --full --windows 7 --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1b.err
 mkdir -p gpurun_out/final/profiles_$RND; cp profiles/$RND/*pmc* profiles/$RND/*kernel_stats.csv profiles/$RND/valu_issue_microbench.txt gpurun_out/final/profiles_$RND/ 2>/dev/null
 for n in 2 8; do
-  EZRT_BENCH_BACKEND=gloo MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29650 + n)) bench.py --gpus $n --steps 5 --warmup 2 --windows 5 --cpu-seconds 0 > $O/bench_n${n}_gloo_one_gpu.json 2> $O/bench_n$n.err
+  EZRT_BENCH_BACKEND=gloo MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29650 + n)) bench.py --full --gpus $n --steps 5 --warmup 2 --windows 5 --cpu-seconds 0 > $O/bench_n${n}_gloo_one_gpu.json 2> $O/bench_n$n.err
 done
 rm -rf gpurun_out/prof_$RND/*/  # (raw traces stay on the box)
 python - <<'PY'

@@ -3,7 +3,7 @@
 TAG=${1:-run}; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 (time timeout 1500 python -m pytest tests -m gpu -x -q) > $O/pytest_gpu.log 2>&1; tail -5 $O/pytest_gpu.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 600 python bench.py --full --windows 7 --gpus 1 --steps 20 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
 python - <<PY
 import json
 try:

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 # kernel's duration in the trace would include waiting for wave slots held by the other chunk's launches; bench.py's own trace_ms_per_step
 # comes from a sequential pass too, and the counter passes serialise every dispatch anyway)
 export EZRT_PIPELINE_CALLS=0
-BENCH="python $R/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --extras 0 --configs none --model 0 $@"
+BENCH="python $R/bench.py --full --windows 7 --steps 2 --warmup 1 --cpu-seconds 0 --extras 0 --configs none --model 0 $@"
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $BENCH > $OUT/stats.log 2>&1
 i=0
 for PMC in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" \
