@@ -1,4 +1,4 @@
-"""ctypes declarations for the two C ABIs (include/ezrt.h, include/ezrt_scene_c.h).
+"""ctypes declarations for the C ABIs (include/ezrt.h, include/ezrt_scene_c.h, and the HIP library's own headers).
 
 `declare_trace_abi(lib)` attaches argtypes/restypes for every symbol of
 include/ezrt.h to an already-opened CDLL.  The product only ever opens
@@ -111,6 +111,13 @@ BUILD_ABI = {
 }
 
 
+# stream-ordered ray queries on device memory, libezrt_hip.so only (include/ezrt_query.h); pointers are device addresses
+QUERY_ABI = {
+    "ezrt_query_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ezrt_query_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
+
 # include/ezrt_mgpu.h: one process, N devices (both libraries: the oracle's "devices" are host memory)
 MGPU_ABI = {
     "ezrt_mgpu_create": (C.c_int, [c_float_p, C.c_int, c_float_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
@@ -163,7 +170,7 @@ def load_hip():
             raise RuntimeError(
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
-        _hip = _declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI)
+        _hip = _declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI)
     return _hip
 
 

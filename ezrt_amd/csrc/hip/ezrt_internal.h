@@ -255,6 +255,18 @@ struct Pipe {
   bool free_recorded = false;    // ev_free has been recorded at least once (pipeline_calls: the next user of this scratch set waits for it)
 };
 
+// Scratch of the stream-ordered ray queries (ezrt_query_closest_device / ezrt_query_occluded_device, include/ezrt_query.h): apart
+// from the render Pipes, so that a query may run while a render call of the same scene is in flight on another stream.  Grows to the
+// largest query (a growth frees the old buffers: hipFree synchronises the device); released with the scene.
+struct QueryScratch {
+  DevBuf<float4> rq_o, rq_d;                 // the ray queue (o.w = t_max for occlusion rays)
+  DevBuf<int2> hits;                         // hit records
+  DevBuf<uint32_t> redo_flag, redo_slots;    // redo list (redo_flag zeroed when allocated; the redo launch clears what it sets)
+  DevBuf<uint32_t> ctl;                      // queue length, redo count, reservation counters (zeroed by the pack kernel)
+  DevBuf<uint32_t> ovf;                      // traceq4 spill area of the traversal stacks
+  DevBuf<unsigned long long> counters;       // a private counter slot: queries leave ezrt_counters alone
+};
+
 struct EzrtScene {
   int n_tri = 0, n_nodes = 0;
   DevBuf<float4> tri_geom;
@@ -301,6 +313,7 @@ struct EzrtScene {
   // between them, each on its own stream, so one sub-chunk's latency-bound phases (the ends of the
   // persistent trace launches, the late bounces, launch gaps) run under the other's bulk work.
   Pipe pipe[ezh::SHARED_STREAMS]; // (two: deeper pipelines were measured in round 5 and removed in round 6)
+  QueryScratch query;           // ezrt_query_*_device
   int num_cus = 0;
   uint32_t chunk_seq = 0;     // chunks rendered so far (pipeline_calls: chunk i uses scratch set i & 1)
   bool chunk_pipelined = false; // the chunk being enqueued runs on a scratch set's own stream (set by ezrt_render_device)

@@ -2,6 +2,7 @@
 // budgets and workgroups per CU, chunks, the two scratch sets and their streams), the audit entry points (ezrt_render_paths,
 // ezrt_query_hits, ezrt_debug_math) and the small utility kernels (tone map, Sobol, non-finite count).  DESIGN.md 5.
 #include "ezrt_internal.h"
+#include "ezrt_query.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -201,11 +202,12 @@ int wps4(const EzrtScene* s, bool rel) {
   while (v > 4 && records_staged4(s, v) < std::min(s->tune.min_staged, s->n_inner4)) v--;
   return v;
 }
-// rel: the launch traverses boxes translated by a common origin (traceq4_kernel<.., true>)
-TraceCfg trace_cfg4(const EzrtScene* s, bool rel) {
+// rel: the launch traverses boxes translated by a common origin (traceq4_kernel<.., true>); wps > 0: workgroups per CU of a kernel
+// with another register budget (traceq4_occ_kernel) instead of wps4's
+TraceCfg trace_cfg4(const EzrtScene* s, bool rel, int wps = 0) {
   TraceCfg c;
   Tuning tu = s->tune;
-  tu.trace_wps = wps4(s, rel);
+  tu.trace_wps = wps > 0 ? wps : wps4(s, rel);
   c.lds = (size_t)stack_rows4(s) * BLOCK * sizeof(int);
   const size_t lds_fixed = c.lds + BLOCK * sizeof(int);
   int blocks_per_cu = tu.trace_wps > 0 ? tu.trace_wps : 5;
@@ -1122,6 +1124,143 @@ static int ezrt_query_hits_body(EzrtScene* s, const float* rays, int n_rays, int
 }
 int ezrt_query_hits(EzrtScene* s, const float* rays, int n_rays, int32_t* tri_id, float* t_hit) {
   return ezi::guarded("ezrt_query_hits", [&]() -> int { return ezrt_query_hits_body(s, rays, n_rays, tri_id, t_hit); });
+}
+
+// ---- stream-ordered queries on device memory (include/ezrt_query.h)
+// `bytes` of DEVICE memory of device `dev` at p.  hipPointerGetAttributes fails on plain host memory: that is a "no", and the error it
+// leaves is cleared so that the caller's next HIP call does not see it.  Where the runtime reports the allocation's extent, the
+// buffer must lie inside it.
+static bool device_buffer_of(const void* p, size_t bytes, int dev) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != dev) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;
+  }
+  return (const char*)p >= (const char*)base && bytes <= size - (size_t)((const char*)p - (const char*)base);
+}
+// occluded == NULL: closest hits into tri_id / t_hit.  The caller rays as one stage of a render call (the audit_via_queue route of
+// ezrt_query_hits) without its synchronisation and copies: query_dev_pack_kernel -> traceq4_kernel (or traceq4_occ_kernel, or the
+// binary traceq_kernel) -> the device-driven redo launch -> query_answer_kernel, all on `st`.
+static int query_device_body(EzrtScene* s, const float* rays, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,
+                             uint8_t* occluded, hipStream_t st) {
+  const size_t n = (size_t)(n_rays > 0 ? n_rays : 0);
+  // the scene's device: where its records live
+  hipPointerAttribute_t sat;
+  if (!s->tri_geom.p || hipPointerGetAttributes(&sat, s->tri_geom.p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EZRT_ERR_INVALID, "the scene has no device records");
+  }
+  const int dev = sat.device;
+  if (!device_buffer_of(rays, n * 6 * sizeof(float), dev) || (t_max && !device_buffer_of(t_max, n * sizeof(float), dev)) ||
+      (occluded && !device_buffer_of(occluded, n, dev)) || (tri_id && !device_buffer_of(tri_id, n * sizeof(int32_t), dev)) ||
+      (t_hit && !device_buffer_of(t_hit, n * sizeof(float), dev)))
+    return fail(EZRT_ERR_INVALID, "rays, t_max and outputs must be device memory of the scene's device (%d), %zu rays long", dev, n);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  struct Restore {
+    int d;
+    ~Restore() { (void)hipSetDevice(d); }
+  } restore{prev};
+  if (dev != prev) HIP_TRY(hipSetDevice(dev));
+  int rc = ensure_num_cus(s);
+  if (rc) return rc;
+
+  QueryScratch& q = s->query;
+  constexpr size_t HEAD_SLOT = (size_t)TRACE_HEADS * TRACE_HEAD_STRIDE;
+  constexpr size_t CTL_WORDS = TRACE_HEAD_STRIDE + 2 * HEAD_SLOT; // [0] queue length, [1] redo count; heads of the trace and redo launches
+  const bool wide = use_wide4(s);
+  // occlusion rays run the bounded any-hit kernel where the render calls run the nearest-first 4-wide traversal; elsewhere (binary
+  // kernel, pruning off or in slot order) they take the closest-hit route and query_answer_kernel compares with t_max: exact either way
+  const bool occ_kernel = occluded && wide && prune_mode(s) == 2;
+  const TraceCfg cfg = trace_cfg(s);
+  // (traceq4_occ_kernel runs at OCC_WPS waves per SIMD -- 90 VGPRs, no spills; at 6 it spilled 5 -- so at most that many workgroups per
+  // CU: a persistent launch must be resident all at once)
+  constexpr int OCC_WPS = 5;
+  const TraceCfg cfg4 = wide ? trace_cfg4(s, false, occ_kernel ? std::min(OCC_WPS, wps4(s, false)) : 0) : TraceCfg();
+  HIP_TRY(q.rq_o.ensure(n));
+  HIP_TRY(q.rq_d.ensure(n));
+  HIP_TRY(q.hits.ensure(n));
+  HIP_TRY(q.redo_slots.ensure(n));
+  if (q.redo_flag.n < n) {
+    HIP_TRY(q.redo_flag.ensure(n));
+    HIP_TRY(hipMemsetAsync(q.redo_flag.p, 0, q.redo_flag.n * sizeof(uint32_t), st));
+  }
+  HIP_TRY(q.ctl.ensure(CTL_WORDS));
+  if (!q.counters.p) {
+    HIP_TRY(q.counters.ensure((size_t)CTR_SLOTS * EZRT_CTR_COUNT));
+    HIP_TRY(hipMemsetAsync(q.counters.p, 0, q.counters.n * sizeof(unsigned long long), st));
+  }
+  if (wide) HIP_TRY(q.ovf.ensure((size_t)cfg4.grid_full * BLOCK * (size_t)std::max(OVF_CAP, ovf_cap4(s))));
+
+  const unsigned g1 = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(query_dev_pack_kernel, dim3(g1), dim3(256), 0, st, rays, t_max, (uint32_t)n, occ_kernel ? 1u : 0u, q.rq_o.p,
+                     q.rq_d.p, q.ctl.p, (uint32_t)CTL_WORDS);
+  TraceQArgs t;
+  t.sc = trace_scene(s->dev());
+  t.rq.o = q.rq_o.p;
+  t.rq.d = q.rq_d.p;
+  t.hits = q.hits.p;
+  t.n_paths = q.ctl.p;
+  t.rays_per_path = 1u;
+  t.const_origin = 0u;
+  t.inner_rel = nullptr;
+  t.origin[0] = t.origin[1] = t.origin[2] = 0.0f;
+  t.head = q.ctl.p + TRACE_HEAD_STRIDE;
+  t.counters = q.counters.p;
+  fill_trace_knobs(s, cfg, t);
+  t.dbg = nullptr;
+  t.slot_map = nullptr;
+  t.steal = s->tune.steal ? 1u : 0u;
+  t.count_rays = 0u;
+  t.redo_count = q.ctl.p + 1;
+  t.redo_slots = q.redo_slots.p;
+  t.redo_flag = q.redo_flag.p;
+  t.force_pending = 0u;
+  t.wave_log = nullptr;
+  const int launches = s->n_trace_launches; // (the launch helpers count render launches: ezrt_last_render_ms reports them)
+  if (occ_kernel) {
+    TraceQ4Args A;
+    fill_traceq4_args(s, cfg4, t, nullptr, nullptr, q.ovf.p, A);
+    hipLaunchKernelGGL((traceq4_occ_kernel<OCC_WPS>), dim3(cfg4.grid_full), dim3(BLOCK), cfg4.lds_t, st, A);
+  } else if (wide) {
+    launch_traceq4_cfg(s, cfg4, t, nullptr, st, nullptr, q.ovf.p);
+  } else {
+    launch_traceq_cfg(s, cfg, t, false, st);
+  }
+  if (t.steal || wide) { // exact ties, rays that are not tame, full spill areas: the in-order kernel, its queue length on the device
+    TraceQArgs r = t;
+    r.steal = 0u;
+    r.slot_map = q.redo_slots.p;
+    r.n_paths = q.ctl.p + 1;
+    r.head = q.ctl.p + TRACE_HEAD_STRIDE + HEAD_SLOT;
+    launch_traceq_cfg(s, cfg, r, true, st);
+  }
+  s->n_trace_launches = launches;
+  hipLaunchKernelGGL(query_answer_kernel, dim3(g1), dim3(256), 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int ezrt_query_closest_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,
+                              void* stream) {
+  return ezi::guarded("ezrt_query_closest_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || !t_hit || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
+    if (n_rays == 0) return 0;
+    return query_device_body(s, rays_od6, t_max, n_rays, tri_id, t_hit, nullptr, (hipStream_t)stream);
+  });
+}
+int ezrt_query_occluded_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, uint8_t* occluded, void* stream) {
+  return ezi::guarded("ezrt_query_occluded_device", [&]() -> int {
+    if (!s || !rays_od6 || !occluded || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
+    if (n_rays == 0) return 0;
+    return query_device_body(s, rays_od6, t_max, n_rays, nullptr, nullptr, occluded, (hipStream_t)stream);
+  });
 }
 
 static int ezrt_tonemap_body(const float* rgba, int n_pixels, uint8_t* rgb8) {

@@ -226,9 +226,16 @@ EZD bool tie_precedes(const TraceQ4Args& A, int32_t tri_a, int32_t tri_b, f3 S, 
 // SEMI: rays with an exactly-zero direction component are traversed here (with the NaN watch) instead of sent to the redo
 // list.  A template parameter because the watch costs every ray of the launch 2-3 % (a ballot per iteration, four flags,
 // registers); the host turns it on for the launches that see such rays in numbers: the MIS integrators' bounce stages.
-template <bool REL, bool LOG, int PRUNE, bool GEN, bool SEMI = false, bool GS = false>
+// OCC (traceq4_occ_kernel only; DESIGN.md 5 "Occlusion queries"): every ray is a bounded any-hit query.  Its extent t_max rides in the
+// queue's o.w (unused otherwise); the ray starts with best_t = t_max, takes the first triangle accepted with t < t_max and ends there.
+// A candidate at exactly t_max is no hit and never a tie; pruning against t_max is the proof above with best_t := t_max.  A thief
+// starts from its victim's best_t, which is t_max itself while the victim has pending subtrees (its first hit ends it).  The hit
+// record holds {-1, t_max} or A hit below t_max; rays sent to the redo list come back with their closest hit, and the query's unpack
+// kernel answers t < t_max for all of them.
+template <bool REL, bool LOG, int PRUNE, bool GEN, bool SEMI = false, bool GS = false, bool OCC = false>
 EZD void traceq4_body(const TraceQ4Args& A) {
   static_assert(!GEN || REL, "generated rays start at the launch's uniform origin");
+  static_assert(!OCC || (!REL && !LOG && PRUNE == 2), "occlusion rays carry their own origin and t_max; nearest-first order only");
   extern __shared__ __attribute__((aligned(16))) int lds_stack[];
   const TraceQArgs& a = A.q;
   // LDS layout: [lane table: BLOCK ints][stack rows][staged records]
@@ -322,7 +329,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
       if (best_tri >= 0) {
         const unsigned long long key = ((unsigned long long)__float_as_uint(best_t) << 32) | (uint32_t)best_tri;
         const unsigned long long old = atomicMin(&hits64[slot], key);
-        if ((uint32_t)(old >> 32) == (uint32_t)(key >> 32) && (uint32_t)old != (uint32_t)key) tie = true;
+        if (!OCC && (uint32_t)(old >> 32) == (uint32_t)(key >> 32) && (uint32_t)old != (uint32_t)key) tie = true;
       }
     } else {
       a.hits[slot] = make_int2(best_tri, __float_as_int(best_t));
@@ -341,7 +348,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
       tie_tri = -1; // (a tie at a distance that has just been beaten does not matter any more)
       // (a thief's threshold may come from a hit another contributor of its ray found, which can be closer than this one)
       if (PRUNE) prune_t = hw_min(prune_t, (t + pdelta) * PRUNE_REL);
-    } else if (t == best_t && tri != best_tri) {
+    } else if (!OCC && t == best_t && tri != best_tri) { // (OCC: t == t_max is no hit, and any hit below it is the answer)
       if (A.tri_leaf && tie_tri < 0) tie_tri = tri; // ordered against best_tri at publish (tie_precedes)
       else if (tri != tie_tri) tie = true;           // a third candidate (or no tables): the redo list
     }
@@ -370,7 +377,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           S = REL ? mk(a.origin[0], a.origin[1], a.origin[2]) : mk(nx_o.x, nx_o.y, nx_o.z);
           d = mk(nx_d.x, nx_d.y, nx_d.z);
           inv = mk(ez_rcp(d.x), ez_rcp(d.y), ez_rcp(d.z));
-          best_t = INF;
+          best_t = OCC ? nx_o.w : INF;
           best_tri = -1;
           sp = 0;
           sb = 0;
@@ -462,14 +469,15 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           const int src = taker ? wsrc[ir0] : lane;
           const uint32_t hs = (uint32_t)__shfl((int)nx_slot, src, 64);
           const float hdx = __shfl(nx_d.x, src, 64), hdy = __shfl(nx_d.y, src, 64), hdz = __shfl(nx_d.z, src, 64), hdw = __shfl(nx_d.w, src, 64);
-          float hox = 0.0f, hoy = 0.0f, hoz = 0.0f;
+          float hox = 0.0f, hoy = 0.0f, hoz = 0.0f, how = 0.0f;
           if (!REL) hox = __shfl(nx_o.x, src, 64), hoy = __shfl(nx_o.y, src, 64), hoz = __shfl(nx_o.z, src, 64);
+          if (OCC) how = __shfl(nx_o.w, src, 64); // (t_max)
           __builtin_amdgcn_wave_barrier();
           if (giver) nx_slot = REF_NONE;
           if (taker) { // (adopted by the next refill, like a ray this lane had prefetched itself)
             nx_slot = hs;
             nx_d = make_float4(hdx, hdy, hdz, hdw);
-            if (!REL) nx_o = make_float4(hox, hoy, hoz, 0.0f);
+            if (!REL) nx_o = make_float4(hox, hoy, hoz, how);
           }
         }
       }
@@ -503,7 +511,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           // the victim's best hit so far bounds the thief's pruning too (knob steal_bound; round 5): a real hit of the SAME ray, so the
           // final minimum is no larger and the proven margin applies -- the oldest pending row is the farthest subtree under the
           // nearest-first order, the one most likely to lie wholly behind that hit, and the thief used to walk it with best_t = INF
-          const float vbt = (PRUNE && A.steal_bound) ? __shfl(best_t, src, 64) : INF;
+          const float vbt = (OCC || (PRUNE && A.steal_bound)) ? __shfl(best_t, src, 64) : INF;
           if (thief) {
             semi = vsemi != 0;
             anyhit = vany != 0;
@@ -512,7 +520,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
             S = mk(vsx, vsy, vsz);
             d = mk(vdx, vdy, vdz);
             inv = mk(ez_rcp(vdx), ez_rcp(vdy), ez_rcp(vdz));
-            best_t = INF;
+            best_t = OCC ? vbt : INF; // (OCC: the victim's t_max -- it has no hit yet, or it would have ended)
             best_tri = -1;
             sp = 0;
             sb = 0;
@@ -714,7 +722,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           }
         }
         if (at_leaf) {
-          if (anyhit && best_tri >= 0) finish(); // (an env shadow ray that has hit something is done: only isHit is asked of it)
+          if ((OCC || anyhit) && best_tri >= 0) finish(); // (an env shadow ray that has hit something is done: only isHit is asked of it)
           else pop_or_finish();
         }
       }
@@ -745,6 +753,12 @@ EZD void traceq4_body(const TraceQ4Args& A) {
 template <int WPS, bool REL, bool LOG = false, int PRUNE = 0, bool GEN = false, bool SEMI = false, bool GS = false>
 __global__ __launch_bounds__(BLOCK, WPS) void traceq4_kernel(TraceQ4Args A) {
   traceq4_body<REL, LOG, PRUNE, GEN, SEMI, GS>(A);
+}
+// ezrt_query_occluded_device: bounded any-hit rays (OCC above) in the bounce stages' schedule -- own origins, nearest-first order with
+// pruning, scattered draw -- with the NaN watch for rays with a zero direction component (SEMI)
+template <int WPS>
+__global__ __launch_bounds__(BLOCK, WPS) void traceq4_occ_kernel(TraceQ4Args A) {
+  traceq4_body<false, false, 2, false, true, true, true>(A);
 }
 
 } // namespace ezd

@@ -772,4 +772,39 @@ __global__ void query_unpack_kernel(const int2* hits, uint32_t n, int32_t* tri, 
   t[i] = h.x >= 0 ? __int_as_float(h.y) : INF;
 }
 
+// ezrt_query_closest_device / ezrt_query_occluded_device (stream-ordered, rays already in device memory).  A ray whose t_max
+// cannot be beaten -- NaN, or <= 0.0005, the smallest distance hit_triangle_t accepts -- enters the queue dead (d.w = 0: never
+// adopted) and is answered "miss" by query_answer_kernel without a hit record.  occ: min(t_max, INF) goes to o.w (traceq4_occ_kernel).
+// ctl: [0] the queue length, [1] the redo count, [2, n_zero) the reservation counters of the trace and redo launches (zeroed).
+EZD bool query_live(const float* tmax, uint32_t i) { return !tmax || tmax[i] > 0.0005f; }
+__global__ void query_dev_pack_kernel(const float* rays, const float* tmax, uint32_t n, uint32_t occ, float4* o, float4* d, uint32_t* ctl,
+                                      uint32_t n_zero) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  for (uint32_t k = i + 1u; k < n_zero; k += gridDim.x * blockDim.x) ctl[k] = 0u;
+  if (i == 0) ctl[0] = n;
+  if (i >= n) return;
+  const float* r = rays + (size_t)i * 6;
+  // (the reference's traversal starts at best_t = INF: nothing at INF or beyond is a hit, so an occlusion ray's extent is capped there)
+  const float tm = tmax ? tmax[i] : INF;
+  o[i] = make_float4(r[0], r[1], r[2], occ ? (tm < INF ? tm : INF) : 0.0f);
+  d[i] = make_float4(r[3], r[4], r[5], query_live(tmax, i) ? 1.0f : 0.0f);
+}
+// hit records -> the caller's outputs: {tri, t} of the hits below t_max, else a miss {-1, INF} (occ == NULL), or occ[i] = 1 for them
+__global__ void query_answer_kernel(const int2* hits, const float* tmax, uint32_t n, int32_t* tri, float* t, uint8_t* occ) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bool hit = false;
+  int2 h = make_int2(-1, 0);
+  if (query_live(tmax, i)) {
+    h = hits[i];
+    hit = h.x >= 0 && (!tmax || __int_as_float(h.y) < tmax[i]);
+  }
+  if (occ) {
+    occ[i] = hit ? 1u : 0u;
+  } else {
+    tri[i] = hit ? h.x : -1;
+    t[i] = hit ? __int_as_float(h.y) : INF;
+  }
+}
+
 } // namespace ezd
