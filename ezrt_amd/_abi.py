@@ -95,6 +95,7 @@ HOST_ABI = {
     "ezrt_host_camera": (C.c_int, [C.c_float, C.c_float, C.c_float, c_float_p, c_float_p]),
     "ezrt_host_p2_query": (C.c_int, [c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_float_p,
                                      C.POINTER(C.c_int), c_float_p]),
+    "ezrt_host_refit_nodes": (C.c_int, [c_float_p, C.c_int, c_float_p, C.c_int, c_float_p]),
     "ezrt_host_last_error": (C.c_char_p, []),
 }
 
@@ -115,6 +116,12 @@ BUILD_ABI = {
 QUERY_ABI = {
     "ezrt_query_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ezrt_query_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
+
+# device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
+REFIT_ABI = {
+    "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 
@@ -170,7 +177,7 @@ def load_hip():
             raise RuntimeError(
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
-        _hip = _declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI)
+        _hip = _declare(_declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI), REFIT_ABI)
     return _hip
 
 

@@ -4,6 +4,7 @@
 //                         reference's leaves, the 4-wide collapse, the per-triangle pruning bounds
 //   ezrt_launch.hip       every kernel launch: the launch policy of a render call (variants, LDS budgets, chunks, streams), the audit
 //                         entry points and the small utility kernels
+//   ezrt_refit.hip        ezrt_scene_refit_device: new vertex positions into an existing scene over the topology create kept
 // Types only -- no kernel is defined here (a __global__ function may live in one translation unit only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,6 +52,82 @@ inline int guarded(const char* what, F body) noexcept {
   } catch (...) {
     return fail(EZRT_ERR_DEVICE, "%s failed: unknown exception", what);
   }
+}
+} // namespace ezi
+
+namespace ezi {
+// a node of the caller's arrays (decoded) or of the library's own tree over its leaves (ezrt_scene_build.hip: retree_leaves)
+struct HostNode {
+  int left, right, n, index;
+  float AA[3], BB[3];
+};
+
+// Per-triangle records that are functions of the vertices alone: shared by ezrt_scene_create (host) and the refit's per-triangle
+// kernel (ezrt_refit.hip), so that both evaluate the same operations in the same order (contraction is off in every build).
+// N = normalize(cross(p2 - p1, p3 - p1)), P5/fsh:172 -- same fp32 ops
+__host__ __device__ inline void tri_normal(const float* t, float& nx, float& ny, float& nz) {
+  float e1x = t[3] - t[0], e1y = t[4] - t[1], e1z = t[5] - t[2];
+  float e2x = t[6] - t[0], e2y = t[7] - t[1], e2z = t[8] - t[2];
+  float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+  float inv = 1.0f / __builtin_sqrtf(cx * cx + cy * cy + cz * cz);
+  nx = cx * inv;
+  ny = cy * inv;
+  nz = cz * inv;
+}
+// Distance pruning's per-triangle bound eta_T (ezrt_traceq4.h "Distance pruning"), in double precision.  kind 0: no hit can be
+// accepted (NaN / inf / zero normal: eta = 0); 1: no bound (eta = +inf, a triangle that is not ordinary); 2: a bound.
+struct PruneEta {
+  double eta, m_t, inv_smin, zeta;
+  int kind;
+};
+__host__ __device__ inline PruneEta prune_eta(const float* t, float nx_f, float ny_f, float nz_f) {
+  const double eps = 1.0 / 16777216.0, dinf = (double)__builtin_inff();
+  PruneEta r;
+  r.eta = 0.0;
+  r.inv_smin = 0.0;
+  r.zeta = 0.0;
+  r.kind = 0;
+  double p[3][3], n[3] = {(double)nx_f, (double)ny_f, (double)nz_f}, m_t = 0.0;
+  for (int v = 0; v < 3; v++)
+    for (int c = 0; c < 3; c++) {
+      p[v][c] = (double)t[v * 3 + c];
+      m_t = __builtin_fmax(m_t, p[v][c] < 0 ? -p[v][c] : p[v][c]);
+    }
+  r.m_t = m_t;
+  const double nn = __builtin_sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  if (!(nn == nn) || nn > 1e300 || nn == 0.0) return r; // NaN / inf / zero normal: hit_triangle_t can never accept it (eta = 0)
+  r.eta = dinf;                                          // until proven otherwise
+  r.kind = 1;
+  if (!(m_t < 1e30) || !(nn > 0.5 && nn < 2.0)) return r; // a stored normal that is not unit (underflow in the cross product): no bound
+  double u[3] = {n[0] / nn, n[1] / nn, n[2] / nn}, q[3][3], zeta = 0.0;
+  for (int v = 0; v < 3; v++) {
+    const double h = u[0] * (p[v][0] - p[0][0]) + u[1] * (p[v][1] - p[0][1]) + u[2] * (p[v][2] - p[0][2]);
+    for (int c = 0; c < 3; c++) q[v][c] = p[v][c] - u[c] * h;
+    zeta = __builtin_fmax(zeta, h < 0 ? -h : h);
+  }
+  double smin = 1.0, diam = 0.0, emin = dinf; // min sin(angle / 2), longest and shortest edge of the projected triangle
+  for (int v = 0; v < 3; v++) {
+    const double* o = q[v];
+    const double* e = q[(v + 1) % 3];
+    const double* f = q[(v + 2) % 3];
+    const double a[3] = {e[0] - o[0], e[1] - o[1], e[2] - o[2]}, b[3] = {f[0] - o[0], f[1] - o[1], f[2] - o[2]};
+    const double la = __builtin_sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = __builtin_sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+    diam = __builtin_fmax(diam, la);
+    emin = __builtin_fmin(emin, la);
+    if (!(la > 0.0 && lb > 0.0)) {
+      smin = 0.0;
+      break;
+    }
+    double c = (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]) / (la * lb);
+    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+    smin = __builtin_fmin(smin, __builtin_sqrt((1.0 - c) * 0.5));
+  }
+  if (!(smin >= 1e-4) || !(zeta <= 1e-3 * emin)) return r; // thinner than ~0.01 degrees, or bent off its stored plane: no bound
+  r.eta = zeta + 15.2 * eps * (diam + zeta) / smin + 19.8 * eps * m_t;
+  r.inv_smin = 1.0 / smin;
+  r.zeta = zeta;
+  r.kind = 2;
+  return r;
 }
 } // namespace ezi
 
@@ -265,6 +342,35 @@ struct QueryScratch {
   DevBuf<uint32_t> ctl;                      // queue length, redo count, reservation counters (zeroed by the pack kernel)
   DevBuf<uint32_t> ovf;                      // traceq4 spill area of the traversal stacks
   DevBuf<unsigned long long> counters;       // a private counter slot: queries leave ezrt_counters alone
+  hipEvent_t ev_end = nullptr;               // recorded behind every query's last kernel: a refit waits for it (ezrt_refit.h)
+};
+
+// What ezrt_scene_refit_device (ezrt_refit.hip) walks: the topology ezrt_scene_create keeps (host vectors, moved out of create's own
+// work arrays) and, from the first refit on, its device copy and the refit's scratch.  Nothing here is read by a render or a query.
+struct RefitTree { // one binary tree, bottom-up: node ids in order of height (leaves first), level k = [level_off[k], level_off[k+1])
+  DevBuf<int4> nodes;              // (left, right, n, index) per node id
+  DevBuf<int32_t> order;
+  std::vector<int> level_off;
+  DevBuf<float4> box;              // per node: (AA, -), (BB, -)
+  DevBuf<double> eta_max;          // per node: max eta_T of the triangles below it
+};
+struct RefitState {
+  int is_dag = 0;                  // the caller's arrays have a node with two parents: refused
+  bool ready = false;              // the device topology below is complete
+  RefitTree caller, own;           // the caller's tree; retree_leaves' tree (retreed scenes only)
+  DevBuf<int4> bin_recs;           // per inner node of the caller's tree: (binary record, left, right, -)
+  DevBuf<int4> rec4_slots;         // per 4-wide record: the tree node of each slot (0 = unused)
+  DevBuf<double> eta, m_t, sorted; // per triangle; `sorted`: 2 x n_tri, the sorted copies of both
+  DevBuf<unsigned char> sort_tmp;
+  size_t sort_tmp_bytes = 0;
+  DevBuf<unsigned long long> ctl;  // reductions and the pruning scalars (ezrt_refit.hip: RCTL_*)
+  unsigned long long* ctl_host = nullptr; // pinned read-back of ctl
+  hipEvent_t ev_pipe[ezh::SHARED_STREAMS] = {};
+  ~RefitState() {
+    if (ctl_host) (void)hipHostFree(ctl_host);
+    for (hipEvent_t& e : ev_pipe)
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
 struct EzrtScene {
@@ -314,6 +420,12 @@ struct EzrtScene {
   // persistent trace launches, the late bounces, launch gaps) run under the other's bulk work.
   Pipe pipe[ezh::SHARED_STREAMS]; // (two: deeper pipelines were measured in round 5 and removed in round 6)
   QueryScratch query;           // ezrt_query_*_device
+  // topology for ezrt_scene_refit_device (ezrt_refit.h), kept by ezrt_scene_create
+  std::vector<ezi::HostNode> topo_nodes;            // the caller's nodes as decoded at create (only topology and ranges are read)
+  std::vector<int> topo_inner_id;                   // binary record of each inner node (-1: a leaf)
+  std::vector<ezi::HostNode> topo_tree4;            // retree_leaves' tree (retreed scenes only: else the 4-wide records cut the caller's)
+  std::vector<std::array<int, 4>> topo_rec_slots;   // per 4-wide record: tree node of each slot, 0 = unused
+  RefitState* refit = nullptr;
   int num_cus = 0;
   uint32_t chunk_seq = 0;     // chunks rendered so far (pipeline_calls: chunk i uses scratch set i & 1)
   bool chunk_pipelined = false; // the chunk being enqueued runs on a scratch set's own stream (set by ezrt_render_device)
@@ -357,4 +469,6 @@ inline int prune_mode(const EzrtScene* s) {
 namespace ezi {
 // ezrt_launch.hip
 __attribute__((visibility("hidden"))) void release_chunk_scratch(Pipe& pp);
+// `bytes` of DEVICE memory of device `dev` at p (the pointer check of the stream-ordered entry points: ezrt_query.h, ezrt_refit.h)
+__attribute__((visibility("hidden"))) bool device_buffer_of(const void* p, size_t bytes, int dev);
 } // namespace ezi

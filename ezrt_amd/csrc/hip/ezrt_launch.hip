@@ -1130,7 +1130,8 @@ int ezrt_query_hits(EzrtScene* s, const float* rays, int n_rays, int32_t* tri_id
 // `bytes` of DEVICE memory of device `dev` at p.  hipPointerGetAttributes fails on plain host memory: that is a "no", and the error it
 // leaves is cleared so that the caller's next HIP call does not see it.  Where the runtime reports the allocation's extent, the
 // buffer must lie inside it.
-static bool device_buffer_of(const void* p, size_t bytes, int dev) {
+} // extern "C"
+bool ezi::device_buffer_of(const void* p, size_t bytes, int dev) {
   hipPointerAttribute_t at;
   if (hipPointerGetAttributes(&at, p) != hipSuccess) {
     (void)hipGetLastError();
@@ -1145,6 +1146,7 @@ static bool device_buffer_of(const void* p, size_t bytes, int dev) {
   }
   return (const char*)p >= (const char*)base && bytes <= size - (size_t)((const char*)p - (const char*)base);
 }
+extern "C" {
 // occluded == NULL: closest hits into tri_id / t_hit.  The caller rays as one stage of a render call (the audit_via_queue route of
 // ezrt_query_hits) without its synchronisation and copies: query_dev_pack_kernel -> traceq4_kernel (or traceq4_occ_kernel, or the
 // binary traceq_kernel) -> the device-driven redo launch -> query_answer_kernel, all on `st`.
@@ -1158,6 +1160,7 @@ static int query_device_body(EzrtScene* s, const float* rays, const float* t_max
     return fail(EZRT_ERR_INVALID, "the scene has no device records");
   }
   const int dev = sat.device;
+  using ezi::device_buffer_of;
   if (!device_buffer_of(rays, n * 6 * sizeof(float), dev) || (t_max && !device_buffer_of(t_max, n * sizeof(float), dev)) ||
       (occluded && !device_buffer_of(occluded, n, dev)) || (tri_id && !device_buffer_of(tri_id, n * sizeof(int32_t), dev)) ||
       (t_hit && !device_buffer_of(t_hit, n * sizeof(float), dev)))
@@ -1245,6 +1248,9 @@ static int query_device_body(EzrtScene* s, const float* rays, const float* t_max
   s->n_trace_launches = launches;
   hipLaunchKernelGGL(query_answer_kernel, dim3(g1), dim3(256), 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
   HIP_TRY(hipGetLastError());
+  // the end of this query on its stream: a refit of the scene (ezrt_refit.h) makes its own stream wait for it
+  if (!q.ev_end) HIP_TRY(hipEventCreateWithFlags(&q.ev_end, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(q.ev_end, st));
   return 0;
 }
 int ezrt_query_closest_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,

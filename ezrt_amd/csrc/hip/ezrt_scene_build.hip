@@ -45,10 +45,7 @@ void parallel_for(int n, int grain, F f) {
 }
 constexpr int PAR_MAX = 16; // threads of parallel_for at most (per-thread partial results are arrays of this size)
 
-struct HostNode {
-  int left, right, n, index;
-  float AA[3], BB[3];
-};
+using ezi::HostNode;
 HostNode decode_node(const float* nodes, int i) {
   const float* p = nodes + (size_t)i * EZRT_NODE_FLOATS;
   HostNode h;
@@ -379,6 +376,7 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   std::vector<float4> inner4;
   std::vector<std::array<int, 4>> rec_slot_nodes; // per record (in its final numbering): tree4's node of each slot, 0 = unused
   std::vector<HostNode> tree4;                    // the binary tree the records are a collapse of: the reference's, or retree_leaves'
+  std::vector<HostNode> hn_kept;                  // the decoded caller nodes, kept for ezrt_scene_refit_device
   bool retreed = false;
   int n_inner4 = 0, stack_need4 = 1;
   {
@@ -523,6 +521,7 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
       }
       if (!retreed || ((size_t)stack_need4 + 4) * BLOCK * sizeof(int) <= 60 * 1024) break; // (the bound of use_wide4)
     }
+    hn_kept = std::move(hn);
   }
   lap("re-tree + 4-wide collapse");
   // ---- tables of tie_precedes (ezrt_traceq4.h): only for arrays that are a tree with nested boxes (the 4-wide records exist)
@@ -562,14 +561,11 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   parallel_for(n_tri, 1 << 15, [&](int lo_i, int hi_i, int) {
   for (int i = lo_i; i < hi_i; i++) {
     const float* t = tri + (size_t)i * EZRT_TRI_FLOATS;
-    // N = normalize(cross(p2 - p1, p3 - p1)), P5/fsh:172 -- same fp32 ops, contraction off
-    float e1x = t[3] - t[0], e1y = t[4] - t[1], e1z = t[5] - t[2];
-    float e2x = t[6] - t[0], e2y = t[7] - t[1], e2z = t[8] - t[2];
-    float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-    float inv = 1.0f / __builtin_sqrtf(cx * cx + cy * cy + cz * cz);
-    geom[(size_t)i * 3 + 0] = make_float4(t[0], t[1], t[2], cx * inv);
-    geom[(size_t)i * 3 + 1] = make_float4(t[3], t[4], t[5], cy * inv);
-    geom[(size_t)i * 3 + 2] = make_float4(t[6], t[7], t[8], cz * inv);
+    float nx, ny, nz; // N = normalize(cross(p2 - p1, p3 - p1)), P5/fsh:172 (ezi::tri_normal: shared with the refit)
+    ezi::tri_normal(t, nx, ny, nz);
+    geom[(size_t)i * 3 + 0] = make_float4(t[0], t[1], t[2], nx);
+    geom[(size_t)i * 3 + 1] = make_float4(t[3], t[4], t[5], ny);
+    geom[(size_t)i * 3 + 2] = make_float4(t[6], t[7], t[8], nz);
   }
   });
 
@@ -595,59 +591,25 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   }
   lap("  leaf boxes hold their triangles");
   if (prunable) {
-    const double eps = 1.0 / 16777216.0, dinf = (double)__builtin_inff();
+    const double dinf = (double)__builtin_inff();
     std::vector<double> eta((size_t)n_tri, 0.0);
     double part_M[PAR_MAX] = {0}, part_G[PAR_MAX] = {0}, part_Z[PAR_MAX] = {0}; // per-thread maxima and counts (order-independent)
     int64_t part_bad[PAR_MAX] = {0};
     parallel_for(n_tri, 1 << 14, [&](int lo_i, int hi_i, int tid) {
     double prune_M = 0.0, prune_G = 0.0, prune_Z = 0.0; // (this thread's)
     int64_t prune_bad = 0;
-    for (int i = lo_i; i < hi_i; i++) {
-      const float* t = tri + (size_t)i * EZRT_TRI_FLOATS;
-      double p[3][3], n[3] = {(double)geom[(size_t)i * 3].w, (double)geom[(size_t)i * 3 + 1].w, (double)geom[(size_t)i * 3 + 2].w}, m_t = 0.0;
-      for (int v = 0; v < 3; v++)
-        for (int c = 0; c < 3; c++) {
-          p[v][c] = (double)t[v * 3 + c];
-          m_t = __builtin_fmax(m_t, p[v][c] < 0 ? -p[v][c] : p[v][c]);
-        }
-      prune_M = __builtin_fmax(prune_M, m_t);
-      const double nn = __builtin_sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-      if (!(nn == nn) || nn > 1e300 || nn == 0.0) continue; // NaN / inf / zero normal: hit_triangle_t can never accept it (eta = 0)
-      eta[(size_t)i] = dinf;                                  // until proven otherwise
-      if (!(m_t < 1e30) || !(nn > 0.5 && nn < 2.0)) { // a stored normal that is not unit (underflow in the cross product): no bound
+    for (int i = lo_i; i < hi_i; i++) { // (ezi::prune_eta: the bound's arithmetic, shared with the refit)
+      const ezi::PruneEta e = ezi::prune_eta(tri + (size_t)i * EZRT_TRI_FLOATS, geom[(size_t)i * 3].w, geom[(size_t)i * 3 + 1].w,
+                                             geom[(size_t)i * 3 + 2].w);
+      prune_M = __builtin_fmax(prune_M, e.m_t);
+      if (e.kind == 0) continue; // no hit can be accepted: eta = 0
+      eta[(size_t)i] = e.eta;
+      if (e.kind == 1) { // not ordinary: eta = +inf
         prune_bad++;
         continue;
       }
-      double u[3] = {n[0] / nn, n[1] / nn, n[2] / nn}, q[3][3], zeta = 0.0;
-      for (int v = 0; v < 3; v++) {
-        const double h = u[0] * (p[v][0] - p[0][0]) + u[1] * (p[v][1] - p[0][1]) + u[2] * (p[v][2] - p[0][2]);
-        for (int c = 0; c < 3; c++) q[v][c] = p[v][c] - u[c] * h;
-        zeta = __builtin_fmax(zeta, h < 0 ? -h : h);
-      }
-      double smin = 1.0, diam = 0.0, emin = dinf; // min sin(angle / 2), longest and shortest edge of the projected triangle
-      for (int v = 0; v < 3; v++) {
-        const double* o = q[v];
-        const double* e = q[(v + 1) % 3];
-        const double* f = q[(v + 2) % 3];
-        const double a[3] = {e[0] - o[0], e[1] - o[1], e[2] - o[2]}, b[3] = {f[0] - o[0], f[1] - o[1], f[2] - o[2]};
-        const double la = __builtin_sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = __builtin_sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-        diam = __builtin_fmax(diam, la);
-        emin = __builtin_fmin(emin, la);
-        if (!(la > 0.0 && lb > 0.0)) {
-          smin = 0.0;
-          break;
-        }
-        double c = (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]) / (la * lb);
-        c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-        smin = __builtin_fmin(smin, __builtin_sqrt((1.0 - c) * 0.5));
-      }
-      if (!(smin >= 1e-4) || !(zeta <= 1e-3 * emin)) { // thinner than ~0.01 degrees, or bent off its stored plane: no bound
-        prune_bad++;
-        continue;
-      }
-      eta[(size_t)i] = zeta + 15.2 * eps * (diam + zeta) / smin + 19.8 * eps * m_t;
-      prune_G = __builtin_fmax(prune_G, 1.0 / smin);
-      prune_Z = __builtin_fmax(prune_Z, zeta);
+      prune_G = __builtin_fmax(prune_G, e.inv_smin);
+      prune_Z = __builtin_fmax(prune_Z, e.zeta);
     }
     part_M[tid] = prune_M;
     part_G[tid] = prune_G;
@@ -864,6 +826,11 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   }
   SC_TRY(hipMemset(s->counters.p, 0, (size_t)CTR_SLOTS * EZRT_CTR_COUNT * sizeof(unsigned long long)));
 #undef SC_TRY
+  // the topology a refit walks (moves, not copies: ezrt_refit.hip uploads it at the first refit)
+  s->topo_nodes = std::move(hn_kept);
+  s->topo_inner_id = std::move(inner_id);
+  if (retreed) s->topo_tree4 = std::move(tree4);
+  s->topo_rec_slots = std::move(rec_slot_nodes);
   lap("device allocation + upload");
   s->stats[0] = n_tri;
   s->stats[1] = n_nodes;

@@ -262,6 +262,39 @@ int ezrt_host_p2_query(const float* tri9, int n_tri, int method, int leaf_n, con
   EZ_CATCH
 }
 
+int ezrt_host_refit_nodes(const float* tri36, int n_tri, const float* nodes_in, int n_nodes, float* nodes_out) {
+  if (!tri36 || !nodes_in || !nodes_out || n_tri < 0 || n_nodes < 1) return fail(-1, "bad argument");
+  EZ_TRY
+  std::vector<Triangle> tris((size_t)n_tri);
+  for (int i = 0; i < n_tri; i++) {
+    const float* p = tri36 + (size_t)i * 36;
+    tris[(size_t)i].p1 = vec3(p[0], p[1], p[2]);
+    tris[(size_t)i].p2 = vec3(p[3], p[4], p[5]);
+    tris[(size_t)i].p3 = vec3(p[6], p[7], p[8]);
+  }
+  std::vector<BVHNode> nodes((size_t)n_nodes);
+  for (int i = 0; i < n_nodes; i++) {
+    const float* p = nodes_in + (size_t)i * 12;
+    BVHNode& b = nodes[(size_t)i];
+    b.left = (int)p[0]; // (the device layout's decoding: ivec3 truncation)
+    b.right = (int)p[1];
+    b.n = (int)p[3];
+    b.index = (int)p[4];
+    b.AA = vec3(p[6], p[7], p[8]);
+    b.BB = vec3(p[9], p[10], p[11]);
+  }
+  refitBVH(tris, nodes);
+  if (nodes_out != nodes_in) memmove(nodes_out, nodes_in, (size_t)n_nodes * 12 * sizeof(float));
+  for (int i = 1; i < n_nodes; i++) {
+    float* p = nodes_out + (size_t)i * 12;
+    const BVHNode& b = nodes[(size_t)i];
+    p[6] = b.AA.x, p[7] = b.AA.y, p[8] = b.AA.z;
+    p[9] = b.BB.x, p[10] = b.BB.y, p[11] = b.BB.z;
+  }
+  return 0;
+  EZ_CATCH
+}
+
 const char* ezrt_host_last_error(void) { return g_err.c_str(); }
 
 } // extern "C"

@@ -569,6 +569,35 @@ Triangle_encoded encodeTriangle(const Triangle& t) {
   e.param4 = vec3(m.clearcoatGloss, m.IOR, m.transmission);
   return e;
 }
+void refitBVH(const std::vector<Triangle>& triangles, std::vector<BVHNode>& nodes) {
+  const int n_nodes = (int)nodes.size();
+  const int64_t n_tri = (int64_t)triangles.size();
+  for (int i = n_nodes - 1; i >= 1; i--) { // children carry larger ids than their parents: one backward sweep
+    BVHNode& nd = nodes[(size_t)i];
+    if (nd.n > 0) {
+      if (nd.index < 0 || (int64_t)nd.index + nd.n > n_tri)
+        throw std::invalid_argument("refitBVH: leaf " + std::to_string(i) + " has a triangle range outside the triangle array");
+      nd.AA = vec3((float)1145141919, (float)1145141919, (float)1145141919);
+      nd.BB = vec3((float)-1145141919, (float)-1145141919, (float)-1145141919);
+      for (int k = nd.index; k < nd.index + nd.n; k++) {
+        const Triangle& t = triangles[(size_t)k];
+        nd.AA.x = gmin(nd.AA.x, gmin(t.p1.x, gmin(t.p2.x, t.p3.x)));
+        nd.AA.y = gmin(nd.AA.y, gmin(t.p1.y, gmin(t.p2.y, t.p3.y)));
+        nd.AA.z = gmin(nd.AA.z, gmin(t.p1.z, gmin(t.p2.z, t.p3.z)));
+        nd.BB.x = gmax(nd.BB.x, gmax(t.p1.x, gmax(t.p2.x, t.p3.x)));
+        nd.BB.y = gmax(nd.BB.y, gmax(t.p1.y, gmax(t.p2.y, t.p3.y)));
+        nd.BB.z = gmax(nd.BB.z, gmax(t.p1.z, gmax(t.p2.z, t.p3.z)));
+      }
+    } else {
+      if (nd.left <= i || nd.right <= i || nd.left >= n_nodes || nd.right >= n_nodes)
+        throw std::invalid_argument("refitBVH: inner node " + std::to_string(i) + ": children must satisfy parent < child < nNodes");
+      const BVHNode& l = nodes[(size_t)nd.left];
+      const BVHNode& r = nodes[(size_t)nd.right];
+      nd.AA = vec3(gmin(l.AA.x, r.AA.x), gmin(l.AA.y, r.AA.y), gmin(l.AA.z, r.AA.z));
+      nd.BB = vec3(gmax(l.BB.x, r.BB.x), gmax(l.BB.y, r.BB.y), gmax(l.BB.z, r.BB.z));
+    }
+  }
+}
 BVHNode_encoded encodeBVH(const BVHNode& n) {
   BVHNode_encoded e;
   e.childs = vec3((float)n.left, (float)n.right, 0.0f);

@@ -5,6 +5,7 @@ handlers of the reference do for a user (P3/main.cpp:596-672), minus the window.
   mouse(x, y)          frameCounter = 0; rotatAngle / upAngle from the drag, upAngle clamped to
                        [-89, 89] (P3/main.cpp:650-660)                               -> drag(dx, dy)
   mouseWheel(dir)      frameCounter = 0; r += -direction * 0.5 (P3/main.cpp:670-674) -> wheel(direction)
+  (moved geometry)     frameCounter = 0 after a refit of the scene (ezrt_refit.h)     -> set_geometry(tri)
 
 A camera change only resets the counter: frame 0 ignores the previous frame-buffer content (the
 reference multiplies it by 0), so the buffer is not cleared.  A checkpoint is {frame buffer, frame
@@ -55,6 +56,13 @@ class ProgressiveRenderer:
     def wheel(self, direction):
         self.frameCounter = 0
         self.r += -direction * 0.5
+
+    def set_geometry(self, tri):
+        """New vertex positions and normals (the scene's triangle array, same count and order; materials are kept): refit the
+        scene, then restart the running mean at frame 0 like a camera change."""
+        from . import refit as R
+        R.refit(self.scene, tri)
+        self.frameCounter = 0
 
     # ---- checkpoint / resume
     def settings(self):

@@ -180,3 +180,15 @@ def p2Query(tri9, rays, sah=True, leaf_n=8, use_bvh=True):
     _check(lib.ezrt_host_p2_query(_fp(tri9), tri9.shape[0], int(bool(sah)), int(leaf_n), _fp(rays), rays.shape[0],
                                   int(bool(use_bvh)), _fp(out), idx.ctypes.data_as(C.POINTER(C.c_int)), _fp(t)), lib)
     return out, idx, t
+
+
+def refitBVH(tri36, nodes):
+    """refitBVH (ezrt_scene.hpp) on the encoded arrays: a copy of `nodes` [n, 12] with the box of every node but the sentinel
+    recomputed from the triangles' positions (`tri36` [m, 36]; only p1 p2 p3 are read).  Topology and triangle ranges are kept:
+    a leaf's box is the builder's own fold over its range, an inner node's the union of its children's."""
+    lib = _abi.load_host()
+    tri = np.ascontiguousarray(tri36, np.float32).reshape(-1, 36)
+    src = np.ascontiguousarray(nodes, np.float32).reshape(-1, 12)
+    out = np.empty_like(src)
+    _check(lib.ezrt_host_refit_nodes(_fp(tri), tri.shape[0], _fp(src), src.shape[0], _fp(out)), lib)
+    return out

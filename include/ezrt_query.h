@@ -29,7 +29,8 @@
  *     scene.  Growing it may synchronise the device.
  *   - Queries on one scene must be ordered among themselves: issue them on one stream, or synchronise between them.
  *   - Queries may run concurrently with ezrt_render_device calls of the same scene on another stream: a scene's records are read
- *     only after ezrt_scene_create.
+ *     only after ezrt_scene_create.  A refit (ezrt_refit.h) is the one call that rewrites them: it waits for the queries already
+ *     issued on the scene, and queries issued after it returns see the new geometry.
  *   - A query changes no scene state a caller can observe: ezrt_counters and ezrt_last_render_ms report the render calls only.
  *
  * Returns 0 or a negative EZRT_ERR_* code (ezrt.h; message in ezrt_last_error()):

@@ -116,6 +116,14 @@ BVHNode testNode();
 int buildBVH(std::vector<Triangle>& triangles, std::vector<BVHNode>& nodes, int l, int r, int n);
 int buildBVHwithSAH(std::vector<Triangle>& triangles, std::vector<BVHNode>& nodes, int l, int r, int n);
 
+// Refit: recompute every box of `nodes` (ids 1 .. size-1; node 0, the sentinel, is kept) for new triangle positions, topology
+// and triangle ranges unchanged.  A leaf's box is buildBVH's own fold over its range [index, index + n) in index order: from
+// AA = 1145141919, BB = -1145141919 (P5/main.cpp:405-423), glm::min / glm::max (the first operand wins ties and NaN) against each
+// triangle's min(p1, min(p2, p3)) / max(p1, max(p2, p3)).  An inner node's box is the union of its children's, left then right,
+// with the same operators -- for the builders' arrays exactly the fold over the node's range, signed zeros included.  Only
+// p1 p2 p3 are read.  Throws std::invalid_argument if a child id is not in (i, size) or a leaf's range leaves the triangle array.
+void refitBVH(const std::vector<Triangle>& triangles, std::vector<BVHNode>& nodes);
+
 // Order of triangles whose sort keys (centroid coordinates) are exactly equal.  The reference calls
 // std::sort, which leaves it to the C++ library (parity unpinned):
 //   Stable     (default) equal keys keep their current order -- platform independent, and what the GPU

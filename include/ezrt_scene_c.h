@@ -49,6 +49,11 @@ int ezrt_host_counts(EzrtHostScene* h, int* n_tri, int* n_nodes);
 /* encode loops (P3/main.cpp:720-748): tri_out[nTri*36], nodes_out[nNodes*12] */
 int ezrt_host_encode(EzrtHostScene* h, float* tri_out, float* nodes_out);
 
+/* refitBVH (ezrt_scene.hpp): nodes_out = nodes_in (n_nodes x 12 floats, the encoded layout) with the boxes of nodes 1 .. n_nodes-1
+ * recomputed from the triangles' p1 p2 p3 (tri36: n_tri x 36 floats; floats 9-35 are not read).  Topology, triangle ranges and
+ * node 0 are copied unchanged.  nodes_out may equal nodes_in. */
+int ezrt_host_refit_nodes(const float* tri36, int n_tri, const float* nodes_in, int n_nodes, float* nodes_out);
+
 /* HDRLoader::load (P5/lib/hdrloader.cpp:50-118).  *data is malloc-ed w*h*3
  * floats, released with ezrt_host_free. */
 int ezrt_host_hdr_load(const char* path, int* w, int* h, float** data);
