@@ -119,6 +119,13 @@ QUERY_ABI = {
 }
 
 
+# stream-ordered surface queries on device memory, libezrt_hip.so only (include/ezrt_surface.h); pointers are device addresses
+SURFACE_ABI = {
+    "ezrt_query_surface_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -177,7 +184,7 @@ def load_hip():
             raise RuntimeError(
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
-        _hip = _declare(_declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI), REFIT_ABI)
+        _hip = _declare(_declare(_declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI), SURFACE_ABI), REFIT_ABI)
     return _hip
 
 

@@ -412,19 +412,27 @@ __host__ __device__ inline ShadeDen shade_denominators(f3 p1, f3 p2, f3 p3) {
   return d;
 }
 
-template <bool P5TRI>
-EZD void shade_point(const DevScene& sc, int32_t tri, float t, f3 S, f3 d, Hit& h) {
-  const float4* g = sc.tri_geom + (size_t)tri * 3;
+// The surface attributes of a winning hit: hitTriangle's isInside, hitPoint and smooth normal (P5/fsh:172-178, 199-214) for
+// triangle `tri` at distance t along the ray (S, d) as given.  Reads the two per-triangle records (tri_geom, tri_shade: seven 16-byte
+// loads), not the material table.  shade_point (every shaded hit of a render) and query_surface_kernel (ezrt_surface.h) both run it,
+// so a query's attributes are the render's on the bits.  P5TRI: the P5/fsh:206-207 form of the smooth-normal interpolation (+1e-7
+// denominators), else P3/fsh:273-274 = P4/fsh:196-197 (the +-0.00005 form).  N_out = the smooth normal, normalised, negated when
+// inside (N = the geometric normal, tri_geom's .w).  on_record(r2) is called once the shade record is loaded (r2.y = bits of the
+// material index): shade_point issues its material loads there, ahead of the arithmetic, in the order they always had -- the
+// render's kernels compile to the same instructions as before this helper existed.
+template <bool P5TRI, class OnRecord>
+EZD void surface_point(const float4* tri_geom, const float4* tri_shade, int32_t tri, float t, f3 S, f3 d, f3& P_out, f3& N_out,
+                       bool& inside_out, OnRecord&& on_record) {
+  const float4* g = tri_geom + (size_t)tri * 3;
   float4 a = g[0], b = g[1], c = g[2];
   f3 p1 = mk(a.x, a.y, a.z), p2 = mk(b.x, b.y, b.z), p3 = mk(c.x, c.y, c.z);
   f3 N = mk(a.w, b.w, c.w);
   bool inside = dot(N, d) > 0.0f;
   f3 P = S + d * t;
-  const float4* rq = sc.tri_shade + (size_t)tri * SHADE_REC_FLOAT4;
+  const float4* rq = tri_shade + (size_t)tri * SHADE_REC_FLOAT4;
   const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2], r3 = rq[3];
   f3 n1 = mk(r0.x, r0.y, r0.z), n2 = mk(r0.w, r1.x, r1.y), n3 = mk(r1.z, r1.w, r2.x);
-  const float4* mq = sc.mat_table + (size_t)__float_as_uint(r2.y) * MAT_REC_FLOAT4;
-  const float4 m0 = mq[0], m1 = mq[1], m2 = mq[2], m3 = mq[3], m4 = mq[4], m5 = mq[5], m6 = mq[6];
+  on_record(r2);
   float alpha, beta;
   if (P5TRI) { // P5/fsh:206-207
     alpha = (-(P.x - p2.x) * (p3.y - p2.y) + (P.y - p2.y) * (p3.x - p2.x)) / r3.x;
@@ -435,8 +443,19 @@ EZD void shade_point(const DevScene& sc, int32_t tri, float t, f3 S, f3 d, Hit& 
   }
   float gama = 1.0f - alpha - beta;
   f3 Ns = normalize(n1 * alpha + n2 * beta + n3 * gama);
-  h.P = P;
-  h.N = inside ? -Ns : Ns;
+  P_out = P;
+  N_out = inside ? -Ns : Ns;
+  inside_out = inside;
+}
+
+template <bool P5TRI>
+EZD void shade_point(const DevScene& sc, int32_t tri, float t, f3 S, f3 d, Hit& h) {
+  float4 m0, m1, m2, m3, m4, m5, m6;
+  bool inside;
+  surface_point<P5TRI>(sc.tri_geom, sc.tri_shade, tri, t, S, d, h.P, h.N, inside, [&](float4 r2) {
+    const float4* mq = sc.mat_table + (size_t)__float_as_uint(r2.y) * MAT_REC_FLOAT4;
+    m0 = mq[0], m1 = mq[1], m2 = mq[2], m3 = mq[3], m4 = mq[4], m5 = mq[5], m6 = mq[6];
+  });
   h.viewDir = d;
   h.m.emissive = mk(m0.x, m0.y, m0.z);
   h.m.baseColor = mk(m0.w, m1.x, m1.y);

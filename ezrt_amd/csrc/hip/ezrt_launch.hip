@@ -3,6 +3,7 @@
 // ezrt_query_hits, ezrt_debug_math) and the small utility kernels (tone map, Sobol, non-finite count).  DESIGN.md 5.
 #include "ezrt_internal.h"
 #include "ezrt_query.h"
+#include "ezrt_surface.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1147,11 +1148,19 @@ bool ezi::device_buffer_of(const void* p, size_t bytes, int dev) {
   return (const char*)p >= (const char*)base && bytes <= size - (size_t)((const char*)p - (const char*)base);
 }
 extern "C" {
+// The optional outputs of ezrt_query_surface_device (ezrt_surface.h), and which form of the smooth normal they take.
+struct SurfaceOut {
+  float* point;
+  float* normal;
+  uint8_t* inside;
+  bool p5tri;
+};
 // occluded == NULL: closest hits into tri_id / t_hit.  The caller rays as one stage of a render call (the audit_via_queue route of
 // ezrt_query_hits) without its synchronisation and copies: query_dev_pack_kernel -> traceq4_kernel (or traceq4_occ_kernel, or the
-// binary traceq_kernel) -> the device-driven redo launch -> query_answer_kernel, all on `st`.
+// binary traceq_kernel) -> the device-driven redo launch -> query_answer_kernel, all on `st`.  surf != NULL (closest hits only):
+// query_surface_kernel takes query_answer_kernel's place and also writes the winners' surface attributes.
 static int query_device_body(EzrtScene* s, const float* rays, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,
-                             uint8_t* occluded, hipStream_t st) {
+                             uint8_t* occluded, hipStream_t st, const SurfaceOut* surf = nullptr) {
   const size_t n = (size_t)(n_rays > 0 ? n_rays : 0);
   // the scene's device: where its records live
   hipPointerAttribute_t sat;
@@ -1163,7 +1172,10 @@ static int query_device_body(EzrtScene* s, const float* rays, const float* t_max
   using ezi::device_buffer_of;
   if (!device_buffer_of(rays, n * 6 * sizeof(float), dev) || (t_max && !device_buffer_of(t_max, n * sizeof(float), dev)) ||
       (occluded && !device_buffer_of(occluded, n, dev)) || (tri_id && !device_buffer_of(tri_id, n * sizeof(int32_t), dev)) ||
-      (t_hit && !device_buffer_of(t_hit, n * sizeof(float), dev)))
+      (t_hit && !device_buffer_of(t_hit, n * sizeof(float), dev)) ||
+      (surf && surf->point && !device_buffer_of(surf->point, n * 3 * sizeof(float), dev)) ||
+      (surf && surf->normal && !device_buffer_of(surf->normal, n * 3 * sizeof(float), dev)) ||
+      (surf && surf->inside && !device_buffer_of(surf->inside, n, dev)))
     return fail(EZRT_ERR_INVALID, "rays, t_max and outputs must be device memory of the scene's device (%d), %zu rays long", dev, n);
   int prev = 0;
   HIP_TRY(hipGetDevice(&prev));
@@ -1246,9 +1258,20 @@ static int query_device_body(EzrtScene* s, const float* rays, const float* t_max
     launch_traceq_cfg(s, cfg, r, true, st);
   }
   s->n_trace_launches = launches;
-  hipLaunchKernelGGL(query_answer_kernel, dim3(g1), dim3(256), 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
+  if (surf) {
+    const DevScene sc = s->dev();
+    if (surf->p5tri)
+      hipLaunchKernelGGL(query_surface_kernel<true>, dim3(g1), dim3(256), 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
+                         (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
+    else
+      hipLaunchKernelGGL(query_surface_kernel<false>, dim3(g1), dim3(256), 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
+                         (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
+  } else {
+    hipLaunchKernelGGL(query_answer_kernel, dim3(g1), dim3(256), 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
+  }
   HIP_TRY(hipGetLastError());
-  // the end of this query on its stream: a refit of the scene (ezrt_refit.h) makes its own stream wait for it
+  // the end of this query on its stream (after its last read of the scene's records, the surface kernel's included): a refit of
+  // the scene (ezrt_refit.h) makes its own stream wait for it
   if (!q.ev_end) HIP_TRY(hipEventCreateWithFlags(&q.ev_end, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(q.ev_end, st));
   return 0;
@@ -1266,6 +1289,25 @@ int ezrt_query_occluded_device(EzrtScene* s, const float* rays_od6, const float*
     if (!s || !rays_od6 || !occluded || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
     if (n_rays == 0) return 0;
     return query_device_body(s, rays_od6, t_max, n_rays, nullptr, nullptr, occluded, (hipStream_t)stream);
+  });
+}
+int ezrt_query_surface_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int integrator, int32_t* tri_id,
+                              float* t_hit, float* hit_point, float* normal, uint8_t* inside, void* stream) {
+  return ezi::guarded("ezrt_query_surface_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || !t_hit || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
+    // the render's choice of the smooth-normal form: P5TRI = INTEG >= 50 (ezrt_kernels.h)
+    bool p5;
+    switch (integrator) {
+    case EZRT_INTEGRATOR_P3_DIFFUSE:
+    case EZRT_INTEGRATOR_P4_DISNEY: p5 = false; break;
+    case EZRT_INTEGRATOR_P5_SOBOL:
+    case EZRT_INTEGRATOR_P5_MIS:
+    case EZRT_INTEGRATOR_P5_MIS_ANISO: p5 = true; break;
+    default: return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    }
+    if (n_rays == 0) return 0;
+    const SurfaceOut surf{hit_point, normal, inside, p5};
+    return query_device_body(s, rays_od6, t_max, n_rays, tri_id, t_hit, nullptr, (hipStream_t)stream, &surf);
   });
 }
 

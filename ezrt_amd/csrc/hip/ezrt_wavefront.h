@@ -806,5 +806,39 @@ __global__ void query_answer_kernel(const int2* hits, const float* tmax, uint32_
     t[i] = hit ? __int_as_float(h.y) : INF;
   }
 }
+// ezrt_query_surface_device: query_answer_kernel's {tri, t} plus the winner's surface attributes (surface_point, the arithmetic of
+// every shaded hit) for the caller's ray as given, re-read from `rays`.  Hit lanes alone read the two per-triangle records; a miss
+// writes zeros.  point / normal / inside may each be NULL (not written).
+template <bool P5TRI>
+__global__ void query_surface_kernel(const float4* tri_geom, const float4* tri_shade, const float* rays, const int2* hits,
+                                     const float* tmax, uint32_t n, int32_t* tri, float* t, float* point, float* normal,
+                                     uint8_t* inside) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bool hit = false;
+  int2 h = make_int2(-1, 0);
+  if (query_live(tmax, i)) {
+    h = hits[i];
+    hit = h.x >= 0 && (!tmax || __int_as_float(h.y) < tmax[i]);
+  }
+  tri[i] = hit ? h.x : -1;
+  t[i] = hit ? __int_as_float(h.y) : INF;
+  f3 P = mk(0.0f, 0.0f, 0.0f), N = mk(0.0f, 0.0f, 0.0f);
+  bool in = false;
+  if (hit) {
+    const float* r = rays + (size_t)i * 6;
+    surface_point<P5TRI>(tri_geom, tri_shade, h.x, __int_as_float(h.y), mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), P, N, in,
+                         [](float4) {});
+  }
+  if (point) {
+    float* p = point + (size_t)i * 3;
+    p[0] = P.x, p[1] = P.y, p[2] = P.z;
+  }
+  if (normal) {
+    float* q = normal + (size_t)i * 3;
+    q[0] = N.x, q[1] = N.y, q[2] = N.z;
+  }
+  if (inside) inside[i] = in ? 1u : 0u;
+}
 
 } // namespace ezd

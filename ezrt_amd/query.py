@@ -1,8 +1,9 @@
-"""Stream-ordered ray queries on device tensors (include/ezrt_query.h).
+"""Stream-ordered ray queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
     hit = query.occluded(scene, rays, t_max)          # is anything in the way before t_max?  (bool)
+    tri, t, point, normal, inside = query.surface(scene, rays)   # closest hit + hit point, shading normal, side (include/ezrt_surface.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
@@ -10,11 +11,15 @@
 return without waiting for it.  There is no t_min: a triangle is accepted at t >= 0.0005 only, so a ray leaving a surface needs its
 origin offset by the caller.  A miss is (-1, 114514.0): ezrt_query_hits' miss (the reference's INF).
 """
+import collections
 import ctypes as C
 
 import torch
 
 from . import _abi, trace
+
+
+Surface = collections.namedtuple("Surface", "tri t point normal inside")
 
 
 def _check(scene, rays, t_max):
@@ -103,3 +108,33 @@ def occluded(scene, rays, t_max=None, stream=None):
                                                 C.c_void_p(out.data_ptr()), C.c_void_p(h)))
     _keep((rays, t_max, out), ts, rays)
     return out.view(torch.bool)
+
+
+_SURFACE_INTEGRATORS = (_abi.INTEGRATOR_P3_DIFFUSE, _abi.INTEGRATOR_P4_DISNEY, _abi.INTEGRATOR_P5_SOBOL, _abi.INTEGRATOR_P5_MIS,
+                        _abi.INTEGRATOR_P5_MIS_ANISO)
+
+
+def surface(scene, rays, t_max=None, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=None):
+    """Surface(tri, t, point, normal, inside): `closest` plus the reference's hitTriangle fields of each hit -- point = o + d * t
+    (float32 [..., 3]), normal = the smooth shading normal, facing the ray's side (float32 [..., 3]), inside = the ray meets the
+    triangle's back (bool).  `integrator` picks the form of the smooth normal as a render call does: 3 and 4 the chapter-3/4 form, 50,
+    51 and 52 chapter 5's.  A miss gives zeros in point, normal and inside.  The winner's material is tri36[tri, 18:36]."""
+    lib, n = _check(scene, rays, t_max)
+    _abi._declare(lib, _abi.SURFACE_ABI)
+    if integrator not in _SURFACE_INTEGRATORS:
+        raise ValueError("integrator must be one of %s, not %r" % (_SURFACE_INTEGRATORS, integrator))
+    lead = tuple(rays.shape[:-1])
+    tri = torch.empty(lead, dtype=torch.int32, device=rays.device)
+    t = torch.empty(lead, dtype=torch.float32, device=rays.device)
+    point = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
+    normal = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
+    inside = torch.empty(lead, dtype=torch.uint8, device=rays.device)
+    if n == 0:
+        return Surface(tri, t, point, normal, inside.view(torch.bool))
+    h, ts = _stream(rays, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_surface_device(scene._h, P(rays.data_ptr()), P(t_max.data_ptr()) if t_max is not None else None,
+                                               n, int(integrator), P(tri.data_ptr()), P(t.data_ptr()), P(point.data_ptr()),
+                                               P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
+    _keep((rays, t_max, tri, t, point, normal, inside), ts, rays)
+    return Surface(tri, t, point, normal, inside.view(torch.bool))
