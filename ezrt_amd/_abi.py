@@ -69,6 +69,7 @@ TRACE_ABI = {
     "ezrt_scene_stats": (C.c_int, [C.c_void_p, c_int64_p]),
     "ezrt_scene_prune_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "ezrt_debug_math": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_int, c_float_p]),
+    "ezrt_debug_fn": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, c_float_p]),
     "ezrt_last_error": (C.c_char_p, []),
     "ezrt_trim": (C.c_int, []),
     "ezrt_backend": (C.c_char_p, []),
@@ -154,16 +155,23 @@ MGPU_ABI = {
 TRANSPORT_RCCL, TRANSPORT_PEER, TRANSPORT_HOST = 0, 1, 2
 
 
-def _declare(lib, table):
+# Test hooks of include/ezrt.h that a library may have been built without (an oracle built from older sources): binding such a
+# library does not fail, calling the hook on it does (AttributeError).  The product library is bound strictly (load_hip).
+TEST_HOOKS = ("ezrt_debug_fn",)
+
+
+def _declare(lib, table, optional=()):
     for name, (res, args) in table.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args
     return lib
 
 
-def declare_trace_abi(lib):
-    return _declare(_declare(lib, TRACE_ABI), MGPU_ABI)
+def declare_trace_abi(lib, strict=False):
+    return _declare(_declare(lib, TRACE_ABI, () if strict else TEST_HOOKS), MGPU_ABI)
 
 
 def declare_host_abi(lib):
@@ -184,7 +192,7 @@ def load_hip():
             raise RuntimeError(
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
-        _hip = _declare(_declare(_declare(_declare(declare_trace_abi(C.CDLL(path)), BUILD_ABI), QUERY_ABI), SURFACE_ABI), REFIT_ABI)
+        _hip = _declare(_declare(_declare(_declare(declare_trace_abi(C.CDLL(path), strict=True), BUILD_ABI), QUERY_ABI), SURFACE_ABI), REFIT_ABI)
     return _hip
 
 

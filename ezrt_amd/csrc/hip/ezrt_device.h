@@ -397,11 +397,65 @@ __host__ __device__ inline void mat_derive(Mat& m) {
   m.gtr1_pilog = EZ_PI * ez_log(a2);
 }
 
+// A material's row of DevScene::mat_table: its 18 floats as the reference stores them (texels 6-11 of a triangle record,
+// `m18`) followed by what mat_derive makes of them.  ezrt_scene_create packs one row per distinct material through
+// mat_pack_row and shade_point reads it back through mat_unpack_row; the function-level audit (ezrt_debug_fn) sends its
+// operand materials down the same two functions.
+constexpr int MAT_ROW_FLOAT4 = 7;
+// the reference's 18 material floats -> Mat, constants derived (m18[16], m18[17] = IOR, transmission: read by no shader)
+__host__ __device__ inline void mat_from18(Mat& m, const float* m18) {
+  m.emissive = f3{m18[0], m18[1], m18[2]};
+  m.baseColor = f3{m18[3], m18[4], m18[5]};
+  m.subsurface = m18[6];
+  m.metallic = m18[7];
+  m.specular = m18[8];
+  m.specularTint = m18[9];
+  m.roughness = m18[10];
+  m.anisotropic = m18[11];
+  m.sheen = m18[12];
+  m.sheenTint = m18[13];
+  m.clearcoat = m18[14];
+  m.clearcoatGloss = m18[15];
+  mat_derive(m);
+}
+inline void mat_pack_row(const float* m18, float4* row) {
+  Mat m;
+  mat_from18(m, m18);
+  row[0] = make_float4(m18[0], m18[1], m18[2], m18[3]);
+  row[1] = make_float4(m18[4], m18[5], m18[6], m18[7]);
+  row[2] = make_float4(m18[8], m18[9], m18[10], m18[11]);
+  row[3] = make_float4(m18[12], m18[13], m18[14], m18[15]);
+  row[4] = make_float4(m18[16], m18[17], m.Cspec0.x, m.Cspec0.y);
+  row[5] = make_float4(m.Cspec0.z, m.Csheen.x, m.Csheen.y, m.Csheen.z);
+  row[6] = make_float4(m.alpha_gtr2, m.alpha_gtr1, m.gtr1_a2m1, m.gtr1_pilog);
+}
+EZD void mat_unpack_row(Mat& m, float4 m0, float4 m1, float4 m2, float4 m3, float4 m4, float4 m5, float4 m6) {
+  m.emissive = mk(m0.x, m0.y, m0.z);
+  m.baseColor = mk(m0.w, m1.x, m1.y);
+  m.subsurface = m1.z;
+  m.metallic = m1.w;
+  m.specular = m2.x;
+  m.specularTint = m2.y;
+  m.roughness = m2.z;
+  m.anisotropic = m2.w;
+  m.sheen = m3.x;
+  m.sheenTint = m3.y;
+  m.clearcoat = m3.z;
+  m.clearcoatGloss = m3.w;
+  // (m4.x, m4.y = IOR, transmission: carried by the reference, read by no shader)
+  m.Cspec0 = mk(m4.z, m4.w, m5.x);
+  m.Csheen = mk(m5.y, m5.z, m5.w);
+  m.alpha_gtr2 = m6.x;
+  m.alpha_gtr1 = m6.y;
+  m.gtr1_a2m1 = m6.z;
+  m.gtr1_pilog = m6.w;
+}
+
 // What a winning hit reads besides the 48-byte tri_geom record: 64 B per triangle, four aligned 16-byte loads
 // (the reference record's texels 3-11 were seven, P5/fsh:110-135, 199-214):
 //   (n1.xyz, n2.x) (n2.yz, n3.xy) (n3.z, bits(material index), -, -) (alpha and beta denominators of the smooth-normal
 //   interpolation, P5/fsh:206-207 form and P3/fsh:273-274 form: functions of the triangle alone)
-constexpr int SHADE_REC_FLOAT4 = 4, MAT_REC_FLOAT4 = 7;
+constexpr int SHADE_REC_FLOAT4 = 4, MAT_REC_FLOAT4 = MAT_ROW_FLOAT4;
 struct ShadeDen { float a5, b5, a34, b34; };
 __host__ __device__ inline ShadeDen shade_denominators(f3 p1, f3 p2, f3 p3) {
   ShadeDen d;
@@ -457,25 +511,7 @@ EZD void shade_point(const DevScene& sc, int32_t tri, float t, f3 S, f3 d, Hit& 
     m0 = mq[0], m1 = mq[1], m2 = mq[2], m3 = mq[3], m4 = mq[4], m5 = mq[5], m6 = mq[6];
   });
   h.viewDir = d;
-  h.m.emissive = mk(m0.x, m0.y, m0.z);
-  h.m.baseColor = mk(m0.w, m1.x, m1.y);
-  h.m.subsurface = m1.z;
-  h.m.metallic = m1.w;
-  h.m.specular = m2.x;
-  h.m.specularTint = m2.y;
-  h.m.roughness = m2.z;
-  h.m.anisotropic = m2.w;
-  h.m.sheen = m3.x;
-  h.m.sheenTint = m3.y;
-  h.m.clearcoat = m3.z;
-  h.m.clearcoatGloss = m3.w;
-  // (m4.x, m4.y = IOR, transmission: carried by the reference, read by no shader)
-  h.m.Cspec0 = mk(m4.z, m4.w, m5.x);
-  h.m.Csheen = mk(m5.y, m5.z, m5.w);
-  h.m.alpha_gtr2 = m6.x;
-  h.m.alpha_gtr1 = m6.y;
-  h.m.gtr1_a2m1 = m6.z;
-  h.m.gtr1_pilog = m6.w;
+  mat_unpack_row(h.m, m0, m1, m2, m3, m4, m5, m6);
 }
 
 // ---------------------------------------------------------------------------

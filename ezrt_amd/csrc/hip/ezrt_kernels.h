@@ -505,6 +505,102 @@ __global__ void isect_kernel(int op, const float* a, const float* b, int n, floa
   else out[i] = ray_is_tame(S, inv) ? hit_aabb_tame(S, inv, AA, BB) : __uint_as_float(0x7fc00000u);
 }
 
+// Function-level audit (ezrt_debug_fn, include/ezrt.h): the BRDF, the samplers and the environment lookups the shading kernels
+// call (the fused brdf_evaluate_pdf of the MIS loops and integrator 52's sampler included: ops 11-13), on caller-supplied operands.  op / chapter / layouts are the header's.  Materials arrive as mat_table rows packed on
+// the host by mat_pack_row (what ezrt_scene_create does) and are read with shade_point's mat_unpack_row, or -- `inline_mat` --
+// as their 18 floats, derived here by mat_derive.  The environment ops read `sc`, the scene's own DevScene.
+struct FnArgs {
+  DevScene sc;
+  int op, chapter, inline_mat, n;
+  const float* a;
+  const float4* rows; // n x MAT_ROW_FLOAT4 (table mode)
+  const float* m18;   // n x 18 (inline mode)
+  float* out;
+};
+__global__ __launch_bounds__(256) void fn_kernel(FnArgs q) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= q.n) return;
+  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
+  Mat m;
+  if ((q.op >= 1 && q.op <= 4) || (q.op >= 11 && q.op <= 13)) {
+    if (q.inline_mat) {
+      mat_from18(m, q.m18 + (size_t)i * 18);
+    } else {
+      const float4* mq = q.rows + (size_t)i * MAT_ROW_FLOAT4;
+      mat_unpack_row(m, mq[0], mq[1], mq[2], mq[3], mq[4], mq[5], mq[6]);
+    }
+  }
+  const float env_clamp = q.chapter == 3 ? 10.0f : 0.0f;
+  f3 r = mk(0, 0, 0);
+  switch (q.op) {
+    case 1: {
+      const float* p = q.a + (size_t)i * 9;
+      r = brdf_evaluate<false>(ld3(p), ld3(p + 3), ld3(p + 6), mk(0, 0, 0), mk(0, 0, 0), m);
+      break;
+    }
+    case 2: {
+      const float* p = q.a + (size_t)i * 9;
+      const f3 N = ld3(p + 3);
+      f3 X, Y;
+      get_tangent(N, X, Y);
+      r = q.chapter == 4 ? brdf_evaluate<true>(ld3(p), N, ld3(p + 6), X, Y, m) : brdf_evaluate<false>(ld3(p), N, ld3(p + 6), X, Y, m);
+      break;
+    }
+    case 3: {
+      const float* p = q.a + (size_t)i * 9;
+      r = sample_brdf(p[0], p[1], p[2], ld3(p + 3), ld3(p + 6), m);
+      break;
+    }
+    case 4: {
+      const float* p = q.a + (size_t)i * 9;
+      q.out[i] = brdf_pdf(ld3(p), ld3(p + 3), ld3(p + 6), m);
+      return;
+    }
+    case 5: q.out[i] = hdr_pdf<false>(q.sc, ld3(q.a + (size_t)i * 3), ctr); return;
+    case 6: {
+      const float* p = q.a + (size_t)i * 2;
+      r = sample_hdr<false>(q.sc, p[0], p[1], ctr);
+      break;
+    }
+    case 7: r = hdr_color<false>(q.sc, ld3(q.a + (size_t)i * 3), env_clamp, ctr); break;
+    case 9: {
+      const float* p = q.a + (size_t)i * 5;
+      r = to_normal_hemisphere(sample_hemisphere(p[0], p[1]), ld3(p + 2));
+      break;
+    }
+    case 11:   // what the MIS loops of integrators 51 / 52 call per evaluated direction (ezrt_wavefront.h, mega_kernel)
+    case 12: {
+      const float* p = q.a + (size_t)i * 9;
+      const f3 N = ld3(p + 3);
+      f3 X, Y, f;
+      float pdf;
+      get_tangent(N, X, Y);
+      if (q.op == 11) brdf_evaluate_pdf<false>(ld3(p), N, ld3(p + 6), X, Y, m, f, pdf);
+      else brdf_evaluate_pdf<true>(ld3(p), N, ld3(p + 6), X, Y, m, f, pdf);
+      float* o = q.out + (size_t)i * 4;
+      o[0] = f.x, o[1] = f.y, o[2] = f.z, o[3] = pdf;
+      return;
+    }
+    case 13: { // integrator 52's sampler
+      const float* p = q.a + (size_t)i * 9;
+      const f3 N = ld3(p + 6);
+      f3 X, Y;
+      get_tangent(N, X, Y);
+      r = sample_brdf_aniso(p[0], p[1], p[2], ld3(p + 3), N, X, Y, m);
+      break;
+    }
+    default: { // 10 (the host admits no other op)
+      float pdf;
+      hdr_color_pdf<false>(q.sc, ld3(q.a + (size_t)i * 3), env_clamp, ctr, r, pdf);
+      float* o = q.out + (size_t)i * 4;
+      o[0] = r.x, o[1] = r.y, o[2] = r.z, o[3] = pdf;
+      return;
+    }
+  }
+  float* o = q.out + (size_t)i * 3;
+  o[0] = r.x, o[1] = r.y, o[2] = r.z;
+}
+
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).
 // res[0] = mismatches, res[1] = the smallest mismatching pattern.
 __global__ void rcp_audit_kernel(unsigned long long* res) {

@@ -1400,4 +1400,67 @@ int ezrt_debug_math(int op, const float* a, const float* b, int n, float* out) {
   return ezi::guarded("ezrt_debug_math", [&]() -> int { return ezrt_debug_math_body(op, a, b, n, out); });
 }
 
+static int ezrt_debug_fn_body(EzrtScene* s, int op, int chapter, const float* a, const float* b, int n, float* out) {
+  if (!a || !out || n < 0) return fail(EZRT_ERR_INVALID, "bad argument");
+  const int inline_mat = (chapter & 0x100) ? 1 : 0;
+  chapter &= 0xff;
+  if (op == 8) return fail(EZRT_ERR_UNSUPPORTED, "op 8 (hitBVH): see the surface queries (ezrt_surface.h)");
+  if (op < 1 || op > 13) return fail(EZRT_ERR_INVALID, "unknown op %d", op);
+  const bool mat_op = op <= 4 || op >= 11, env_op = op == 5 || op == 6 || op == 7 || op == 10;
+  if (mat_op && !b) return fail(EZRT_ERR_INVALID, "ops 1-4 and 11-13 need n x 18 material floats in b");
+  if (env_op && !s) return fail(EZRT_ERR_INVALID, "this op needs a scene");
+  if (env_op && !s->hdr.p) return fail(EZRT_ERR_INVALID, "this op needs the scene's environment (ezrt_scene_set_env)");
+  if (env_op && op != 7 && !s->has_cache) return fail(EZRT_ERR_INVALID, "this op needs the env cache (ezrt_scene_set_env)");
+  if (n == 0) return 0;
+  static const int WA[14] = {0, 9, 9, 9, 9, 3, 2, 3, 0, 5, 3, 9, 9, 9}, WO[14] = {0, 3, 3, 3, 1, 1, 3, 3, 0, 3, 4, 4, 4, 3};
+  const size_t wa = (size_t)WA[op], wo = (size_t)WO[op];
+  // the scene's device (where its environment lives), as the stream-ordered queries select it
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  struct Restore {
+    int d;
+    ~Restore() { (void)hipSetDevice(d); }
+  } restore{prev};
+  if (env_op) {
+    hipPointerAttribute_t sat;
+    if (hipPointerGetAttributes(&sat, s->hdr.p) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(EZRT_ERR_INVALID, "the scene's environment is not device memory");
+    }
+    if (sat.device != prev) HIP_TRY(hipSetDevice(sat.device));
+  }
+  DevBuf<float> da, dm, dout;
+  DevBuf<float4> drows;
+  HIP_TRY(da.ensure((size_t)n * wa));
+  HIP_TRY(dout.ensure((size_t)n * wo));
+  HIP_TRY(hipMemcpy(da.p, a, (size_t)n * wa * sizeof(float), hipMemcpyHostToDevice));
+  FnArgs q;
+  memset(&q, 0, sizeof q);
+  if (s) q.sc = s->dev();
+  q.op = op;
+  q.chapter = chapter;
+  q.inline_mat = inline_mat;
+  q.n = n;
+  q.a = da.p;
+  q.out = dout.p;
+  if (mat_op && inline_mat) {
+    HIP_TRY(dm.ensure((size_t)n * 18));
+    HIP_TRY(hipMemcpy(dm.p, b, (size_t)n * 18 * sizeof(float), hipMemcpyHostToDevice));
+    q.m18 = dm.p;
+  } else if (mat_op) { // the road of a scene's materials: one table row each, packed here on the host
+    std::vector<float4> rows((size_t)n * MAT_ROW_FLOAT4);
+    for (int i = 0; i < n; i++) mat_pack_row(b + (size_t)i * 18, &rows[(size_t)i * MAT_ROW_FLOAT4]);
+    HIP_TRY(drows.ensure(rows.size()));
+    HIP_TRY(hipMemcpy(drows.p, rows.data(), rows.size() * sizeof(float4), hipMemcpyHostToDevice));
+    q.rows = drows.p;
+  }
+  hipLaunchKernelGGL(fn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, q);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * wo * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+int ezrt_debug_fn(EzrtScene* s, int op, int chapter, const float* a, const float* b, int n, float* out) {
+  return ezi::guarded("ezrt_debug_fn", [&]() -> int { return ezrt_debug_fn_body(s, op, chapter, a, b, n, out); });
+}
+
 } // extern "C"

@@ -732,27 +732,8 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
       auto it = index.find(key);
       if (it == index.end()) {
         it = index.emplace(key, (uint32_t)index.size()).first;
-        Mat m;
-        m.emissive = f3{t[18], t[19], t[20]};
-        m.baseColor = f3{t[21], t[22], t[23]};
-        m.subsurface = t[24];
-        m.metallic = t[25];
-        m.specular = t[26];
-        m.specularTint = t[27];
-        m.roughness = t[28];
-        m.anisotropic = t[29];
-        m.sheen = t[30];
-        m.sheenTint = t[31];
-        m.clearcoat = t[32];
-        m.clearcoatGloss = t[33];
-        mat_derive(m);
-        mats.push_back(make_float4(t[18], t[19], t[20], t[21]));
-        mats.push_back(make_float4(t[22], t[23], t[24], t[25]));
-        mats.push_back(make_float4(t[26], t[27], t[28], t[29]));
-        mats.push_back(make_float4(t[30], t[31], t[32], t[33]));
-        mats.push_back(make_float4(t[34], t[35], m.Cspec0.x, m.Cspec0.y));
-        mats.push_back(make_float4(m.Cspec0.z, m.Csheen.x, m.Csheen.y, m.Csheen.z));
-        mats.push_back(make_float4(m.alpha_gtr2, m.alpha_gtr1, m.gtr1_a2m1, m.gtr1_pilog));
+        mats.resize(mats.size() + MAT_REC_FLOAT4);
+        mat_pack_row(t + 18, &mats[mats.size() - MAT_REC_FLOAT4]);
       }
       last_key = key;
       last_id = it->second;

@@ -275,6 +275,27 @@ class TraceLib:
         return out
 
 
+    FN_IN_WIDTH = {1: 9, 2: 9, 3: 9, 4: 9, 5: 3, 6: 2, 7: 3, 8: 6, 9: 5, 10: 3, 11: 9, 12: 9, 13: 9}
+    FN_OUT_WIDTH = {1: 3, 2: 3, 3: 3, 4: 1, 5: 1, 6: 3, 7: 3, 8: 12, 9: 3, 10: 4, 11: 4, 12: 4, 13: 3}
+
+    def debug_fn(self, scene, op, chapter, a, b=None, inline=False):
+        """ezrt_debug_fn (test hook, include/ezrt.h): one shading function on [n, FN_IN_WIDTH[op]] operands -> [n, FN_OUT_WIDTH[op]].
+        b = [n, 18] materials (ops 1-4, 11-13); scene = the Scene whose environment ops 5, 6, 7, 10 read, else None;
+        inline: the material constants are derived in the kernel, not read from a host-built table row."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, self.FN_IN_WIDTH[op])
+        n = a.shape[0]
+        bb = None
+        if b is not None:
+            bb = np.ascontiguousarray(b, np.float32).reshape(-1, 18)
+            assert bb.shape[0] == n
+        out = np.zeros((n, self.FN_OUT_WIDTH[op]), np.float32)
+        rc = self.lib.ezrt_debug_fn(scene._h if scene is not None else None, int(op), int(chapter) | (0x100 if inline else 0),
+                                    _fp(a), _fp(bb) if bb is not None else None, n, _fp(out))
+        if rc != 0:
+            raise TraceError("%s (rc=%d)" % (self.lib.ezrt_last_error().decode(), rc))
+        return out
+
+
 def hip():
     """The product: hand-written gfx950 kernels behind the C ABI."""
     return TraceLib(_abi.load_hip())

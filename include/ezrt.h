@@ -212,6 +212,34 @@ int ezrt_scene_prune_info(EzrtScene* s, double out[8]);
  * -- out[0] = number of mismatches (a NaN equals a NaN), out bits [1] = the first mismatching pattern; the oracle divides, so 0. */
 int ezrt_debug_math(int op, const float* a, const float* b, int n, float* out);
 
+/* Test hook: the shading functions one at a time, on caller-supplied operands (host arrays in, host arrays out), so that
+ * the HIP library's BRDF, samplers and environment lookups can be compared with the oracle's function by function.  The HIP
+ * library runs the device functions its shading kernels call (ops 1, 2: integrators 4 and 50; 3, 9: the samplers; 10-13: the
+ * MIS loops of 51 and 52; op 4's brdf_pdf stands alone only here -- the kernels reach its text through op 11's fused pair).  `chapter` selects the variant (3, 4 or 5).  b = n x 18
+ * material floats in the order of a triangle record's texels 6-11 (emissive, baseColor, subsurface, metallic, specular,
+ * specularTint, roughness, anisotropic, sheen, sheenTint, clearcoat, clearcoatGloss, IOR, transmission), ops 1-4 and 11-13.
+ *   1 BRDF_Evaluate (P5/fsh:500-549)                  a = n x (V N L), b                  -> n x 3
+ *   2 the uniform loop's evaluate with X, Y = getTangent(N): chapter 4 anisotropic (P4/fsh:412-473), else chapter 5's
+ *     BRDF_Evaluate_aniso = the isotropic body (P5/fsh:437-498)    a = n x (V N L), b     -> n x 3
+ *   3 SampleBRDF (P5/fsh:633-664)                     a = n x (xi1 xi2 xi3 V N), b        -> n x 3
+ *   4 BRDF_Pdf (P5/fsh:715-752)                       a = n x (V N L), b                  -> n
+ *   5 hdrPdf (P5/fsh:701-712)                         a = n x L                           -> n
+ *   6 SampleHdr (P5/fsh:667-679)                      a = n x (xi1 xi2)                   -> n x 3
+ *   7 hdrColor (P5/fsh:693-697; chapter 3 clamps to 10, P3/fsh:151-156)   a = n x L       -> n x 3
+ *   8 hitBVH: EZRT_ERR_UNSUPPORTED in the HIP library (ezrt_surface.h is its audit); the oracle answers n x (S d) -> n x 12
+ *   9 toNormalHemisphere(SampleHemisphere(xi1, xi2), N) (P5/fsh:561-576)  a = n x (xi1 xi2 N) -> n x 3
+ *  10 hdrColor and hdrPdf of one direction, as the MIS loop asks for them (P5/fsh:829-830)  a = n x L -> n x (colour, pdf)
+ *  11 BRDF_Evaluate and BRDF_Pdf of one direction as the MIS loop of integrator 51 asks for them (P5/fsh:832-833, 858-859;
+ *     the HIP library evaluates the pair in one fused function)   a = n x (V N L), b      -> n x (f_r, pdf) = ops 1 and 4
+ *  12 the same pair of integrator 52: the anisotropic evaluate (P4/fsh:412-473) and brdf_pdf_aniso with X, Y = getTangent(N)
+ *  13 integrator 52's sample_brdf_aniso, X, Y = getTangent(N)   a = n x (xi1 xi2 xi3 V N), b -> n x 3
+ * Ops 5, 6, 7 and 10 read the environment of scene `s` (ezrt_scene_set_env: map, cache, filter; in the HIP library also the
+ * layout its options select); the other ops ignore `s`, which may be NULL.  chapter | 0x100: the HIP library derives the
+ * material's constants inside the kernel instead of reading them from a row of the material table built on the host as
+ * ezrt_scene_create builds it (every render route reads the table; the bit checks that the derivation gives the same bits
+ * compiled for the device as compiled for the host); the oracle ignores the bit. */
+int ezrt_debug_fn(EzrtScene* s, int op, int chapter, const float* a, const float* b, int n, float* out);
+
 const char* ezrt_last_error(void);
 /* Optional: release what the library keeps between scenes -- the HIP streams of destroyed scenes, which are parked for
  * the next scene on the same device instead of destroyed.  Returns the number of streams destroyed.  Call

@@ -1297,6 +1297,55 @@ int ezrt_oracle_fn(EzrtScene* s, int op, int chapter, const float* a, const floa
   return 0;
 }
 
+/* ezrt_debug_fn (include/ezrt.h): the oracle's side of the function-level audit = ezrt_oracle_fn, plus op 10 = ops 7 and 5
+ * of the same direction (the HIP library fuses the two lookups; here they are the two calls).  The 0x100 bit of `chapter`
+ * (how the HIP library obtains the material constants) means nothing here. */
+int ezrt_debug_fn(EzrtScene* s, int op, int chapter, const float* a, const float* b, int n, float* out) {
+  chapter &= 0xff;
+  if (op >= 11 && op <= 13) { /* the MIS loops' evaluate + pdf of one direction (11: P5/fsh:832-833 isotropic; 12: integrator
+                               * 52's anisotropic pair) and integrator 52's sampler (13), X, Y = getTangent(N) */
+    if (!a || !b || !out || n < 0) return fail(EZRT_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; i++) {
+      const float *p = a + (size_t)i * 9, *q = b + (size_t)i * 18;
+      Material m;
+      memset(&m, 0, sizeof m);
+      m.emissive = V3(q[0], q[1], q[2]);
+      m.baseColor = V3(q[3], q[4], q[5]);
+      m.subsurface = q[6]; m.metallic = q[7]; m.specular = q[8]; m.specularTint = q[9]; m.roughness = q[10];
+      m.anisotropic = q[11]; m.sheen = q[12]; m.sheenTint = q[13]; m.clearcoat = q[14]; m.clearcoatGloss = q[15];
+      m.IOR = q[16]; m.transmission = q[17];
+      v3 X, Y;
+      if (op == 13) {
+        v3 V = V3(p[3], p[4], p[5]), N = V3(p[6], p[7], p[8]);
+        get_tangent(N, &X, &Y);
+        v3 r = sample_brdf_aniso(p[0], p[1], p[2], V, N, X, Y, &m);
+        out[(size_t)i * 3] = r.x; out[(size_t)i * 3 + 1] = r.y; out[(size_t)i * 3 + 2] = r.z;
+      } else {
+        v3 V = V3(p[0], p[1], p[2]), N = V3(p[3], p[4], p[5]), L = V3(p[6], p[7], p[8]);
+        get_tangent(N, &X, &Y);
+        v3 f = brdf_evaluate(V, N, L, X, Y, &m, op == 12);
+        float pdf = op == 12 ? brdf_pdf_aniso(V, N, L, X, Y, &m) : brdf_pdf(V, N, L, &m);
+        out[(size_t)i * 4] = f.x; out[(size_t)i * 4 + 1] = f.y; out[(size_t)i * 4 + 2] = f.z; out[(size_t)i * 4 + 3] = pdf;
+      }
+    }
+    return 0;
+  }
+  if (op != 10) return ezrt_oracle_fn(s, op, chapter, a, b, n, out);
+  if (!a || !out || n < 0) return fail(EZRT_ERR_INVALID, "bad argument");
+  if (!s) return fail(EZRT_ERR_INVALID, "this op needs a scene");
+  for (int i = 0; i < n; i++) {
+    float c[3], pdf;
+    int rc = ezrt_oracle_fn(s, 7, chapter, a + (size_t)i * 3, NULL, 1, c);
+    if (rc == 0) rc = ezrt_oracle_fn(s, 5, chapter, a + (size_t)i * 3, NULL, 1, &pdf);
+    if (rc) return rc;
+    out[(size_t)i * 4] = c[0];
+    out[(size_t)i * 4 + 1] = c[1];
+    out[(size_t)i * 4 + 2] = c[2];
+    out[(size_t)i * 4 + 3] = pdf;
+  }
+  return 0;
+}
+
 int ezrt_debug_math(int op, const float* a, const float* b, int n, float* out) {
   if (!a || !out || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument");
   if (op == 10 || op == 12) { /* hitAABB: a = n rays (S, d), b = n boxes (AA, BB) */

@@ -24,19 +24,13 @@ from oracle import ref as R  # noqa: E402
 
 from ezrt_amd import _abi, scene as S, scenes, trace  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fn_operands as F  # noqa: E402  (the operands: shared with tests/test_gpu_fn_parity.py, device == oracle)
+from fn_operands import N_FN, _unit, _vnl, same_bits  # noqa: E402,F401
+
 pytestmark = pytest.mark.skipif(not all(R.fsh_available(c) for c in (3, 4, 5)),
                                 reason="oracle/_ref/libezrt_ref_fsh_p*.so not built (python oracle/ref_recipe/build_ref.py)")
 _F = C.POINTER(C.c_float)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same_bits(a, b):
-    """Bit equality; a NaN equals a NaN (include/ezrt.h: sign and payload of a NaN are not part of the contract)."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
 
 
 @pytest.fixture(scope="module")
@@ -61,40 +55,6 @@ def ofn(oracle):
     return call
 
 
-def _unit(rng, n):
-    v = rng.normal(size=(n, 3))
-    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
-
-
-def _materials(rng, n):
-    """Random Disney parameters, with the edge values the reference's branches test mixed in (metallic 1, roughness 0,
-    clearcoatGloss 0 / 1 -> GTR1's a >= 1 branch is unreachable but a = 0.1 / 0.001 are, black base colour -> Cdlum = 0)."""
-    m = rng.uniform(0.0, 1.0, (n, 18)).astype(np.float32)
-    m[:, 0:3] = 0.0
-    edge = rng.integers(0, 8, n)
-    m[edge == 0, 7] = 1.0          # metallic
-    m[edge == 1, 10] = 0.0         # roughness
-    m[edge == 2, 15] = 1.0         # clearcoatGloss
-    m[edge == 3, 15] = 0.0
-    m[edge == 4, 3:6] = 0.0        # baseColor black: Ctint = vec3(1)
-    m[edge == 5, 14] = 0.0         # clearcoat
-    return m
-
-
-N_FN = 100_000
-
-
-def _vnl(rng, n):
-    """V N L triples: N random, V and L mostly in N's hemisphere, a share below it (the early returns)."""
-    N = _unit(rng, n)
-    V, L = _unit(rng, n), _unit(rng, n)
-    flip_v = (np.einsum("ij,ij->i", V, N) < 0) & (rng.uniform(size=n) < 0.85)
-    flip_l = (np.einsum("ij,ij->i", L, N) < 0) & (rng.uniform(size=n) < 0.85)
-    V[flip_v] = -V[flip_v]
-    L[flip_l] = -L[flip_l]
-    return np.concatenate([V, N, L], 1).astype(np.float32)
-
-
 def test_fragment_seed_is_the_integer_pixel(fsh):
     """P5/fsh:315-318: uint((pix.x*0.5+0.5)*width) with pix = the pixel centre is the pixel index the oracle seeds with
     (SURVEY 8c "seed px,py = i,j"), for every column and row of the BASELINE frame sizes and some odd ones."""
@@ -113,8 +73,7 @@ def test_fragment_seed_is_the_integer_pixel(fsh):
 
 
 def test_brdf_evaluate_chapter5_isotropic(fsh, ofn):
-    rng = np.random.default_rng(1)
-    a, m = _vnl(rng, N_FN), _materials(rng, N_FN)
+    a, m = F.evaluate_iso_random()
     got, want = fsh[5].fn(1, a, m), ofn(None, 1, 5, a, m)
     assert same_bits(got, want) and float(np.abs(want).max()) > 0.1
 
@@ -122,8 +81,7 @@ def test_brdf_evaluate_chapter5_isotropic(fsh, ofn):
 def test_brdf_evaluate_of_the_uniform_loops(fsh, ofn):
     """Chapter 4's anisotropic BRDF_Evaluate (P4/fsh:412-473) and chapter 5's BRDF_Evaluate_aniso, whose body is the
     ISOTROPIC one (P5/fsh:465-471), each with X, Y from the shader's own getTangent."""
-    rng = np.random.default_rng(2)
-    a, m = _vnl(rng, N_FN), _materials(rng, N_FN)
+    a, m = F.evaluate_uniform_random()
     g4, w4 = fsh[4].fn(2, a, m), ofn(None, 2, 4, a, m)
     g5, w5 = fsh[5].fn(2, a, m), ofn(None, 2, 5, a, m)
     assert same_bits(g4, w4) and same_bits(g5, w5)
@@ -132,13 +90,7 @@ def test_brdf_evaluate_of_the_uniform_loops(fsh, ofn):
 
 
 def test_sample_brdf_and_pdf(fsh, ofn):
-    rng = np.random.default_rng(3)
-    m = _materials(rng, N_FN)
-    xi = rng.uniform(0, 1, (N_FN, 3)).astype(np.float32)
-    xi[:64, 2] = np.float32(1.0)       # rand() can return exactly 1.0: the clearcoat branch's upper edge
-    xi[64:128, 1] = np.float32(1.0)
-    vn = _vnl(rng, N_FN)
-    a = np.concatenate([xi, vn[:, 0:6]], 1)
+    a, m, vn = F.sample_brdf_random()
     got, want = fsh[5].fn(3, a, m), ofn(None, 3, 5, a, m)
     assert same_bits(got, want)
     # the pdf of the directions just sampled (the use the integrator makes of it) and of random ones
@@ -148,10 +100,7 @@ def test_sample_brdf_and_pdf(fsh, ofn):
 
 
 def test_hemisphere_sampling(fsh, ofn):
-    rng = np.random.default_rng(4)
-    a = np.concatenate([rng.uniform(0, 1, (N_FN, 2)).astype(np.float32), _unit(rng, N_FN)], 1)
-    a[:16, 0] = np.float32(1.0)
-    a[16:32, 2:5] = np.float32([1, 0, 0])      # |N.x| > 0.999: the other helper axis
+    a = F.hemisphere_random()
     assert same_bits(fsh[5].fn(9, a), ofn(None, 9, 5, a))
 
 
@@ -159,22 +108,65 @@ def test_hemisphere_sampling(fsh, ofn):
 def test_env_functions(fsh, ofn, oracle, bunny_small, bilinear):
     """SampleHdr, hdrPdf (sine of the ELEVATION, integer W*W/2: Q13), hdrColor on the scene's map + cache; chapter 3's
     clamp to 10 and chapter 4's unclamped sampleHdr with the NEAREST filter of those chapters."""
-    rng = np.random.default_rng(5)
     so = oracle.scene_create(bunny_small.tri, bunny_small.nodes)
     so.set_env(bunny_small.hdr, bunny_small.cache, bilinear)
     for c in (3, 4, 5):
         fsh[c].set_env(bunny_small.hdr, bunny_small.cache, bilinear)
-    L = _unit(rng, N_FN)
-    L[:8] = np.float32([[0, 1, 0], [0, -1, 0], [1, 0, 0], [-1, 0, 0], [0, 0, 1], [0, 0, -1], [-1, 0, 1e-20], [-1, 0, -1e-20]])
-    L *= rng.uniform(0.5, 2.0, (N_FN, 1)).astype(np.float32)     # hdrColor normalises
-    xi = rng.uniform(0, 1, (N_FN, 2)).astype(np.float32)
-    xi[:4] = np.float32([[0, 0], [1, 1], [0, 1], [1, 0]])
+    L, xi = F.env_random()
     assert same_bits(fsh[5].fn(6, xi), ofn(so, 6, 5, xi))
     assert same_bits(fsh[5].fn(5, L), ofn(so, 5, 5, L))
     assert same_bits(fsh[5].fn(7, L), ofn(so, 7, 5, L))
     assert same_bits(fsh[4].fn(7, L), ofn(so, 7, 4, L))
     assert same_bits(fsh[3].fn(7, L), ofn(so, 7, 3, L))
     assert float(fsh[3].fn(7, L).max()) <= 10.0 < float(fsh[4].fn(7, L).max())
+
+
+def _edge_check(name, got, want, labels, expect_nonfinite):
+    bad = F.mismatches(got, want)
+    assert bad.size == 0, "%s: shader != oracle at %d rows, first: %s shader %r oracle %r" % (
+        name, bad.size, labels[bad[0]], got[bad[0]], want[bad[0]])
+    nf = F.nonfinite_rows(want)
+    assert np.array_equal(nf, expect_nonfinite), "%s: non-finite rows are not the named ones: %s" % (
+        name, [labels[i] for i in np.flatnonzero(nf != expect_nonfinite)[:8]])
+
+
+def test_brdf_functions_on_the_edge_set(fsh, ofn):
+    """The edge operands of tests/fn_operands.py (every scalar parameter at 0, 1, -0.0, the smallest normal, a subnormal;
+    base colours black / one channel / above 1; cosines of exactly 0 and +- the smallest values; L == V, L == -V; N on the
+    axes and around getTangent's switch; xi at 0 and 1) through the executed shader and the oracle: the oracle is pinned on
+    the inputs the device is compared with it on (tests/test_gpu_fn_parity.py).  The rows that are not finite are named."""
+    a, m, lab = F.edge_evaluate()
+    _edge_check("op 1", fsh[5].fn(1, a, m), ofn(None, 1, 5, a, m), lab, F.expected_nonfinite(1, 5, lab))
+    _edge_check("op 2 ch 4", fsh[4].fn(2, a, m), ofn(None, 2, 4, a, m), lab, F.expected_nonfinite(2, 4, lab))
+    _edge_check("op 2 ch 5", fsh[5].fn(2, a, m), ofn(None, 2, 5, a, m), lab, F.expected_nonfinite(2, 5, lab))
+    _edge_check("op 4", fsh[5].fn(4, a, m), ofn(None, 4, 5, a, m), lab, F.expected_nonfinite(4, 5, lab))
+    a, m, lab = F.edge_sample_brdf()
+    want = ofn(None, 3, 5, a, m)
+    _edge_check("op 3", fsh[5].fn(3, a, m), want, lab, F.expected_nonfinite(3, 5, lab))
+    assert float(np.abs(want[np.isfinite(want)]).max()) > 0.1
+    a2 = np.concatenate([a[:, 3:9], want], 1)           # the pdf of the directions just sampled, the NaN ones included
+    w4 = ofn(None, 4, 5, a2, m)
+    _edge_check("op 4 of op 3's directions", fsh[5].fn(4, a2, m), w4, lab, F.expected_nonfinite(4, 5, lab))
+    assert float(w4.max()) > 0.1
+    a, lab = F.edge_hemisphere()
+    want = ofn(None, 9, 5, a)
+    _edge_check("op 9", fsh[5].fn(9, a), want, lab, F.expected_nonfinite(9, 5, lab))
+    assert float(np.abs(want).max()) > 0.1
+
+
+@pytest.mark.parametrize("bilinear", [1, 0])
+def test_env_functions_on_the_edge_set(fsh, ofn, oracle, bunny_small, bilinear):
+    so = oracle.scene_create(bunny_small.tri, bunny_small.nodes)
+    so.set_env(bunny_small.hdr, bunny_small.cache, bilinear)
+    for c in (3, 4, 5):
+        fsh[c].set_env(bunny_small.hdr, bunny_small.cache, bilinear)
+    L, lab = F.edge_env_dirs()
+    xi, xlab = F.edge_env_xi(bunny_small.cache)
+    assert sum("cache.x=0.5" in l for l in xlab) >= 8
+    _edge_check("op 5", fsh[5].fn(5, L), ofn(so, 5, 5, L), lab, F.expected_nonfinite(5, 5, lab))
+    _edge_check("op 6", fsh[5].fn(6, xi), ofn(so, 6, 5, xi), xlab, F.expected_nonfinite(6, 5, xlab))
+    for c in (3, 4, 5):
+        _edge_check("op 7 ch %d" % c, fsh[c].fn(7, L), ofn(so, 7, c, L), lab, F.expected_nonfinite(7, c, lab))
 
 
 def _camera_rays(eye, cam, w, h, rng):
