@@ -127,6 +127,23 @@ SURFACE_ABI = {
 }
 
 
+# stream-ordered shading queries on device memory, libezrt_hip.so only (include/ezrt_shade.h); pointers are device addresses
+SHADE_ABI = {
+    # s, tri_id, n, mat18, stream
+    "ezrt_query_material_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # s, integrator, tri_id, V, N, L, n, f_r, pdf, stream
+    "ezrt_shade_eval_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    # s, integrator, tri_id, xi, V, N, n, L, stream
+    "ezrt_shade_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
+    # s, L, n, env_clamp, colour, pdf, stream
+    "ezrt_env_eval_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, xi, n, L, stream
+    "ezrt_env_sample_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -192,7 +209,10 @@ def load_hip():
             raise RuntimeError(
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
-        _hip = _declare(_declare(_declare(_declare(declare_trace_abi(C.CDLL(path), strict=True), BUILD_ABI), QUERY_ABI), SURFACE_ABI), REFIT_ABI)
+        lib = declare_trace_abi(C.CDLL(path), strict=True)
+        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, REFIT_ABI):
+            _declare(lib, table)
+        _hip = lib
     return _hip
 
 

@@ -41,6 +41,7 @@ void ezrt_scene_destroy(EzrtScene* s) {
     if (s->ev_trace[i][1]) (void)hipEventDestroy(s->ev_trace[i][1]);
   }
   if (s->query.ev_end) (void)hipEventDestroy(s->query.ev_end);
+  if (s->query.ev_shade_end) (void)hipEventDestroy(s->query.ev_shade_end);
   delete s->refit;
   if (s->pipe[0].stream) ezh::stream_shared_release(s->pipe[0].stream_device);
   delete s;

@@ -343,6 +343,7 @@ struct QueryScratch {
   DevBuf<uint32_t> ovf;                      // traceq4 spill area of the traversal stacks
   DevBuf<unsigned long long> counters;       // a private counter slot: queries leave ezrt_counters alone
   hipEvent_t ev_end = nullptr;               // recorded behind every query's last kernel: a refit waits for it (ezrt_refit.h)
+  hipEvent_t ev_shade_end = nullptr;         // ... and behind every shading query (ezrt_shade.h: no scratch, an order of their own)
 };
 
 // What ezrt_scene_refit_device (ezrt_refit.hip) walks: the topology ezrt_scene_create keeps (host vectors, moved out of create's own

@@ -601,6 +601,136 @@ __global__ __launch_bounds__(256) void fn_kernel(FnArgs q) {
   o[0] = r.x, o[1] = r.y, o[2] = r.z;
 }
 
+// ---- shading queries (include/ezrt_shade.h): one element per lane, operands and results in the caller's device arrays.  The
+// material of an element is the table row of its triangle, reached as shade_point reaches it: the third texel of the triangle's
+// shade record holds the material index, and the row's 16-byte loads are issued right behind that load, ahead of the arithmetic.
+// Every kernel is specialised at compile time for what it evaluates (the integrator, the outputs asked for): no lane carries a
+// runtime switch, the registers of a lobe it never evaluates, or the loads of a row it never reads.
+//
+// The table row of triangle `tri`, or false for a miss / an id beyond the scene (the element's outputs are zeros then).  ROWS: how
+// many of the row's MAT_REC_FLOAT4 texels are loaded, from the first; the others are zeros.
+template <int ROWS>
+EZD bool shade_mat_row(const float4* tri_shade, const float4* mat_table, int32_t n_tri, int32_t tri, float4 (&m)[MAT_REC_FLOAT4]) {
+  if ((uint32_t)tri >= (uint32_t)n_tri) return false;
+  const float4 r2 = tri_shade[(size_t)tri * SHADE_REC_FLOAT4 + 2];
+  const float4* mq = mat_table + (size_t)__float_as_uint(r2.y) * MAT_REC_FLOAT4;
+#pragma unroll
+  for (int k = 0; k < MAT_REC_FLOAT4; k++) m[k] = k < ROWS ? mq[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  return true;
+}
+EZD void st3(float* p, f3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
+
+// ezrt_query_material_device: the 18 floats the row starts with (texels 0-4; mat_pack_row)
+__global__ __launch_bounds__(256) void shade_material_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
+                                                             const int32_t* tri_id, uint32_t n, float* mat18) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 m[MAT_REC_FLOAT4];
+  const bool ok = shade_mat_row<5>(tri_shade, mat_table, n_tri, tri_id[i], m);
+  float* o = mat18 + (size_t)i * 18;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    o[4 * k + 0] = ok ? m[k].x : 0.0f;
+    o[4 * k + 1] = ok ? m[k].y : 0.0f;
+    o[4 * k + 2] = ok ? m[k].z : 0.0f;
+    o[4 * k + 3] = ok ? m[k].w : 0.0f;
+  }
+  o[16] = ok ? m[4].x : 0.0f;
+  o[17] = ok ? m[4].y : 0.0f;
+}
+
+// ezrt_shade_eval_device: f_r and pdf of the direction L as the bounce loop of integrator INTEG computes them for its rayL
+// (ezrt_wavefront.h "start bounce b").  Integrator 3 reads baseColor alone: the row's first two texels.
+template <int INTEG, bool WANT_PDF>
+__global__ __launch_bounds__(256) void shade_eval_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
+                                                         const int32_t* tri_id, const float* Vp, const float* Np, const float* Lp,
+                                                         uint32_t n, float* f_out, float* pdf_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr bool MIS = integ_mis<INTEG>();
+  float4 q[MAT_REC_FLOAT4];
+  const bool ok = shade_mat_row<INTEG == EZRT_INTEGRATOR_P3_DIFFUSE ? 2 : MAT_REC_FLOAT4>(tri_shade, mat_table, n_tri, tri_id[i], q);
+  f3 f_r = mk(0, 0, 0);
+  float pdf = 0.0f;
+  if (ok) {
+    Mat m;
+    mat_unpack_row(m, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+    const f3 V = ld3(Vp + (size_t)i * 3), N = ld3(Np + (size_t)i * 3), L = ld3(Lp + (size_t)i * 3);
+    if (MIS) {
+      constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
+      f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
+      if (ANISO_IS) get_tangent(N, X, Y);
+      brdf_evaluate_pdf<ANISO_IS>(V, N, L, X, Y, m, f_r, pdf);
+    } else {
+      pdf = 1.0f / (2.0f * PI);
+      if (INTEG == EZRT_INTEGRATOR_P3_DIFFUSE) {
+        f_r = m.baseColor / PI;
+      } else {
+        f3 tangent, bitangent;
+        get_tangent(N, tangent, bitangent);
+        f_r = brdf_evaluate<INTEG == EZRT_INTEGRATOR_P4_DISNEY>(V, N, L, tangent, bitangent, m);
+      }
+    }
+  }
+  st3(f_out + (size_t)i * 3, f_r);
+  if (WANT_PDF) pdf_out[i] = pdf;
+}
+
+// ezrt_shade_sample_device: the direction the bounce loop of integrator INTEG continues in.  Without MIS (3, 4, 50: one
+// instantiation) it is the uniform hemisphere about N and no material is read.
+template <int INTEG>
+__global__ __launch_bounds__(256) void shade_sample_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
+                                                           const int32_t* tri_id, const float* xip, const float* Vp, const float* Np,
+                                                           uint32_t n, float* L_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr bool MIS = integ_mis<INTEG>();
+  const int32_t tri = tri_id[i];
+  f3 L = mk(0, 0, 0);
+  if (MIS) {
+    float4 q[MAT_REC_FLOAT4];
+    if (shade_mat_row<MAT_REC_FLOAT4>(tri_shade, mat_table, n_tri, tri, q)) {
+      Mat m;
+      mat_unpack_row(m, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+      constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
+      const float* xi = xip + (size_t)i * 3;
+      const f3 V = ld3(Vp + (size_t)i * 3), N = ld3(Np + (size_t)i * 3);
+      f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
+      if (ANISO_IS) get_tangent(N, X, Y);
+      L = ANISO_IS ? sample_brdf_aniso(xi[0], xi[1], xi[2], V, N, X, Y, m) : sample_brdf(xi[0], xi[1], xi[2], V, N, m);
+    }
+  } else if ((uint32_t)tri < (uint32_t)n_tri) {
+    const float* xi = xip + (size_t)i * 3;
+    L = to_normal_hemisphere(sample_hemisphere(xi[0], xi[1]), ld3(Np + (size_t)i * 3));
+  }
+  st3(L_out + (size_t)i * 3, L);
+}
+
+// ezrt_env_eval_device: hdr_color and / or hdr_pdf of L; both = the fused lookup of the MIS loops
+template <bool COLOUR, bool WANT_PDF>
+__global__ __launch_bounds__(256) void env_eval_kernel(DevScene sc, const float* Lp, uint32_t n, float env_clamp, float* colour,
+                                                       float* pdf_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
+  const f3 L = ld3(Lp + (size_t)i * 3);
+  f3 c = mk(0, 0, 0);
+  float pdf = 0.0f;
+  if (COLOUR && WANT_PDF) hdr_color_pdf<false>(sc, L, env_clamp, ctr, c, pdf);
+  else if (COLOUR) c = hdr_color<false>(sc, L, env_clamp, ctr);
+  else pdf = hdr_pdf<false>(sc, L, ctr);
+  if (COLOUR) st3(colour + (size_t)i * 3, c);
+  if (WANT_PDF) pdf_out[i] = pdf;
+}
+
+// ezrt_env_sample_device
+__global__ __launch_bounds__(256) void env_sample_kernel(DevScene sc, const float* xip, uint32_t n, float* L_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
+  st3(L_out + (size_t)i * 3, sample_hdr<false>(sc, xip[(size_t)i * 2], xip[(size_t)i * 2 + 1], ctr));
+}
+
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).
 // res[0] = mismatches, res[1] = the smallest mismatching pattern.
 __global__ void rcp_audit_kernel(unsigned long long* res) {

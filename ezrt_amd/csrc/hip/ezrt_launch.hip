@@ -4,6 +4,7 @@
 #include "ezrt_internal.h"
 #include "ezrt_query.h"
 #include "ezrt_surface.h"
+#include "ezrt_shade.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1308,6 +1309,136 @@ int ezrt_query_surface_device(EzrtScene* s, const float* rays_od6, const float* 
     if (n_rays == 0) return 0;
     const SurfaceOut surf{hit_point, normal, inside, p5};
     return query_device_body(s, rays_od6, t_max, n_rays, tri_id, t_hit, nullptr, (hipStream_t)stream, &surf);
+  });
+}
+
+// ---- shading queries on device memory (include/ezrt_shade.h): one kernel each on `st`, no scratch
+} // extern "C"
+// What every call does before and after its launch: the scene's device found and made current (restored on return), every buffer of
+// `bufs` checked to be `bytes` of that device's memory, then launch(), then the event a later refit waits for.
+struct ShadeBuf {
+  const void* p;
+  size_t bytes;
+};
+template <class Launch>
+static int shade_call(EzrtScene* s, std::initializer_list<ShadeBuf> bufs, size_t n, hipStream_t st, Launch&& launch) {
+  hipPointerAttribute_t sat;
+  if (!s->tri_shade.p || hipPointerGetAttributes(&sat, s->tri_shade.p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EZRT_ERR_INVALID, "the scene has no device records");
+  }
+  const int dev = sat.device;
+  for (const ShadeBuf& b : bufs)
+    if (b.p && !ezi::device_buffer_of(b.p, b.bytes, dev))
+      return fail(EZRT_ERR_INVALID, "inputs and outputs must be device memory of the scene's device (%d), %zu elements long", dev, n);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  struct Restore {
+    int d;
+    ~Restore() { (void)hipSetDevice(d); }
+  } restore{prev};
+  if (dev != prev) HIP_TRY(hipSetDevice(dev));
+  launch(dim3((unsigned)((n + 255) / 256)), dim3(256));
+  HIP_TRY(hipGetLastError());
+  // the end of this call on its stream, after its last read of the per-triangle records: a refit makes its own stream wait for it
+  QueryScratch& q = s->query;
+  if (!q.ev_shade_end) HIP_TRY(hipEventCreateWithFlags(&q.ev_shade_end, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(q.ev_shade_end, st));
+  return 0;
+}
+static bool shade_integrator(int integrator) {
+  return integrator == EZRT_INTEGRATOR_P3_DIFFUSE || integrator == EZRT_INTEGRATOR_P4_DISNEY || integrator == EZRT_INTEGRATOR_P5_SOBOL ||
+         integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO;
+}
+template <int INTEG>
+static void launch_shade_eval(EzrtScene* s, dim3 g, dim3 b, hipStream_t st, const int32_t* tri_id, const float* V, const float* N,
+                              const float* L, int n, float* f_r, float* pdf) {
+  if (pdf)
+    hipLaunchKernelGGL((shade_eval_kernel<INTEG, true>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
+                       (uint32_t)n, f_r, pdf);
+  else
+    hipLaunchKernelGGL((shade_eval_kernel<INTEG, false>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
+                       (uint32_t)n, f_r, pdf);
+}
+extern "C" {
+int ezrt_query_material_device(EzrtScene* s, const int32_t* tri_id, int n, float* mat18, void* stream) {
+  return ezi::guarded("ezrt_query_material_device", [&]() -> int {
+    if (!s || !tri_id || !mat18 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{tri_id, N * sizeof(int32_t)}, {mat18, N * 18 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(shade_material_kernel, g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, (uint32_t)n, mat18);
+    });
+  });
+}
+int ezrt_shade_eval_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* V, const float* N, const float* L, int n,
+                           float* f_r, float* pdf, void* stream) {
+  return ezi::guarded("ezrt_shade_eval_device", [&]() -> int {
+    if (!s || !tri_id || !V || !N || !L || !f_r || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{tri_id, K * sizeof(int32_t)}, {V, v3}, {N, v3}, {L, v3}, {f_r, v3}, {pdf, K * sizeof(float)}}, K, st,
+                      [&](dim3 g, dim3 b) {
+                        switch (integrator) { // the one dispatch: each kernel is compiled for its integrator
+                        case EZRT_INTEGRATOR_P3_DIFFUSE: launch_shade_eval<EZRT_INTEGRATOR_P3_DIFFUSE>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
+                        case EZRT_INTEGRATOR_P4_DISNEY: launch_shade_eval<EZRT_INTEGRATOR_P4_DISNEY>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
+                        case EZRT_INTEGRATOR_P5_SOBOL: launch_shade_eval<EZRT_INTEGRATOR_P5_SOBOL>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
+                        case EZRT_INTEGRATOR_P5_MIS: launch_shade_eval<EZRT_INTEGRATOR_P5_MIS>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
+                        default: launch_shade_eval<EZRT_INTEGRATOR_P5_MIS_ANISO>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
+                        }
+                      });
+  });
+}
+int ezrt_shade_sample_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* xi, const float* V, const float* N, int n,
+                             float* L, void* stream) {
+  return ezi::guarded("ezrt_shade_sample_device", [&]() -> int {
+    if (!s || !tri_id || !xi || !V || !N || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{tri_id, K * sizeof(int32_t)}, {xi, v3}, {V, v3}, {N, v3}, {L, v3}}, K, st, [&](dim3 g, dim3 b) {
+      const float4 *ts = s->tri_shade.p, *mt = s->mat_table.p;
+      const int32_t nt = (int32_t)s->n_tri;
+      if (integrator == EZRT_INTEGRATOR_P5_MIS)
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+      else if (integrator == EZRT_INTEGRATOR_P5_MIS_ANISO)
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+      else // 3, 4 and 50 continue in the same direction: the uniform hemisphere about N
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_SOBOL>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+    });
+  });
+}
+int ezrt_env_eval_device(EzrtScene* s, const float* L, int n, float env_clamp, float* colour, float* pdf, void* stream) {
+  return ezi::guarded("ezrt_env_eval_device", [&]() -> int {
+    if (!s || !L || (!colour && !pdf) || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument (one of colour and pdf is required) or n < 0");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if (pdf && !s->has_cache) return fail(EZRT_ERR_INVALID, "the pdf needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{L, v3}, {colour, v3}, {pdf, K * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      const DevScene sc = s->dev();
+      if (colour && pdf) hipLaunchKernelGGL((env_eval_kernel<true, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+      else if (colour) hipLaunchKernelGGL((env_eval_kernel<true, false>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+      else hipLaunchKernelGGL((env_eval_kernel<false, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+    });
+  });
+}
+int ezrt_env_sample_device(EzrtScene* s, const float* xi, int n, float* L, void* stream) {
+  return ezi::guarded("ezrt_env_sample_device", [&]() -> int {
+    if (!s || !xi || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if (!s->has_cache) return fail(EZRT_ERR_INVALID, "sampling needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{xi, K * 2 * sizeof(float)}, {L, K * 3 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(env_sample_kernel, g, b, 0, st, s->dev(), xi, (uint32_t)n, L);
+    });
   });
 }
 

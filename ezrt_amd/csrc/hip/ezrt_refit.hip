@@ -386,7 +386,7 @@ int refit_body(EzrtScene* s, const float* tri36, int n_tri, hipStream_t st) {
   }
 
   // after everything already issued on the scene: the last render call (its end event follows every chunk it accumulated), the two
-  // pipelined streams (chunks there do not wait for the caller's stream), the last device query
+  // pipelined streams (chunks there do not wait for the caller's stream), the last device query, the last shading query
   if (s->ev_end) HIP_TRY(hipStreamWaitEvent(st, s->ev_end, 0));
   for (int i = 0; i < ezh::SHARED_STREAMS; i++)
     if (s->pipe[i].stream) {
@@ -394,6 +394,7 @@ int refit_body(EzrtScene* s, const float* tri36, int n_tri, hipStream_t st) {
       HIP_TRY(hipStreamWaitEvent(st, R.ev_pipe[i], 0));
     }
   if (s->query.ev_end) HIP_TRY(hipStreamWaitEvent(st, s->query.ev_end, 0));
+  if (s->query.ev_shade_end) HIP_TRY(hipStreamWaitEvent(st, s->query.ev_shade_end, 0));
 
   const int n = s->n_tri;
   const bool wide = s->n_inner4 > 0;

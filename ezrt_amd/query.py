@@ -22,16 +22,22 @@ from . import _abi, trace
 Surface = collections.namedtuple("Surface", "tri t point normal inside")
 
 
-def _check(scene, rays, t_max):
+def _scene_lib(scene, abi):
+    """The library of an open scene of the HIP product, with the entry points of `abi` declared."""
     if not isinstance(scene, trace.Scene) or not scene._h:
         raise TypeError("scene must be an open trace.Scene")
     lib = scene._tl.lib
     try:
         if not scene._tl.backend().startswith("hip:"):
             raise AttributeError
-        _abi._declare(lib, _abi.QUERY_ABI)
+        _abi._declare(lib, abi)
     except AttributeError:
         raise TypeError("device queries need a scene of the HIP library (backend %r)" % scene._tl.backend()) from None
+    return lib
+
+
+def _check(scene, rays, t_max):
+    lib = _scene_lib(scene, _abi.QUERY_ABI)
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
         raise TypeError("rays must be a GPU tensor")
     if rays.dtype != torch.float32:
