@@ -144,6 +144,16 @@ SHADE_ABI = {
 }
 
 
+# stream-ordered path queries on device memory, libezrt_hip.so only (include/ezrt_path.h); pointers are device addresses
+PATH_ABI = {
+    # s, p, sample_xyf, n, rays_od6, stream
+    "ezrt_camera_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # s, integrator, max_bounce, env_clamp, rays_od6, sample_xyf, n, radiance, stream
+    "ezrt_query_radiance_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -210,7 +220,7 @@ def load_hip():
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
-        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, REFIT_ABI):
+        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

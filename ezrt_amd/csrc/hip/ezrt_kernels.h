@@ -5,6 +5,10 @@
 //       a 256-thread workgroup owns a 16x16 pixel block of one frame, each of
 //       its four wavefronts an 8x8 sub-tile, so the 64 primary rays of a wave
 //       are coherent.  Sample radiance goes to a frame-major sample buffer.
+//       Its primary-ray arithmetic (camera_dir) and its bounce loop (path_radiance)
+//       are device functions of their own: camera_rays_kernel and
+//       radiance_query_kernel<INTEG> (include/ezrt_path.h) hand the first out
+//       and run the second along caller rays, one path per lane as here.
 //   accumulate_kernel    the reference's running mean mix(last, c, 1/(k+1))
 //       (P5/fsh:943-944) applied in frame order, one thread per pixel.
 //   sobol_kernel / tonemap_kernel / query_kernel / math_kernel  small entry
@@ -95,17 +99,16 @@ EZD uint32_t queue_to_sample(uint32_t qslot, const FastDiv& n_sub_div, uint32_t 
   return ((fk * n_sub + r2) << sh) | (qslot & ((1u << sh) - 1u));
 }
 
-// The primary ray of queue position `qslot`: main() up to the hitBVH call (P5/fsh:315-318 seed, 920-925 jitter, camera,
-// normalize) -- (dir.xyz, 1), or w = 0 for a pixel this shard does not own.  ONE definition for every kernel that needs the
-// direction, so that the ray the trace follows and the ray the shading stage shades are the same bits.
-EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const FastDiv& div_blocks, const FastDiv& div_sub, uint32_t scatter,
-                       uint32_t scatter_shift, uint32_t frame_first, uint32_t qslot) {
-  int x, y;
-  uint32_t frame;
-  slot_to_pixel(blocks, div_blocks, queue_to_sample(qslot, div_sub, scatter, scatter_shift), frame_first, x, y, frame);
-  if (!pixel_owned(p, x, y)) return make_float4(0, 0, 0, 0.0f);
-  const uint32_t ix = (uint32_t)x, iy = (uint32_t)y;
-  uint32_t seed = (ix * 1973u + iy * 9277u + frame * 26699u) | 1u;
+// The seed of pixel-sample (ix, iy, frame): P5/fsh:315-318
+EZD uint32_t pixel_seed(uint32_t ix, uint32_t iy, uint32_t frame) { return (ix * 1973u + iy * 9277u + frame * 26699u) | 1u; }
+
+// The direction of the primary ray of pixel-sample (ix, iy, frame): main() up to the hitBVH call (P5/fsh:315-318 seed, 920-925
+// jitter, camera, normalize).  `seed` returns the RNG state main() has when it reaches hitBVH: the pixel-sample's seed advanced by
+// the two jitter draws.  ONE definition for every kernel that needs the direction -- the primary stage's trace and shading kernels
+// (primary_dir), trace_kernel and ezrt_camera_rays_device -- so that the ray the trace follows, the ray the shading stage shades
+// and the ray a caller is handed are the same bits.  Of `p` it reads width, height and camera_rotate alone.
+EZD f3 camera_dir(const EzrtRenderParams& p, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t& seed) {
+  seed = pixel_seed(ix, iy, frame);
   const float W = (float)p.width, H = (float)p.height;
   // (x / W for a power-of-two W IS x * (1 / W) on the bits, and every BASELINE frame is one: the four divisions below as
   // multiplications behind a uniform branch were built and measured in round 4 -- C2 -3.3 %: four more launch-invariant values
@@ -117,25 +120,147 @@ EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const Fast
   float vx = pixx + aax, vy = pixy + aay, vz = -1.5f;
   const float* m = p.camera_rotate;
   f3 dir = mk(m[0] * vx + m[4] * vy + m[8] * vz, m[1] * vx + m[5] * vy + m[9] * vz, m[2] * vx + m[6] * vy + m[10] * vz);
-  dir = normalize(dir);
+  return normalize(dir);
+}
+
+// The primary ray of queue position `qslot`: (dir.xyz, 1), or w = 0 for a pixel this shard does not own.
+EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const FastDiv& div_blocks, const FastDiv& div_sub, uint32_t scatter,
+                       uint32_t scatter_shift, uint32_t frame_first, uint32_t qslot) {
+  int x, y;
+  uint32_t frame;
+  slot_to_pixel(blocks, div_blocks, queue_to_sample(qslot, div_sub, scatter, scatter_shift), frame_first, x, y, frame);
+  if (!pixel_owned(p, x, y)) return make_float4(0, 0, 0, 0.0f);
+  uint32_t seed;
+  const f3 dir = camera_dir(p, (uint32_t)x, (uint32_t)y, frame, seed);
   return make_float4(dir.x, dir.y, dir.z, 1.0f);
 }
 
+// Where a path's ray slots are logged (ezrt_render_paths): the 1 + 2 * max_bounce ids and distances of ONE pixel
+struct PathLog {
+  int32_t* tri;
+  float* t;
+};
 template <bool PATHLOG>
-EZD void plog(const TraceArgs& a, size_t pix, int slot, int32_t tri, float t) {
+EZD void plog(const PathLog& lg, int slot, int32_t tri, float t) {
   if (PATHLOG) {
-    int slots = 1 + 2 * a.p.max_bounce;
-    a.log_tri[pix * slots + slot] = tri;
-    a.log_t[pix * slots + slot] = (tri >= 0) ? t : INF;
+    lg.tri[slot] = tri;
+    lg.t[slot] = (tri >= 0) ? t : INF;
   }
+}
+
+// pathTracing of integrator INTEG along ONE primary ray, a whole path in this lane: main() from its hitBVH call to `color`
+// (P5/fsh:926-938 and the chapters' loops).  The ray enters through (org3, dir), used as given; the pixel-sample through
+// (ix, iy, frame) -- Cranley-Patterson offsets, Gray-coded Sobol index -- and `seed`, the RNG state behind the two jitter draws
+// (camera_dir returns it).  ONE definition of the bounce loop for every one-lane kernel: trace_kernel (the megakernel route of a
+// render call and ezrt_render_paths, which logs every ray slot through `lg`) and radiance_query_kernel (caller rays).
+template <int INTEG, bool FULLCTR, bool PATHLOG>
+EZD f3 path_radiance(const DevScene& sc, f3 org3, f3 dir, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t seed, int max_bounce,
+                     float env_clamp, int* stack, Counters& ctr, const PathLog& lg) {
+  constexpr bool P5TRI = (INTEG >= 50);
+  constexpr bool MIS = integ_mis<INTEG>();
+  constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
+  int32_t tri;
+  float t;
+  hit_bvh<FULLCTR, BLOCK>(sc, org3, dir, stack, tri, t, ctr);
+  plog<PATHLOG>(lg, 0, tri, t);
+  if (tri < 0) return hdr_color<FULLCTR>(sc, dir, env_clamp, ctr);
+  Hit hit;
+  shade_point<P5TRI>(sc, tri, t, org3, dir, hit);
+  const f3 Le0 = hit.m.emissive;
+  f3 Lo = mk(0, 0, 0), history = mk(1, 1, 1);
+  float cpu = 0.0f, cpv = 0.0f;
+  if (INTEG >= 50) cp_offsets(ix, iy, cpu, cpv);
+  const uint32_t gray = gray_code(frame + 1u);
+
+  for (int bounce = 0; bounce < max_bounce; bounce++) {
+    const f3 V = -hit.viewDir, N = hit.N;
+    f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
+    if (ANISO_IS) get_tangent(N, X, Y);
+    if (MIS) {
+      // env importance sample + shadow ray: P5/fsh:819-842
+      float h1 = rnd(seed);
+      float h2 = rnd(seed);
+      f3 Lh = sample_hdr<FULLCTR>(sc, h1, h2, ctr);
+      if (dot(N, Lh) > 0.0f) {
+        int32_t st;
+        float stt;
+        hit_bvh<FULLCTR, BLOCK>(sc, hit.P, Lh, stack, st, stt, ctr);
+        plog<PATHLOG>(lg, 1 + 2 * bounce, st, stt);
+        if (st < 0) {
+          f3 color;
+          float pdf_light;
+          hdr_color_pdf<FULLCTR>(sc, Lh, env_clamp, ctr, color, pdf_light);
+          f3 f_r;
+          float pdf_brdf;
+          brdf_evaluate_pdf<ANISO_IS>(V, N, Lh, X, Y, hit.m, f_r, pdf_brdf);
+          float w = mis_mix_weight(pdf_light, pdf_brdf);
+          Lo = Lo + (((history * w) * color) * f_r) * dot(N, Lh) / pdf_light;
+        }
+      }
+    }
+    // sample direction
+    f3 L;
+    float xi1, xi2;
+    if (INTEG >= 50) { // sobolVec2 + CP: P5/fsh:771-772, 845-846 (dims wrap at 8)
+      uint32_t d0 = ((uint32_t)bounce * 2u) & sc.sobol_mask, d1 = ((uint32_t)bounce * 2u + 1u) & sc.sobol_mask;
+      xi1 = cp_rotate(sobol(d0, gray), cpu);
+      xi2 = cp_rotate(sobol(d1, gray), cpv);
+    } else { // P3/fsh:109-114: z = rand() then phi = 2 pi rand()
+      xi1 = rnd(seed);
+      xi2 = rnd(seed);
+    }
+    float cosine, pdf;
+    f3 f_r;
+    if (MIS) {
+      float xi3 = rnd(seed);
+      L = ANISO_IS ? sample_brdf_aniso(xi1, xi2, xi3, V, N, X, Y, hit.m) : sample_brdf(xi1, xi2, xi3, V, N, hit.m);
+      cosine = dot(N, L);
+      if (cosine <= 0.0f) break;
+    } else {
+      L = to_normal_hemisphere(sample_hemisphere(xi1, xi2), N);
+      pdf = 1.0f / (2.0f * PI);
+      cosine = ez_max(0.0f, dot(L, N));
+      if (INTEG == EZRT_INTEGRATOR_P3_DIFFUSE) {
+        f_r = hit.m.baseColor / PI;
+      } else {
+        f3 tangent, bitangent;
+        get_tangent(N, tangent, bitangent);
+        f_r = brdf_evaluate<INTEG == EZRT_INTEGRATOR_P4_DISNEY>(V, N, L, tangent, bitangent, hit.m);
+      }
+    }
+    int32_t nt;
+    float ntt;
+    hit_bvh<FULLCTR, BLOCK>(sc, hit.P, L, stack, nt, ntt, ctr);
+    plog<PATHLOG>(lg, 2 + 2 * bounce, nt, ntt);
+    if (MIS) {
+      brdf_evaluate_pdf<ANISO_IS>(V, N, L, X, Y, hit.m, f_r, pdf);
+      if (pdf <= 0.0f) break;
+    }
+    if (nt < 0) {
+      f3 sky;
+      float pdf_light = 0.0f;
+      if (MIS) hdr_color_pdf<FULLCTR>(sc, L, env_clamp, ctr, sky, pdf_light);
+      else sky = hdr_color<FULLCTR>(sc, L, env_clamp, ctr);
+      if (MIS) {
+        float w = mis_mix_weight(pdf, pdf_light);
+        Lo = Lo + (((history * w) * sky) * f_r) * cosine / pdf;
+      } else {
+        Lo = Lo + ((history * sky) * f_r) * cosine / pdf;
+      }
+      break;
+    }
+    Hit nh;
+    shade_point<P5TRI>(sc, nt, ntt, hit.P, L, nh);
+    Lo = Lo + ((history * nh.m.emissive) * f_r) * cosine / pdf;
+    history = history * (f_r * cosine / pdf);
+    hit = nh;
+  }
+  return Le0 + Lo;
 }
 
 template <int INTEG, bool FULLCTR, bool PATHLOG>
 __global__ __launch_bounds__(BLOCK) void trace_kernel(TraceArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  constexpr bool P5TRI = (INTEG >= 50);
-  constexpr bool MIS = integ_mis<INTEG>();
-  constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
   const int tid = threadIdx.x;
   const int blk = blockIdx.x % a.n_blocks;
   const int fk = blockIdx.x / a.n_blocks;
@@ -155,128 +280,21 @@ __global__ __launch_bounds__(BLOCK) void trace_kernel(TraceArgs a) {
   if (active) {
     samples = 1;
     const size_t pix = (size_t)y * p.width + x;
+    PathLog lg = {nullptr, nullptr};
     if (PATHLOG) {
       int slots = 1 + 2 * p.max_bounce;
+      lg.tri = a.log_tri + pix * slots;
+      lg.t = a.log_t + pix * slots;
       for (int k = 0; k < slots; k++) {
-        a.log_tri[pix * slots + k] = -2;
-        a.log_t[pix * slots + k] = INF;
+        lg.tri[k] = -2;
+        lg.t[k] = INF;
       }
     }
-    // main(): P5/fsh:315-318, 920-925
     const uint32_t ix = (uint32_t)x, iy = (uint32_t)y;
-    uint32_t seed = (ix * 1973u + iy * 9277u + frame * 26699u) | 1u;
-    const float W = (float)p.width, H = (float)p.height;
-    float pixx = ((float)ix + 0.5f) / W * 2.0f - 1.0f;
-    float pixy = ((float)iy + 0.5f) / H * 2.0f - 1.0f;
-    float aax = (rnd(seed) - 0.5f) / W;
-    float aay = (rnd(seed) - 0.5f) / H;
-    float vx = pixx + aax, vy = pixy + aay, vz = -1.5f;
-    const float* m = p.camera_rotate;
-    f3 dir = mk(m[0] * vx + m[4] * vy + m[8] * vz, m[1] * vx + m[5] * vy + m[9] * vz,
-                m[2] * vx + m[6] * vy + m[10] * vz);
-    dir = normalize(dir);
-    f3 org3 = mk(p.eye[0], p.eye[1], p.eye[2]);
-
-    int32_t tri;
-    float t;
-    hit_bvh<FULLCTR, BLOCK>(sc, org3, dir, stack, tri, t, ctr);
-    plog<PATHLOG>(a, pix, 0, tri, t);
-    if (tri < 0) {
-      colour = hdr_color<FULLCTR>(sc, dir, p.env_clamp, ctr);
-    } else {
-      Hit hit;
-      shade_point<P5TRI>(sc, tri, t, org3, dir, hit);
-      const f3 Le0 = hit.m.emissive;
-      f3 Lo = mk(0, 0, 0), history = mk(1, 1, 1);
-      float cpu = 0.0f, cpv = 0.0f;
-      if (INTEG >= 50) cp_offsets(ix, iy, cpu, cpv);
-      const uint32_t gray = gray_code(frame + 1u);
-
-      for (int bounce = 0; bounce < p.max_bounce; bounce++) {
-        const f3 V = -hit.viewDir, N = hit.N;
-        f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
-        if (ANISO_IS) get_tangent(N, X, Y);
-        if (MIS) {
-          // env importance sample + shadow ray: P5/fsh:819-842
-          float h1 = rnd(seed);
-          float h2 = rnd(seed);
-          f3 Lh = sample_hdr<FULLCTR>(sc, h1, h2, ctr);
-          if (dot(N, Lh) > 0.0f) {
-            int32_t st;
-            float stt;
-            hit_bvh<FULLCTR, BLOCK>(sc, hit.P, Lh, stack, st, stt, ctr);
-            plog<PATHLOG>(a, pix, 1 + 2 * bounce, st, stt);
-            if (st < 0) {
-              f3 color;
-              float pdf_light;
-              hdr_color_pdf<FULLCTR>(sc, Lh, p.env_clamp, ctr, color, pdf_light);
-              f3 f_r;
-              float pdf_brdf;
-              brdf_evaluate_pdf<ANISO_IS>(V, N, Lh, X, Y, hit.m, f_r, pdf_brdf);
-              float w = mis_mix_weight(pdf_light, pdf_brdf);
-              Lo = Lo + (((history * w) * color) * f_r) * dot(N, Lh) / pdf_light;
-            }
-          }
-        }
-        // sample direction
-        f3 L;
-        float xi1, xi2;
-        if (INTEG >= 50) { // sobolVec2 + CP: P5/fsh:771-772, 845-846 (dims wrap at 8)
-          uint32_t d0 = ((uint32_t)bounce * 2u) & sc.sobol_mask, d1 = ((uint32_t)bounce * 2u + 1u) & sc.sobol_mask;
-          xi1 = cp_rotate(sobol(d0, gray), cpu);
-          xi2 = cp_rotate(sobol(d1, gray), cpv);
-        } else { // P3/fsh:109-114: z = rand() then phi = 2 pi rand()
-          xi1 = rnd(seed);
-          xi2 = rnd(seed);
-        }
-        float cosine, pdf;
-        f3 f_r;
-        if (MIS) {
-          float xi3 = rnd(seed);
-          L = ANISO_IS ? sample_brdf_aniso(xi1, xi2, xi3, V, N, X, Y, hit.m) : sample_brdf(xi1, xi2, xi3, V, N, hit.m);
-          cosine = dot(N, L);
-          if (cosine <= 0.0f) break;
-        } else {
-          L = to_normal_hemisphere(sample_hemisphere(xi1, xi2), N);
-          pdf = 1.0f / (2.0f * PI);
-          cosine = ez_max(0.0f, dot(L, N));
-          if (INTEG == EZRT_INTEGRATOR_P3_DIFFUSE) {
-            f_r = hit.m.baseColor / PI;
-          } else {
-            f3 tangent, bitangent;
-            get_tangent(N, tangent, bitangent);
-            f_r = brdf_evaluate<INTEG == EZRT_INTEGRATOR_P4_DISNEY>(V, N, L, tangent, bitangent, hit.m);
-          }
-        }
-        int32_t nt;
-        float ntt;
-        hit_bvh<FULLCTR, BLOCK>(sc, hit.P, L, stack, nt, ntt, ctr);
-        plog<PATHLOG>(a, pix, 2 + 2 * bounce, nt, ntt);
-        if (MIS) {
-          brdf_evaluate_pdf<ANISO_IS>(V, N, L, X, Y, hit.m, f_r, pdf);
-          if (pdf <= 0.0f) break;
-        }
-        if (nt < 0) {
-          f3 sky;
-          float pdf_light = 0.0f;
-          if (MIS) hdr_color_pdf<FULLCTR>(sc, L, p.env_clamp, ctr, sky, pdf_light);
-          else sky = hdr_color<FULLCTR>(sc, L, p.env_clamp, ctr);
-          if (MIS) {
-            float w = mis_mix_weight(pdf, pdf_light);
-            Lo = Lo + (((history * w) * sky) * f_r) * cosine / pdf;
-          } else {
-            Lo = Lo + ((history * sky) * f_r) * cosine / pdf;
-          }
-          break;
-        }
-        Hit nh;
-        shade_point<P5TRI>(sc, nt, ntt, hit.P, L, nh);
-        Lo = Lo + ((history * nh.m.emissive) * f_r) * cosine / pdf;
-        history = history * (f_r * cosine / pdf);
-        hit = nh;
-      }
-      colour = Le0 + Lo;
-    }
+    uint32_t seed;
+    const f3 dir = camera_dir(p, ix, iy, frame, seed);
+    const f3 org3 = mk(p.eye[0], p.eye[1], p.eye[2]);
+    colour = path_radiance<INTEG, FULLCTR, PATHLOG>(sc, org3, dir, ix, iy, frame, seed, p.max_bounce, p.env_clamp, stack, ctr, lg);
     if (PATHLOG) {
       a.log_colour[pix * 3 + 0] = colour.x;
       a.log_colour[pix * 3 + 1] = colour.y;
@@ -729,6 +747,51 @@ __global__ __launch_bounds__(256) void env_sample_kernel(DevScene sc, const floa
   if (i >= n) return;
   Counters ctr = {0, 0, 0, 0, 0, 0, 0};
   st3(L_out + (size_t)i * 3, sample_hdr<false>(sc, xip[(size_t)i * 2], xip[(size_t)i * 2 + 1], ctr));
+}
+
+// ---- path queries (include/ezrt_path.h): one element per lane.  sample_xyf names the pixel-sample (ix, iy, frame) whose random
+// numbers an element uses.
+//
+// ezrt_camera_rays_device: (eye, camera_dir) of each pixel-sample: the primary ray a render call shoots for it
+__global__ __launch_bounds__(256) void camera_rays_kernel(EzrtRenderParams p, const uint32_t* xyf, uint32_t n, float* rays) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* q = xyf + (size_t)i * 3;
+  uint32_t seed;
+  const f3 dir = camera_dir(p, q[0], q[1], q[2], seed);
+  float* o = rays + (size_t)i * 6;
+  o[0] = p.eye[0], o[1] = p.eye[1], o[2] = p.eye[2];
+  st3(o + 3, dir);
+}
+
+// ezrt_query_radiance_device: path_radiance along the caller's ray, a whole path per lane as in trace_kernel -- the same LDS
+// traversal stack, a column per lane (the launch sizes it as the megakernel's: stack_lds_bytes).  The RNG starts where main() has
+// it at its hitBVH call: the pixel-sample's seed behind the two jitter draws.  Work counters stay in the lane and are dropped.
+struct RadianceArgs {
+  DevScene sc;
+  const float* rays;    // n x 6
+  const uint32_t* xyf;  // n x 3
+  uint32_t n;
+  int32_t max_bounce;
+  float env_clamp;
+  float* radiance;      // n x 3
+};
+template <int INTEG>
+__global__ __launch_bounds__(BLOCK) void radiance_query_kernel(RadianceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const float* r = a.rays + (size_t)i * 6;
+  const uint32_t* q = a.xyf + (size_t)i * 3;
+  const uint32_t ix = q[0], iy = q[1], frame = q[2];
+  uint32_t seed = pixel_seed(ix, iy, frame);
+  (void)wang_hash(seed); // the jitter draws of main(): the ray is the caller's, the state behind them the pixel-sample's
+  (void)wang_hash(seed);
+  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
+  const PathLog none = {nullptr, nullptr};
+  const f3 c = path_radiance<INTEG, false, false>(a.sc, ld3(r), ld3(r + 3), ix, iy, frame, seed, a.max_bounce, a.env_clamp,
+                                                   lds_stack + threadIdx.x, ctr, none);
+  st3(a.radiance + (size_t)i * 3, c);
 }
 
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).

@@ -5,6 +5,7 @@
 #include "ezrt_query.h"
 #include "ezrt_surface.h"
 #include "ezrt_shade.h"
+#include "ezrt_path.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1438,6 +1439,55 @@ int ezrt_env_sample_device(EzrtScene* s, const float* xi, int n, float* L, void*
     hipStream_t st = (hipStream_t)stream;
     return shade_call(s, {{xi, K * 2 * sizeof(float)}, {L, K * 3 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(env_sample_kernel, g, b, 0, st, s->dev(), xi, (uint32_t)n, L);
+    });
+  });
+}
+
+// ---- path queries on device memory (include/ezrt_path.h): one kernel each on `st`, no scratch; checked, launched and ordered
+// against a refit by shade_call
+int ezrt_camera_rays_device(EzrtScene* s, const EzrtRenderParams* p, const uint32_t* sample_xyf, int n, float* rays_od6, void* stream) {
+  return ezi::guarded("ezrt_camera_rays_device", [&]() -> int {
+    if (!s || !sample_xyf || !rays_od6 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!p) return fail(EZRT_ERR_INVALID, "params is NULL");
+    if (p->width <= 0 || p->height <= 0) return fail(EZRT_ERR_INVALID, "width/height must be positive");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{sample_xyf, K * 3 * sizeof(uint32_t)}, {rays_od6, K * 6 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(camera_rays_kernel, g, b, 0, st, *p, sample_xyf, (uint32_t)n, rays_od6);
+    });
+  });
+}
+int ezrt_query_radiance_device(EzrtScene* s, int integrator, int max_bounce, float env_clamp, const float* rays_od6,
+                               const uint32_t* sample_xyf, int n, float* radiance, void* stream) {
+  return ezi::guarded("ezrt_query_radiance_device", [&]() -> int {
+    if (!s || !rays_od6 || !sample_xyf || !radiance || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    // (the states a render call rejects, in its words: validate_params)
+    if (max_bounce < 0 || max_bounce > 64) return fail(EZRT_ERR_INVALID, "max_bounce out of range [0,64]");
+    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if ((integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO) && !s->has_cache)
+      return fail(EZRT_ERR_INVALID, "integrator 51 needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{rays_od6, 2 * v3}, {sample_xyf, K * 3 * sizeof(uint32_t)}, {radiance, v3}}, K, st, [&](dim3 g, dim3 b) {
+      RadianceArgs a;
+      a.sc = s->dev();
+      a.rays = rays_od6;
+      a.xyf = sample_xyf;
+      a.n = (uint32_t)n;
+      a.max_bounce = max_bounce;
+      a.env_clamp = env_clamp;
+      a.radiance = radiance;
+      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
+      switch (integrator) { // the one dispatch: each kernel is compiled for its integrator
+      case EZRT_INTEGRATOR_P3_DIFFUSE: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P3_DIFFUSE>, g, b, lds, st, a); break;
+      case EZRT_INTEGRATOR_P4_DISNEY: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P4_DISNEY>, g, b, lds, st, a); break;
+      case EZRT_INTEGRATOR_P5_SOBOL: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_SOBOL>, g, b, lds, st, a); break;
+      case EZRT_INTEGRATOR_P5_MIS: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, lds, st, a); break;
+      default: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, lds, st, a); break;
+      }
     });
   });
 }
