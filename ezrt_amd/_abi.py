@@ -154,6 +154,18 @@ PATH_ABI = {
 }
 
 
+# stream-ordered all-hits queries on device memory, libezrt_hip.so only (include/ezrt_multihit.h); pointers are device addresses
+MULTIHIT_ABI = {
+    # s, rays_od6, t_max, n_rays, max_hits, tri_id, t_hit, n_hits, stream
+    "ezrt_query_all_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    # s, rays_od6, tri_id, t_hit, n, integrator, hit_point, normal, inside, stream
+    "ezrt_surface_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+}
+ALL_HITS_MAX = 64  # EZRT_ALL_HITS_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -220,7 +232,7 @@ def load_hip():
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
-        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, REFIT_ABI):
+        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

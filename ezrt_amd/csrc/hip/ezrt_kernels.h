@@ -794,6 +794,148 @@ __global__ __launch_bounds__(BLOCK) void radiance_query_kernel(RadianceArgs a) {
   st3(a.radiance + (size_t)i * 3, c);
 }
 
+// ---- all-hits queries (include/ezrt_multihit.h): one ray per lane.
+//
+// ezrt_query_all_hits_device: hit_bvh's walk -- the reference's binary records in the reference's order, unpruned, the LDS traversal
+// stack a column per lane (launched with stack_lds_bytes, as radiance_query_kernel) -- that keeps EVERY triangle hit_triangle_t
+// accepts below the ray's bound instead of the nearest: the visit order, and with it the order of equal t, is the reference's by
+// construction.  The sorted list lives in the ray's own output row (global memory, K = max_hits entries): a ray is accepted by a
+// handful of triangles and tests hundreds, so the row is touched a few times per ray, while K * 256 entries in LDS would not fit
+// beside the stack at K = 64 (64 KiB of keys alone) and K entries in registers would cost the walk its occupancy.  `nb` entries
+// are in the row, sorted; `last` holds the t of entry K - 1 once the row is full: a candidate that is not strictly below it is
+// counted and touches no memory.  An insertion shifts the strictly greater entries up one slot (the K-th falls out), so equal t
+// stay in visit order.  HAVE_T = false (no t_hit): the keys of the entries in the row are recomputed from their ids -- t is a pure
+// function of (triangle, ray) -- by the same hit_triangle_t.
+// Afterwards each wave fills the unused slots of its 64 rows with {-1, INF} together: consecutive lanes write consecutive words.
+struct AllHitsArgs {
+  DevScene sc;
+  const float* rays;  // n x 6
+  const float* t_max; // n, or null
+  uint32_t n;
+  int32_t K;
+  FastDiv div_k;      // / K (the fill)
+  int32_t* tri;       // n x K
+  float* t;           // n x K, or null (HAVE_T = false)
+  int32_t* n_hits;    // n, or null
+};
+template <bool HAVE_T>
+__global__ __launch_bounds__(BLOCK) void all_hits_kernel(AllHitsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  const int K = a.K;
+  int nb = 0;
+  if (i < a.n) {
+    const DevScene& sc = a.sc;
+    const float* r = a.rays + (size_t)i * 6;
+    const f3 S = ld3(r), d = ld3(r + 3);
+    // t < min(t_max, INF); a NaN t_max admits nothing (no hit has t < 0.0005)
+    float bound = INF;
+    if (a.t_max) {
+      const float tm = a.t_max[i];
+      bound = tm < INF ? tm : (tm >= INF ? INF : 0.0f);
+    }
+    int32_t* ri = a.tri + (size_t)i * K;
+    float* rt = HAVE_T ? a.t + (size_t)i * K : nullptr;
+    uint32_t count = 0;
+    float last = INF;
+    auto key = [&](int j) -> float {
+      if (HAVE_T) return rt[j];
+      float tj = INF;
+      (void)hit_triangle_t(sc.tri_geom + (size_t)ri[j] * 3, S, d, tj);
+      return tj;
+    };
+    auto put = [&](int j, int32_t id, float tj) {
+      ri[j] = id;
+      if (HAVE_T) rt[j] = tj;
+      if (j == K - 1) last = tj;
+    };
+    int* stack = lds_stack + threadIdx.x;
+    const f3 inv = mk(ez_rcp(d.x), ez_rcp(d.y), ez_rcp(d.z));
+    int sp = 0;
+    uint32_t ref = sc.root_ref;
+    for (;;) {
+      if (ref & LEAF_BIT) {
+        const int first = (int)(ref & 0x00ffffffu);
+        const int n = (int)((ref >> 24) & 0x7fu) + 1;
+        for (int k = first; k < first + n; k++) {
+          float t;
+          if (!hit_triangle_t(sc.tri_geom + (size_t)k * 3, S, d, t) || !(t < bound)) continue;
+          count++;
+          if (nb == K && !(t < last)) continue; // behind a full row: counted only
+          int j = nb < K ? nb++ : K - 1;
+          while (j > 0) {
+            const float tp = key(j - 1);
+            if (!(tp > t)) break;
+            put(j, ri[j - 1], tp);
+            j--;
+          }
+          put(j, k, t);
+        }
+      } else {
+        const float4* q = sc.inner + (size_t)ref * 4;
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+        const float d1 = hit_aabb(S, inv, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y));
+        const float d2 = hit_aabb(S, inv, mk(q1.z, q1.w, q2.x), mk(q2.y, q2.z, q2.w));
+        const uint32_t left = __float_as_uint(q3.x), right = __float_as_uint(q3.y);
+        if (d1 > 0.0f && d2 > 0.0f) {
+          if (d1 < d2) { // left first: push right, continue with left
+            stack[sp * BLOCK] = (int)right;
+            sp++;
+            ref = left;
+          } else {
+            stack[sp * BLOCK] = (int)left;
+            sp++;
+            ref = right;
+          }
+          continue;
+        } else if (d1 > 0.0f) {
+          ref = left;
+          continue;
+        } else if (d2 > 0.0f) {
+          ref = right;
+          continue;
+        }
+      }
+      if (sp == 0) break;
+      sp--;
+      ref = (uint32_t)stack[sp * BLOCK];
+    }
+    if (a.n_hits) a.n_hits[i] = (int32_t)count;
+  }
+  // the unused slots of the wave's 64 rows: one flat run of 64 K words from the wave's first row
+  const uint32_t lane = threadIdx.x & 63u;
+  const size_t base = (size_t)(i - lane) * K;
+  for (uint32_t e = lane; e < 64u * (uint32_t)K; e += 64u) {
+    const uint32_t row = fastdiv(e, a.div_k);
+    const uint32_t slot = e - row * (uint32_t)K;
+    const int used = __shfl(nb, (int)row);
+    if (i - lane + row < a.n && slot >= (uint32_t)used) {
+      a.tri[base + e] = -1;
+      if (HAVE_T) a.t[base + e] = INF;
+    }
+  }
+}
+
+// ezrt_surface_at_device: surface_point for hits the caller holds -- {triangle, t} of element i along ray i.  An id outside the
+// scene writes zeros; point / normal / inside may each be null (not written).
+template <bool P5TRI>
+__global__ __launch_bounds__(256) void surface_at_kernel(const float4* tri_geom, const float4* tri_shade, int32_t n_tri, const float* rays,
+                                                         const int32_t* tri_id, const float* t_hit, uint32_t n, float* point,
+                                                         float* normal, uint8_t* inside) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  f3 P = mk(0.0f, 0.0f, 0.0f), N = mk(0.0f, 0.0f, 0.0f);
+  bool in = false;
+  if ((uint32_t)tri < (uint32_t)n_tri) {
+    const float* r = rays + (size_t)i * 6;
+    surface_point<P5TRI>(tri_geom, tri_shade, tri, t_hit[i], ld3(r), ld3(r + 3), P, N, in, [](float4) {});
+  }
+  if (point) st3(point + (size_t)i * 3, P);
+  if (normal) st3(normal + (size_t)i * 3, N);
+  if (inside) inside[i] = in ? 1u : 0u;
+}
+
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).
 // res[0] = mismatches, res[1] = the smallest mismatching pattern.
 __global__ void rcp_audit_kernel(unsigned long long* res) {

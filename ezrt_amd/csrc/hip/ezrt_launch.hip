@@ -6,6 +6,7 @@
 #include "ezrt_surface.h"
 #include "ezrt_shade.h"
 #include "ezrt_path.h"
+#include "ezrt_multihit.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1488,6 +1489,57 @@ int ezrt_query_radiance_device(EzrtScene* s, int integrator, int max_bounce, flo
       case EZRT_INTEGRATOR_P5_MIS: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, lds, st, a); break;
       default: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, lds, st, a); break;
       }
+    });
+  });
+}
+
+// ---- all-hits queries on device memory (include/ezrt_multihit.h): one kernel each on `st`, no scratch (a ray's sorted list is kept
+// in its own output row); checked, launched and ordered against a refit by shade_call
+int ezrt_query_all_hits_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int max_hits, int32_t* tri_id,
+                               float* t_hit, int32_t* n_hits, void* stream) {
+  return ezi::guarded("ezrt_query_all_hits_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
+    if (max_hits < 1 || max_hits > EZRT_ALL_HITS_MAX) return fail(EZRT_ERR_INVALID, "max_hits out of range [1,%d]", EZRT_ALL_HITS_MAX);
+    if (n_rays == 0) return 0;
+    const size_t N = (size_t)n_rays, K = (size_t)max_hits;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{rays_od6, N * 6 * sizeof(float)}, {t_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {t_hit, N * K * sizeof(float)}, {n_hits, N * sizeof(int32_t)}}, N, st, [&](dim3 g, dim3 b) {
+      AllHitsArgs a;
+      a.sc = s->dev();
+      a.rays = rays_od6;
+      a.t_max = t_max;
+      a.n = (uint32_t)n_rays;
+      a.K = max_hits;
+      a.div_k = make_fastdiv((uint32_t)max_hits);
+      a.tri = tri_id;
+      a.t = t_hit;
+      a.n_hits = n_hits;
+      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
+      if (t_hit) hipLaunchKernelGGL(all_hits_kernel<true>, g, b, lds, st, a);
+      else hipLaunchKernelGGL(all_hits_kernel<false>, g, b, lds, st, a);
+    });
+  });
+}
+int ezrt_surface_at_device(EzrtScene* s, const float* rays_od6, const int32_t* tri_id, const float* t_hit, int n, int integrator,
+                           float* hit_point, float* normal, uint8_t* inside, void* stream) {
+  return ezi::guarded("ezrt_surface_at_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || !t_hit || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!hit_point && !normal && !inside) return fail(EZRT_ERR_INVALID, "one of hit_point, normal and inside is required");
+    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const bool p5 = integrator >= EZRT_INTEGRATOR_P5_SOBOL; // the render's choice of the smooth-normal form, as ezrt_query_surface_device
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{rays_od6, 2 * v3}, {tri_id, K * sizeof(int32_t)}, {t_hit, K * sizeof(float)}, {hit_point, v3}, {normal, v3},
+                          {inside, K}}, K, st, [&](dim3 g, dim3 b) {
+      const DevScene sc = s->dev();
+      if (p5)
+        hipLaunchKernelGGL(surface_at_kernel<true>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
+                           (uint32_t)n, hit_point, normal, inside);
+      else
+        hipLaunchKernelGGL(surface_at_kernel<false>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
+                           (uint32_t)n, hit_point, normal, inside);
     });
   });
 }

@@ -1,9 +1,11 @@
-"""Stream-ordered ray queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h).
+"""Stream-ordered ray queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
     hit = query.occluded(scene, rays, t_max)          # is anything in the way before t_max?  (bool)
     tri, t, point, normal, inside = query.surface(scene, rays)   # closest hit + hit point, shading normal, side (include/ezrt_surface.h)
+    tri, t, count = query.all_hits(scene, rays, max_hits)        # every triangle the ray crosses, nearest first (include/ezrt_multihit.h)
+    point, normal, inside = query.surface_at(scene, rays, tri, t)   # the surface attributes of hits already held: every layer's
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
@@ -38,6 +40,11 @@ def _scene_lib(scene, abi):
 
 def _check(scene, rays, t_max):
     lib = _scene_lib(scene, _abi.QUERY_ABI)
+    return lib, _check_rays(rays, t_max)
+
+
+def _check_rays(rays, t_max):
+    """The number of rays, after the checks every query makes of its rays and t_max."""
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
         raise TypeError("rays must be a GPU tensor")
     if rays.dtype != torch.float32:
@@ -60,7 +67,7 @@ def _check(scene, rays, t_max):
     n = rays.numel() // 6
     if n > 2**31 - 1:
         raise ValueError("at most 2^31 - 1 rays per call")
-    return lib, n
+    return n
 
 
 def _stream(rays, stream):
@@ -144,3 +151,72 @@ def surface(scene, rays, t_max=None, integrator=_abi.INTEGRATOR_P5_SOBOL, stream
                                                P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
     _keep((rays, t_max, tri, t, point, normal, inside), ts, rays)
     return Surface(tri, t, point, normal, inside.view(torch.bool))
+
+
+def all_hits(scene, rays, max_hits, t_max=None, stream=None):
+    """(tri int32 [..., max_hits], t float32 [..., max_hits], count int32 [...]): every triangle the ray crosses below t_max, sorted
+    by distance (equal distances in the reference's visit order: slot 0 is `closest`'s answer on the bits).  `count` is the full
+    number of crossings and may exceed max_hits (1 .. 64); the slots beyond it hold (-1, 114514)."""
+    if not isinstance(max_hits, int) or isinstance(max_hits, bool) or not 1 <= max_hits <= _abi.ALL_HITS_MAX:
+        raise ValueError("max_hits must be an int in [1, %d], not %r" % (_abi.ALL_HITS_MAX, max_hits))
+    n = _check_rays(rays, t_max)
+    lib = _scene_lib(scene, _abi.MULTIHIT_ABI)
+    lead = tuple(rays.shape[:-1])
+    if n * max_hits > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_hits,), dtype=torch.int32, device=rays.device)
+    t = torch.empty(lead + (max_hits,), dtype=torch.float32, device=rays.device)
+    count = torch.empty(lead, dtype=torch.int32, device=rays.device)
+    if n == 0:
+        return tri, t, count
+    h, ts = _stream(rays, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_all_hits_device(scene._h, P(rays.data_ptr()), P(t_max.data_ptr()) if t_max is not None else None, n,
+                                                max_hits, P(tri.data_ptr()), P(t.data_ptr()), P(count.data_ptr()), P(h)))
+    _keep((rays, t_max, tri, t, count), ts, rays)
+    return tri, t, count
+
+
+def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=None):
+    """(point float32 tri.shape + (3,), normal float32 tri.shape + (3,), inside bool tri.shape): for triangle tri[...] at distance
+    t[...] along its ray, what `surface` gives for its winner.  `tri` (int32) and `t` (float32) have the shape rays.shape[:-1], or one
+    trailing dimension more -- the output of `all_hits` -- and every entry of a row then belongs to the row's ray.  An id that is no
+    triangle of the scene (a miss, -1) gives zeros."""
+    _check_rays(rays, None)
+    lib = _scene_lib(scene, _abi.MULTIHIT_ABI)
+    if integrator not in _SURFACE_INTEGRATORS:
+        raise ValueError("integrator must be one of %s, not %r" % (_SURFACE_INTEGRATORS, integrator))
+    lead = tuple(rays.shape[:-1])
+    for name, x, dtype in (("tri", tri, torch.int32), ("t", t, torch.float32)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise TypeError("%s must be a GPU tensor" % name)
+        if x.dtype != dtype:
+            raise TypeError("%s must be %s, not %s" % (name, str(dtype).replace("torch.", ""), x.dtype))
+        if x.device != rays.device:
+            raise ValueError("%s is on %s, the rays on %s" % (name, x.device, rays.device))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    shape = tuple(tri.shape)
+    if shape != lead and shape[:-1] != lead:
+        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
+    if tuple(t.shape) != shape:
+        raise ValueError("t must have shape %s, not %s" % (shape, tuple(t.shape)))
+    n = tri.numel()
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 hits per call")
+    point = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
+    normal = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
+    inside = torch.empty(shape, dtype=torch.uint8, device=rays.device)
+    if n == 0:
+        return point, normal, inside.view(torch.bool)
+    h, ts = _stream(rays, stream)
+    per_hit = rays
+    if shape != lead:                                           # a ray per entry of its row, copied on the query's own stream
+        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=rays.device)
+        with torch.cuda.stream(on):
+            per_hit = rays.unsqueeze(-2).expand(lead + (shape[-1], 6)).contiguous()
+    P = C.c_void_p
+    _call(scene, lib.ezrt_surface_at_device(scene._h, P(per_hit.data_ptr()), P(tri.data_ptr()), P(t.data_ptr()), n, int(integrator),
+                                            P(point.data_ptr()), P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
+    _keep((rays, per_hit, tri, t, point, normal, inside), ts, rays)
+    return point, normal, inside.view(torch.bool)
