@@ -166,6 +166,14 @@ MULTIHIT_ABI = {
 ALL_HITS_MAX = 64  # EZRT_ALL_HITS_MAX
 
 
+# stream-ordered closest-point queries on device memory, libezrt_hip.so only (include/ezrt_closest_point.h); pointers are device addresses
+CLOSEST_POINT_ABI = {
+    # s, points3, d_max, n, tri_id, point, dist, bary, stream
+    "ezrt_query_closest_point_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -232,7 +240,7 @@ def load_hip():
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
-        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, REFIT_ABI):
+        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

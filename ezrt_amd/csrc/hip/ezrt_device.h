@@ -289,6 +289,81 @@ EZD bool hit_triangle_t(const float4* __restrict__ g, f3 S, f3 d, float& t_out) 
   return r1 || r2;
 }
 
+// ---- closest-point queries (include/ezrt_closest_point.h, where the definition is the contract): the region form of the
+// point-triangle projection, case by case in the header's order, then q clamped to the triangle's bounding box.  Returns dist2 =
+// dot(p - q, p - q); q and the barycentrics (v, w) of the projection come back by reference.
+EZD float closest_point_triangle(const float4* __restrict__ g, f3 p, f3& q, float& v, float& w) {
+  const float4 ga = g[0], gb = g[1], gc = g[2];
+  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  const f3 ab = b - a, ac = c - a, ap = p - a;
+  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+  const f3 bp = p - b;
+  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+  const f3 cp = p - c;
+  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+  if (d1 <= 0.0f && d2 <= 0.0f) {
+    v = 0.0f, w = 0.0f;
+  } else if (d3 >= 0.0f && d4 <= d3) {
+    v = 1.0f, w = 0.0f;
+  } else {
+    const float vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+      v = d1 / (d1 - d3), w = 0.0f;
+    } else if (d6 >= 0.0f && d5 <= d6) {
+      v = 0.0f, w = 1.0f;
+    } else {
+      const float vb = d5 * d2 - d1 * d6;
+      if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+        v = 0.0f, w = d2 / (d2 - d6);
+      } else {
+        const float va = d3 * d6 - d5 * d4;
+        if (va <= 0.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f) {
+          w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+          v = 1.0f - w;
+        } else {
+          const float s = va + vb + vc;
+          v = vb / s, w = vc / s;
+        }
+      }
+    }
+  }
+  const f3 qp = (a + ab * v) + ac * w;
+  const f3 lo = mk(ez_min(ez_min(a.x, b.x), c.x), ez_min(ez_min(a.y, b.y), c.y), ez_min(ez_min(a.z, b.z), c.z));
+  const f3 hi = mk(ez_max(ez_max(a.x, b.x), c.x), ez_max(ez_max(a.y, b.y), c.y), ez_max(ez_max(a.z, b.z), c.z));
+  q = mk(qp.x < lo.x ? lo.x : (qp.x > hi.x ? hi.x : qp.x), qp.y < lo.y ? lo.y : (qp.y > hi.y ? hi.y : qp.y),
+         qp.z < lo.z ? lo.z : (qp.z > hi.z ? hi.z : qp.z));
+  const f3 e = p - q;
+  return dot(e, e);
+}
+// The running answer of one query point.  A candidate is a triangle with a finite dist2 <= the bound; the smallest dist2 wins and,
+// among equal dist2, the smallest index -- whatever the order in which the triangles are met.  `best` starts as the bound B
+// (tri = -1): it is the pruning radius of the walk from the first step on.
+struct ClosestBest {
+  float best, v, w;
+  int32_t tri;
+  f3 q;
+};
+EZD void closest_point_candidate(ClosestBest& r, const float4* __restrict__ tri_geom, int32_t k, f3 p) {
+  f3 q;
+  float v, w;
+  const float d2 = closest_point_triangle(tri_geom + (size_t)k * 3, p, q, v, w);
+  // (d2 <= best is false for a NaN d2, d2 < inf for an infinite one; best is never NaN)
+  if (d2 < __builtin_inff() && (d2 < r.best || (d2 == r.best && (r.tri < 0 || k < r.tri)))) {
+    r.best = d2;
+    r.tri = k;
+    r.q = q;
+    r.v = v;
+    r.w = w;
+  }
+}
+// lb of a box: dot(g, g), g = max(lo - p, 0, p - hi) per axis (fmaxf: a NaN difference counts as 0).  For a finite p and a box that
+// holds the bounding box of a triangle, lb <= that triangle's dist2 on the bits (ezrt_kernels.h: closest_point_kernel).
+EZD float closest_point_box(f3 p, f3 lo, f3 hi) {
+  const f3 g = mk(__builtin_fmaxf(__builtin_fmaxf(lo.x - p.x, 0.0f), p.x - hi.x), __builtin_fmaxf(__builtin_fmaxf(lo.y - p.y, 0.0f), p.y - hi.y),
+                  __builtin_fmaxf(__builtin_fmaxf(lo.z - p.z, 0.0f), p.z - hi.z));
+  return dot(g, g);
+}
+
 // hitBVH: P5/fsh:254-306 + hitArray 238-251.  Unpruned, near-first, ties go
 // right-first, strict < keeps the first-found hit -- identical visit order per
 // ray.  The traversal stack lives in LDS: `stack` points at this lane's column

@@ -936,6 +936,136 @@ __global__ __launch_bounds__(256) void surface_at_kernel(const float4* tri_geom,
   if (inside) inside[i] = in ? 1u : 0u;
 }
 
+// ---- closest-point queries (include/ezrt_closest_point.h): one query point per lane.
+//
+// WALK = true, the pruned route (the scene prunes: boxes nested, every leaf box holds its triangles).  A best-first walk over the
+// 4-WIDE records (ezrt_records.h) -- chosen over the binary records because one 128-byte line gives four boxes, so a point needs
+// half the dependent loads on its way down, and because their boxes qualify: a slot's box is a caller's node box (nested, its
+// leaves hold their triangles) or an exact union of caller leaf boxes (retree_leaves, and every box after a refit), i.e. a
+// superset of the bounding box of every triangle below it.  The four slots are sorted by lb (closest_point_box), the walk goes on
+// with the nearest and pushes the others, farthest first, as {lb, ref} pairs on the lane's LDS stack column (two rows per entry;
+// launched with 2 * stack_need_cp rows: the exact worst case when any slot may be the nearest).  A slot is skipped only when
+// lb > best -- on equality it is descended: the tie rule needs every triangle at the minimum -- or when lb is not finite (no finite
+// dist2 below it); a popped entry is checked against the best of that moment again.
+// Why no margin is needed: for a triangle T below a box [lo, hi], q_T is clamped to T's bounding box, which lies in [lo, hi].  Per
+// axis either g = 0 <= |e|, or g = fl(lo - p) with q >= lo > p: q - p >= lo - p in the reals, rounding is monotone and
+// |fl(p - q)| = fl(q - p), so |e| >= g (the same on the hi side).  fl(x * x) is monotone in |x| and fl(fl(X + Y) + Z) in each of
+// X, Y, Z >= 0, so lb = dot(g, g) <= dot(e, e) = dist2_T ON THE BITS, overflow to +inf included.  Hence a skipped subtree holds no
+// triangle with dist2 <= best: neither a winner nor a tie is lost, and the order of the visits does not matter to
+// closest_point_candidate.  Triangles that no leaf holds (a caller's array may have some) are swept after the walk.
+// WALK = false, the sweep route: closest_point_candidate over tri_geom[0 .. n_tri), no tree, for scenes that do not prune.
+// A non-finite p misses at once: every dist2 is then inf or NaN.
+struct ClosestPointArgs {
+  const float4* tri_geom;
+  const float4* inner4;     // WALK: the 4-wide records, record 0 the root
+  const int32_t* uncovered; // WALK: triangles below no leaf
+  int32_t n_uncovered;
+  int32_t n_tri;
+  const float* points;      // n x 3
+  const float* d_max;       // n, or null
+  uint32_t n;
+  int32_t* tri;             // n
+  float* point;             // n x 3, or null
+  float* dist;              // n, or null
+  float* bary;              // n x 2, or null
+};
+constexpr int CP_BLOCK = 64; // one wave per workgroup: the stack column is 2 x 4 B per entry, and LDS is what bounds the occupancy
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void closest_point_kernel(ClosestPointArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const f3 p = ld3(a.points + (size_t)i * 3);
+  const float inf = __builtin_inff();
+  ClosestBest r;
+  r.best = inf;
+  r.tri = -1;
+  r.v = r.w = 0.0f;
+  r.q = mk(0.0f, 0.0f, 0.0f);
+  bool live = ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf;
+  if (a.d_max) {
+    const float dm = a.d_max[i];
+    if (dm >= 0.0f) r.best = dm * dm;
+    else live = false; // negative or NaN: no candidates
+  }
+  if (live && WALK) {
+    int* stack = lds_stack + threadIdx.x;
+    int sp = 0;
+    uint32_t ref = 0u;
+    for (;;) {
+      bool descend = false;
+      if (ref & LEAF_BIT) {
+        const int first = (int)(ref & 0x00ffffffu);
+        const int n = (int)((ref >> 24) & 0x7fu) + 1;
+        for (int k = first; k < first + n; k++) closest_point_candidate(r, a.tri_geom, k, p);
+      } else {
+        const float4* rec = a.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
+        const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
+        const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
+        uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
+        // (an unused slot -- an all-NaN box -- gets lb = inf: never descended)
+        float l0 = r0 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x));
+        float l1 = r1 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y));
+        float l2 = r2 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z));
+        float l3 = r3 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w));
+        auto cswap = [](float& la, uint32_t& ra, float& lb, uint32_t& rb) {
+          if (lb < la) {
+            const float tl = la;
+            la = lb, lb = tl;
+            const uint32_t tr = ra;
+            ra = rb, rb = tr;
+          }
+        };
+        cswap(l0, r0, l1, r1);
+        cswap(l2, r2, l3, r3);
+        cswap(l0, r0, l2, r2);
+        cswap(l1, r1, l3, r3);
+        cswap(l1, r1, l2, r2);
+        // ascending now: the slots worth a visit are a prefix
+        if (l3 <= r.best && l3 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l3);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r3;
+          sp++;
+        }
+        if (l2 <= r.best && l2 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l2);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r2;
+          sp++;
+        }
+        if (l1 <= r.best && l1 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l1);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r1;
+          sp++;
+        }
+        if (l0 <= r.best && l0 < inf) {
+          ref = r0;
+          descend = true;
+        }
+      }
+      if (descend) continue;
+      while (sp > 0) {
+        sp--;
+        if (__uint_as_float((uint32_t)stack[(2 * sp) * CP_BLOCK]) <= r.best) { // checked again: best may have shrunk since the push
+          ref = (uint32_t)stack[(2 * sp + 1) * CP_BLOCK];
+          descend = true;
+          break;
+        }
+      }
+      if (!descend) break;
+    }
+    for (int u = 0; u < a.n_uncovered; u++) closest_point_candidate(r, a.tri_geom, a.uncovered[u], p);
+  }
+  if (live && !WALK)
+    for (int k = 0; k < a.n_tri; k++) closest_point_candidate(r, a.tri_geom, k, p);
+  a.tri[i] = r.tri;
+  if (a.point) st3(a.point + (size_t)i * 3, r.q);
+  if (a.dist) a.dist[i] = r.tri >= 0 ? __builtin_sqrtf(r.best) : inf;
+  if (a.bary) {
+    a.bary[(size_t)i * 2] = r.v;
+    a.bary[(size_t)i * 2 + 1] = r.w;
+  }
+}
+
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).
 // res[0] = mismatches, res[1] = the smallest mismatching pattern.
 __global__ void rcp_audit_kernel(unsigned long long* res) {

@@ -7,6 +7,7 @@
 #include "ezrt_shade.h"
 #include "ezrt_path.h"
 #include "ezrt_multihit.h"
+#include "ezrt_closest_point.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1540,6 +1541,40 @@ int ezrt_surface_at_device(EzrtScene* s, const float* rays_od6, const int32_t* t
       else
         hipLaunchKernelGGL(surface_at_kernel<false>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
                            (uint32_t)n, hit_point, normal, inside);
+    });
+  });
+}
+
+// ---- closest-point queries on device memory (include/ezrt_closest_point.h): one kernel on `st`, no scratch; checked, launched and
+// ordered against a refit by shade_call.  The route is chosen per call: a refit can change whether the scene prunes.
+int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const float* d_max, int n, int32_t* tri_id, float* point,
+                                    float* dist, float* bary, void* stream) {
+  return ezi::guarded("ezrt_query_closest_point_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
+                          {point, N * 3 * sizeof(float)}, {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3, dim3) {
+      ClosestPointArgs a;
+      a.tri_geom = s->tri_geom.p;
+      a.inner4 = s->inner4.p;
+      a.uncovered = s->cp_uncovered.p;
+      a.n_uncovered = s->n_cp_uncovered;
+      a.n_tri = s->n_tri;
+      a.points = points3;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.tri = tri_id;
+      a.point = point;
+      a.dist = dist;
+      a.bary = bary;
+      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+      // the lane's stack column: {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that it exceeds the 64 KiB of a
+      // launch without opt-in (> 126 entries; none of the builders comes near) is swept instead
+      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) hipLaunchKernelGGL(closest_point_kernel<true>, g, b, lds, st, a);
+      else hipLaunchKernelGGL(closest_point_kernel<false>, g, b, 0, st, a);
     });
   });
 }

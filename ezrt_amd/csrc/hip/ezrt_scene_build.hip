@@ -379,6 +379,7 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   std::vector<HostNode> hn_kept;                  // the decoded caller nodes, kept for ezrt_scene_refit_device
   bool retreed = false;
   int n_inner4 = 0, stack_need4 = 1;
+  int stack_need_cp = 1; // entries the best-first walk of closest_point_kernel can have pending (any slot may be the nearest)
   {
     std::vector<HostNode> hn((size_t)n_nodes);
     for (int i = 1; i < n_nodes; i++) hn[(size_t)i] = decode_node(nodes, i);
@@ -477,6 +478,17 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
       }
       lap("  cuts + stack need");
       stack_need4 = std::max(1, need[0]);
+      {
+        std::vector<int> need_cp(recs.size(), 0);
+        for (size_t q = recs.size(); q-- > 0;) {
+          const Rec& r = recs[q];
+          int below = 0;
+          for (int k = 0; k < r.m; k++)
+            if (is_inner(r.slot[k])) below = std::max(below, need_cp[(size_t)rec_of[(size_t)r.slot[k]]]);
+          need_cp[q] = r.m - 1 + below;
+        }
+        stack_need_cp = std::max(1, need_cp[0]);
+      }
       // breadth-first numbering: the top of the tree is a prefix (staged in LDS)
       std::vector<int> order(1, 0), number(recs.size(), -1);
       number[0] = 0;
@@ -557,6 +569,26 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
     }
   }
   lap("tie tables");
+  // ---- closest-point queries (ezrt_closest_point.h): their answer ranges over EVERY triangle of the array, the 4-wide records reach
+  // the triangles of the leaves only -- the (usually empty) rest is listed and swept after the walk
+  std::vector<int32_t> cp_uncovered;
+  if (n_inner4 > 0) {
+    std::vector<unsigned char> held((size_t)n_tri, 0);
+    for (int q = 0; q < n_inner4; q++) {
+      const float4 rf = inner4[(size_t)q * N4_FLOAT4 + N4_ROW_REF];
+      const float f[4] = {rf.x, rf.y, rf.z, rf.w};
+      for (int k = 0; k < 4; k++) {
+        uint32_t u;
+        memcpy(&u, &f[k], 4);
+        if (u == REF_EMPTY || !(u & LEAF_BIT)) continue;
+        const int first = (int)(u & 0x00ffffffu), cnt = (int)((u >> 24) & 0x7fu) + 1;
+        for (int t = first; t < first + cnt; t++) held[(size_t)t] = 1;
+      }
+    }
+    for (int t = 0; t < n_tri; t++)
+      if (!held[(size_t)t]) cp_uncovered.push_back(t);
+  }
+  lap("closest-point coverage");
   std::vector<float4> geom((size_t)n_tri * 3);
   parallel_for(n_tri, 1 << 15, [&](int lo_i, int hi_i, int) {
   for (int i = lo_i; i < hi_i; i++) {
@@ -785,6 +817,12 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   SC_TRY(hipMemcpy(s->inner.p, inner.data(), inner.size() * sizeof(float4), hipMemcpyHostToDevice));
   s->n_inner4 = n_inner4;
   s->stack_need4 = stack_need4;
+  s->stack_need_cp = stack_need_cp;
+  s->n_cp_uncovered = (int)cp_uncovered.size();
+  if (!cp_uncovered.empty()) {
+    SC_TRY(s->cp_uncovered.ensure(cp_uncovered.size()));
+    SC_TRY(hipMemcpy(s->cp_uncovered.p, cp_uncovered.data(), cp_uncovered.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   s->retreed = retreed;
   s->prunable = prunable;
   s->prune_G = prune_G;

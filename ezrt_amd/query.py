@@ -1,4 +1,5 @@
-"""Stream-ordered ray queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h).
+"""Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
+include/ezrt_closest_point.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -6,6 +7,7 @@
     tri, t, point, normal, inside = query.surface(scene, rays)   # closest hit + hit point, shading normal, side (include/ezrt_surface.h)
     tri, t, count = query.all_hits(scene, rays, max_hits)        # every triangle the ray crosses, nearest first (include/ezrt_multihit.h)
     point, normal, inside = query.surface_at(scene, rays, tri, t)   # the surface attributes of hits already held: every layer's
+    tri, point, dist, bary = query.closest_point(scene, points)  # the nearest triangle, point and distance (include/ezrt_closest_point.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
@@ -22,6 +24,7 @@ from . import _abi, trace
 
 
 Surface = collections.namedtuple("Surface", "tri t point normal inside")
+ClosestPoint = collections.namedtuple("ClosestPoint", "tri point dist bary")
 
 
 def _scene_lib(scene, abi):
@@ -220,3 +223,47 @@ def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=
                                             P(point.data_ptr()), P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
     _keep((rays, per_hit, tri, t, point, normal, inside), ts, rays)
     return point, normal, inside.view(torch.bool)
+
+
+def closest_point(scene, points, d_max=None, stream=None):
+    """ClosestPoint(tri int32 [...], point float32 [..., 3], dist float32 [...], bary float32 [..., 2]): for every point of `points`
+    (a contiguous float32 GPU tensor [..., 3]) the nearest triangle of the scene, the nearest point on it, the distance and the
+    barycentrics (v, w) of that point -- attributes interpolate with (1 - v - w, v, w).  `d_max` (optional, float32, of shape
+    points.shape[:-1]) admits only triangles within that distance.  A miss is (-1, zeros, +inf, zeros).  Equal distances: the lowest
+    triangle index.  The definition, on the bits: include/ezrt_closest_point.h."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise TypeError("points must be a GPU tensor")
+    if points.dtype != torch.float32:
+        raise TypeError("points must be float32, not %s" % points.dtype)
+    if points.dim() < 1 or points.shape[-1] != 3:
+        raise ValueError("points must have shape [..., 3], not %s" % (tuple(points.shape),))
+    if not points.is_contiguous():
+        raise ValueError("points must be contiguous")
+    lead = tuple(points.shape[:-1])
+    if d_max is not None:
+        if not isinstance(d_max, torch.Tensor) or not d_max.is_cuda:
+            raise TypeError("d_max must be a GPU tensor")
+        if d_max.dtype != torch.float32:
+            raise TypeError("d_max must be float32, not %s" % d_max.dtype)
+        if d_max.device != points.device:
+            raise ValueError("d_max is on %s, the points on %s" % (d_max.device, points.device))
+        if tuple(d_max.shape) != lead:
+            raise ValueError("d_max must have shape %s, not %s" % (lead, tuple(d_max.shape)))
+        if not d_max.is_contiguous():
+            raise ValueError("d_max must be contiguous")
+    n = points.numel() // 3
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 points per call")
+    lib = _scene_lib(scene, _abi.CLOSEST_POINT_ABI)
+    tri = torch.empty(lead, dtype=torch.int32, device=points.device)
+    point = torch.empty(lead + (3,), dtype=torch.float32, device=points.device)
+    dist = torch.empty(lead, dtype=torch.float32, device=points.device)
+    bary = torch.empty(lead + (2,), dtype=torch.float32, device=points.device)
+    if n == 0:
+        return ClosestPoint(tri, point, dist, bary)
+    h, ts = _stream(points, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_closest_point_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n,
+                                                     P(tri.data_ptr()), P(point.data_ptr()), P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
+    _keep((points, d_max, tri, point, dist, bary), ts, points)
+    return ClosestPoint(tri, point, dist, bary)
