@@ -174,6 +174,18 @@ CLOSEST_POINT_ABI = {
 }
 
 
+# stream-ordered nearest-K queries on device memory, libezrt_hip.so only (include/ezrt_nearest.h); pointers are device addresses
+NEAREST_ABI = {
+    # s, points3, d_max, n, max_k, tri_id, dist, n_within, stream
+    "ezrt_query_nearest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    # s, points3, tri_id, n, point, dist, bary, stream
+    "ezrt_closest_point_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+}
+NEAREST_MAX = 64  # EZRT_NEAREST_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -240,7 +252,8 @@ def load_hip():
                 "ezrt_amd: %s is missing -- build it with `make hip` (or __graft_entry__.build()); "
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
-        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, REFIT_ABI):
+        for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
+                      REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

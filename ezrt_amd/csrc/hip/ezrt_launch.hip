@@ -8,6 +8,7 @@
 #include "ezrt_path.h"
 #include "ezrt_multihit.h"
 #include "ezrt_closest_point.h"
+#include "ezrt_nearest.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
@@ -1575,6 +1576,63 @@ int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const fl
       const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
       if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) hipLaunchKernelGGL(closest_point_kernel<true>, g, b, lds, st, a);
       else hipLaunchKernelGGL(closest_point_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+
+// ---- nearest-K queries on device memory (include/ezrt_nearest.h): one kernel each on `st`, no scratch (a point's sorted list is kept
+// in its own output rows); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by
+// ezrt_query_closest_point_device's condition; n_within selects the counting instance, which cannot shrink its radius below d_max.
+int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d_max, int n, int max_k, int32_t* tri_id, float* dist,
+                              int32_t* n_within, void* stream) {
+  return ezi::guarded("ezrt_query_nearest_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || !dist || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 1 || max_k > EZRT_NEAREST_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [1,%d]", EZRT_NEAREST_MAX);
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {dist, N * K * sizeof(float)}, {n_within, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      NearestArgs a;
+      a.tri_geom = s->tri_geom.p;
+      a.inner4 = s->inner4.p;
+      a.uncovered = s->cp_uncovered.p;
+      a.n_uncovered = s->n_cp_uncovered;
+      a.n_tri = s->n_tri;
+      a.points = points3;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)max_k);
+      a.tri = tri_id;
+      a.dist = dist;
+      a.n_within = n_within;
+      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+      // the lane's stack column, as closest_point_kernel's: {lb, ref} per pending entry (+ 1 of slack); a tree needing more than the
+      // 64 KiB of a launch without opt-in is swept instead
+      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) {
+        if (n_within) hipLaunchKernelGGL((nearest_kernel<true, true>), g, b, lds, st, a);
+        else hipLaunchKernelGGL((nearest_kernel<true, false>), g, b, lds, st, a);
+      } else {
+        if (n_within) hipLaunchKernelGGL((nearest_kernel<false, true>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((nearest_kernel<false, false>), g, b, 0, st, a);
+      }
+    });
+  });
+}
+int ezrt_closest_point_at_device(EzrtScene* s, const float* points3, const int32_t* tri_id, int n, float* point, float* dist, float* bary,
+                                 void* stream) {
+  return ezi::guarded("ezrt_closest_point_at_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!point && !dist && !bary) return fail(EZRT_ERR_INVALID, "one of point, dist and bary is required");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {point, N * 3 * sizeof(float)},
+                          {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(closest_point_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, point, dist,
+                         bary);
     });
   });
 }

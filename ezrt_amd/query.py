@@ -1,5 +1,5 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
-include/ezrt_closest_point.h).
+include/ezrt_closest_point.h, include/ezrt_nearest.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -8,9 +8,12 @@ include/ezrt_closest_point.h).
     tri, t, count = query.all_hits(scene, rays, max_hits)        # every triangle the ray crosses, nearest first (include/ezrt_multihit.h)
     point, normal, inside = query.surface_at(scene, rays, tri, t)   # the surface attributes of hits already held: every layer's
     tri, point, dist, bary = query.closest_point(scene, points)  # the nearest triangle, point and distance (include/ezrt_closest_point.h)
+    tri, dist, count = query.nearest(scene, points, k, d_max, count=True)   # the k nearest triangles in order, and how many lie within d_max
+    tri, point, dist, bary = query.closest_point_at(scene, points, tri)     # ... their nearest points and barycentrics (include/ezrt_nearest.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
-`t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
+`t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
+`d_max` (optional) a float32 GPU tensor of shape points.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
 `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the rays' device) and the functions
 return without waiting for it.  There is no t_min: a triangle is accepted at t >= 0.0005 only, so a ray leaving a surface needs its
 origin offset by the caller.  A miss is (-1, 114514.0): ezrt_query_hits' miss (the reference's INF).
@@ -25,6 +28,7 @@ from . import _abi, trace
 
 Surface = collections.namedtuple("Surface", "tri t point normal inside")
 ClosestPoint = collections.namedtuple("ClosestPoint", "tri point dist bary")
+Nearest = collections.namedtuple("Nearest", "tri dist count")
 
 
 def _scene_lib(scene, abi):
@@ -225,12 +229,8 @@ def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=
     return point, normal, inside.view(torch.bool)
 
 
-def closest_point(scene, points, d_max=None, stream=None):
-    """ClosestPoint(tri int32 [...], point float32 [..., 3], dist float32 [...], bary float32 [..., 2]): for every point of `points`
-    (a contiguous float32 GPU tensor [..., 3]) the nearest triangle of the scene, the nearest point on it, the distance and the
-    barycentrics (v, w) of that point -- attributes interpolate with (1 - v - w, v, w).  `d_max` (optional, float32, of shape
-    points.shape[:-1]) admits only triangles within that distance.  A miss is (-1, zeros, +inf, zeros).  Equal distances: the lowest
-    triangle index.  The definition, on the bits: include/ezrt_closest_point.h."""
+def _check_points(points, d_max):
+    """The number of points, after the checks every point query makes of its points and d_max."""
     if not isinstance(points, torch.Tensor) or not points.is_cuda:
         raise TypeError("points must be a GPU tensor")
     if points.dtype != torch.float32:
@@ -254,6 +254,17 @@ def closest_point(scene, points, d_max=None, stream=None):
     n = points.numel() // 3
     if n > 2**31 - 1:
         raise ValueError("at most 2^31 - 1 points per call")
+    return n
+
+
+def closest_point(scene, points, d_max=None, stream=None):
+    """ClosestPoint(tri int32 [...], point float32 [..., 3], dist float32 [...], bary float32 [..., 2]): for every point of `points`
+    (a contiguous float32 GPU tensor [..., 3]) the nearest triangle of the scene, the nearest point on it, the distance and the
+    barycentrics (v, w) of that point -- attributes interpolate with (1 - v - w, v, w).  `d_max` (optional, float32, of shape
+    points.shape[:-1]) admits only triangles within that distance.  A miss is (-1, zeros, +inf, zeros).  Equal distances: the lowest
+    triangle index.  The definition, on the bits: include/ezrt_closest_point.h."""
+    n = _check_points(points, d_max)
+    lead = tuple(points.shape[:-1])
     lib = _scene_lib(scene, _abi.CLOSEST_POINT_ABI)
     tri = torch.empty(lead, dtype=torch.int32, device=points.device)
     point = torch.empty(lead + (3,), dtype=torch.float32, device=points.device)
@@ -266,4 +277,73 @@ def closest_point(scene, points, d_max=None, stream=None):
     _call(scene, lib.ezrt_query_closest_point_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n,
                                                      P(tri.data_ptr()), P(point.data_ptr()), P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
     _keep((points, d_max, tri, point, dist, bary), ts, points)
+    return ClosestPoint(tri, point, dist, bary)
+
+
+def nearest(scene, points, k, d_max=None, count=False, stream=None):
+    """Nearest(tri int32 [..., k], dist float32 [..., k], count int32 [...] or None): for every point of `points` (a contiguous
+    float32 GPU tensor [..., 3]) the k nearest triangles of the scene, nearest first, and their distances; equal distances are ordered
+    by ascending triangle index, so slot 0 is `closest_point`'s (tri, dist) on the bits and a larger k only appends.  `d_max`
+    (optional, float32, of shape points.shape[:-1]) admits only triangles within that distance.  Slots beyond the candidates hold
+    (-1, +inf).  `count=True` also returns the full number of triangles within d_max, which may exceed k (1 .. 64) -- at a price: the
+    search can then not shrink below d_max, and without a d_max it visits every triangle for every point.  The definition, on the
+    bits: include/ezrt_nearest.h; `closest_point_at` gives the points and barycentrics of the rows."""
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= _abi.NEAREST_MAX:
+        raise ValueError("k must be an int in [1, %d], not %r" % (_abi.NEAREST_MAX, k))
+    n = _check_points(points, d_max)
+    lib = _scene_lib(scene, _abi.NEAREST_ABI)
+    lead = tuple(points.shape[:-1])
+    if n * k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (k,), dtype=torch.int32, device=points.device)
+    dist = torch.empty(lead + (k,), dtype=torch.float32, device=points.device)
+    within = torch.empty(lead, dtype=torch.int32, device=points.device) if count else None
+    if n == 0:
+        return Nearest(tri, dist, within)
+    h, ts = _stream(points, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_nearest_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n, k,
+                                               P(tri.data_ptr()), P(dist.data_ptr()), P(within.data_ptr()) if count else None, P(h)))
+    _keep((points, d_max, tri, dist, within), ts, points)
+    return Nearest(tri, dist, within)
+
+
+def closest_point_at(scene, points, tri, stream=None):
+    """ClosestPoint(tri, point float32 tri.shape + (3,), dist float32 tri.shape, bary float32 tri.shape + (2,)): for triangle
+    tri[...] and its point, what `closest_point` gives for its winner -- the nearest point on that triangle, its distance and
+    barycentrics.  `tri` (int32) has the shape points.shape[:-1], or one trailing dimension more -- the output of `nearest` -- and
+    every entry of a row then belongs to the row's point.  An id that is no triangle of the scene (an unused slot, -1) or a
+    non-finite distance gives (zeros, +inf, zeros).  `tri` is returned as given."""
+    _check_points(points, None)
+    lib = _scene_lib(scene, _abi.NEAREST_ABI)
+    lead = tuple(points.shape[:-1])
+    if not isinstance(tri, torch.Tensor) or not tri.is_cuda:
+        raise TypeError("tri must be a GPU tensor")
+    if tri.dtype != torch.int32:
+        raise TypeError("tri must be int32, not %s" % tri.dtype)
+    if tri.device != points.device:
+        raise ValueError("tri is on %s, the points on %s" % (tri.device, points.device))
+    if not tri.is_contiguous():
+        raise ValueError("tri must be contiguous")
+    shape = tuple(tri.shape)
+    if shape != lead and shape[:-1] != lead:
+        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
+    n = tri.numel()
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 elements per call")
+    point = torch.empty(shape + (3,), dtype=torch.float32, device=points.device)
+    dist = torch.empty(shape, dtype=torch.float32, device=points.device)
+    bary = torch.empty(shape + (2,), dtype=torch.float32, device=points.device)
+    if n == 0:
+        return ClosestPoint(tri, point, dist, bary)
+    h, ts = _stream(points, stream)
+    per_entry = points
+    if shape != lead:                                           # a point per entry of its row, copied on the query's own stream
+        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=points.device)
+        with torch.cuda.stream(on):
+            per_entry = points.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
+    P = C.c_void_p
+    _call(scene, lib.ezrt_closest_point_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(point.data_ptr()),
+                                                  P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
+    _keep((points, per_entry, tri, point, dist, bary), ts, points)
     return ClosestPoint(tri, point, dist, bary)
