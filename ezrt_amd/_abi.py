@@ -186,6 +186,17 @@ NEAREST_ABI = {
 NEAREST_MAX = 64  # EZRT_NEAREST_MAX
 
 
+# stream-ordered inside and signed-distance queries on device memory, libezrt_hip.so only (include/ezrt_inside.h); pointers are
+# device addresses
+INSIDE_ABI = {
+    # s, points3, n, axis, inside, crossings, stream
+    "ezrt_query_inside_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, points3, d_max, n, axis, tri_id, point, sdist, bary, inside, stream
+    "ezrt_query_signed_distance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -253,7 +264,7 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      REFIT_ABI):
+                      INSIDE_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

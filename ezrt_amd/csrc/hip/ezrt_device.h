@@ -364,6 +364,67 @@ EZD float closest_point_box(f3 p, f3 lo, f3 hi) {
   return dot(g, g);
 }
 
+// ---- inside queries (include/ezrt_inside.h, where the definition is the contract): the frame of an axis and the crossing rule
+// G1 .. G6 of one triangle, in the header's order.  The axis is a runtime permutation (uniform over the launch: the selects are on
+// scalar conditions), not six instances.
+struct InsideFrame {
+  int c;    // the ray's coordinate: axis >> 1
+  float g;  // -1 for the negative axes
+  float ps, pt, pu; // the query point in the frame
+};
+EZD float inside_pick(float x, float y, float z, int c) { return c == 0 ? x : (c == 1 ? y : z); }
+EZD InsideFrame inside_frame(int axis, f3 p) {
+  InsideFrame f;
+  f.c = axis >> 1;
+  f.g = (axis & 1) ? -1.0f : 1.0f;
+  f.ps = inside_pick(p.y, p.z, p.x, f.c);
+  f.pt = inside_pick(p.z, p.x, p.y, f.c);
+  f.pu = f.g * inside_pick(p.x, p.y, p.z, f.c);
+  return f;
+}
+EZD bool inside_crossed(const float4* __restrict__ tg, const InsideFrame& f) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  float as = inside_pick(ga.y, ga.z, ga.x, f.c), at = inside_pick(ga.z, ga.x, ga.y, f.c), au = f.g * inside_pick(ga.x, ga.y, ga.z, f.c);
+  float bs = inside_pick(gb.y, gb.z, gb.x, f.c), bt = inside_pick(gb.z, gb.x, gb.y, f.c), bu = f.g * inside_pick(gb.x, gb.y, gb.z, f.c);
+  float cs = inside_pick(gc.y, gc.z, gc.x, f.c), ct = inside_pick(gc.z, gc.x, gc.y, f.c), cu = f.g * inside_pick(gc.x, gc.y, gc.z, f.c);
+  const bool ka = as <= f.ps, kb = bs <= f.ps, kc = cs <= f.ps;
+  if (!((ka || kb || kc) && !(ka && kb && kc))) return false;                                                   // G1
+  if (!((at <= f.pt || bt <= f.pt || ct <= f.pt) && (at >= f.pt || bt >= f.pt || ct >= f.pt))) return false;    // G2
+  if (!(au > f.pu || bu > f.pu || cu > f.pu)) return false;                                                     // G3
+  auto cswap = [](float& xs, float& xt, float& xu, float& ys, float& yt, float& yu) {
+    if (ys < xs || (ys == xs && (yt < xt || (yt == xt && yu < xu)))) { // less(y, x)
+      float h = xs;
+      xs = ys, ys = h;
+      h = xt, xt = yt, yt = h;
+      h = xu, xu = yu, yu = h;
+    }
+  };
+  cswap(as, at, au, bs, bt, bu);
+  cswap(bs, bt, bu, cs, ct, cu);
+  cswap(as, at, au, bs, bt, bu);
+  // fp64 from here: (v0 v1 v2) = (a b c)
+  const double s0 = (double)as, t0 = (double)at, u0 = (double)au;
+  const double s1 = (double)bs - s0, t1 = (double)bt - t0, s2 = (double)cs - s0, t2 = (double)ct - t0;
+  const double A = s1 * t2 - t1 * s2;
+  if (!(__builtin_fabs(A) < __builtin_inf() && A != 0.0)) return false;                                         // G4
+  const double qs = (double)f.ps - s0, qt = (double)f.pt - t0;
+  const double E02 = s2 * qt - t2 * qs;
+  double E;
+  if (bs <= f.ps) {
+    const double s12 = (double)cs - (double)bs, t12 = (double)ct - (double)bt;
+    const double rs = (double)f.ps - (double)bs, rt = (double)f.pt - (double)bt;
+    E = s12 * rt - t12 * rs;
+  } else {
+    E = s1 * qt - t1 * qs;
+  }
+  if ((E02 < 0.0) == (E < 0.0)) return false;                                                                   // G5
+  const double u1 = (double)bu - u0, u2 = (double)cu - u0;
+  const double Ns = t1 * u2 - u1 * t2;
+  const double Nt = u1 * s2 - s1 * u2;
+  const double D = (Ns * qs + Nt * qt) + A * ((double)f.pu - u0);
+  return __builtin_fabs(D) < __builtin_inf() && ((D < 0.0 && A > 0.0) || (D > 0.0 && A < 0.0));                 // G6
+}
+
 // hitBVH: P5/fsh:254-306 + hitArray 238-251.  Unpruned, near-first, ties go
 // right-first, strict < keeps the first-found hit -- identical visit order per
 // ray.  The traversal stack lives in LDS: `stack` points at this lane's column

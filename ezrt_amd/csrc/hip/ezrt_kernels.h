@@ -1265,6 +1265,203 @@ __global__ __launch_bounds__(256) void closest_point_at_kernel(const float4* tri
   }
 }
 
+// ---- inside and signed-distance queries (include/ezrt_inside.h): one query point per lane, a workgroup of one wave.
+//
+// inside_count<WALK> returns crossings(p): the number of triangles with inside_crossed (ezrt_device.h: G1 .. G6 of the header).
+// WALK = true, the pruned route: a depth-first walk over the 4-wide records.  Only the rows of the record that the axis needs are
+// loaded -- lo and hi of s and t, and the far plane of u (hi for a positive axis, lo for a negative one; g * plane > p.u is
+// hi > p or lo < p, exactly) -- and a slot is descended when lo.s <= p.s <= hi.s, lo.t <= p.t <= hi.t and the far plane lies ahead.
+// These are comparisons on the stored fp32 values: G1 - G3 make a crossed triangle's own bounding box pass them, hence every box
+// that holds the triangle (the scene prunes: nested boxes, every leaf box holds its triangles), so no crossed triangle is skipped
+// and no slack is needed.  An unused slot (an all-NaN box) fails every comparison.  The count is an integer sum: the order of the
+// visits does not matter.
+// The stack.  Bare references, one row of 4 B per entry on the lane's LDS column.  Of a record with m slots the first that passes
+// is descended and the others that pass are pushed: at most m - 1 entries; a pop only removes.  So while one child subtree is
+// walked at most m - 1 entries of the record are pending, and the pending entries of any walk are bounded by the fold of
+// (m - 1 + deepest child) over the tree -- which is stack_need_cp (ezrt_scene_build.hip), the bound of every walk that descends
+// one slot and pushes at most three.  Launched with stack_need_cp + 1 rows.
+// Triangles that no leaf holds are swept after the walk.  WALK = false, the sweep route: every triangle, no tree.
+template <bool WALK>
+EZD int32_t inside_count(const float4* __restrict__ tri_geom, const float4* __restrict__ inner4, const int32_t* __restrict__ uncovered,
+                         int32_t n_uncovered, int32_t n_tri, int axis, f3 p, int* __restrict__ stack) {
+  const float inf = __builtin_inff();
+  if (!(ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf)) return 0; // a non-finite p has no crossings
+  const InsideFrame f = inside_frame(axis, p);
+  int32_t count = 0;
+  if (WALK) {
+    const int cs = f.c == 2 ? 0 : f.c + 1, ct = cs == 2 ? 0 : cs + 1;
+    const int row_u = ((axis & 1) ? N4_ROW_AA : N4_ROW_BB) + f.c;
+    int sp = 0;
+    uint32_t ref = 0u;
+    for (;;) {
+      uint32_t next = REF_EMPTY;
+      if (ref & LEAF_BIT) {
+        const int first = (int)(ref & 0x00ffffffu);
+        const int n = (int)((ref >> 24) & 0x7fu) + 1;
+#pragma unroll 1
+        for (int k = first; k < first + n; k++) count += inside_crossed(tri_geom + (size_t)k * 3, f) ? 1 : 0;
+      } else {
+        const float4* rec = inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
+        const float4 ls = rec[N4_ROW_AA + cs], lt = rec[N4_ROW_AA + ct], rf = rec[N4_ROW_REF];
+        const float4 hs = rec[N4_ROW_BB + cs], ht = rec[N4_ROW_BB + ct], fu = rec[row_u];
+        auto take = [&](float lo_s, float hi_s, float lo_t, float hi_t, float far_u, uint32_t r) {
+          if (r != REF_EMPTY && lo_s <= f.ps && f.ps <= hi_s && lo_t <= f.pt && f.pt <= hi_t && f.g * far_u > f.pu) {
+            if (next == REF_EMPTY) next = r;
+            else stack[(sp++) * CP_BLOCK] = (int)r;
+          }
+        };
+        take(ls.x, hs.x, lt.x, ht.x, fu.x, __float_as_uint(rf.x));
+        take(ls.y, hs.y, lt.y, ht.y, fu.y, __float_as_uint(rf.y));
+        take(ls.z, hs.z, lt.z, ht.z, fu.z, __float_as_uint(rf.z));
+        take(ls.w, hs.w, lt.w, ht.w, fu.w, __float_as_uint(rf.w));
+      }
+      if (next == REF_EMPTY) {
+        if (sp == 0) break;
+        next = (uint32_t)stack[(--sp) * CP_BLOCK];
+      }
+      ref = next;
+    }
+#pragma unroll 1
+    for (int u = 0; u < n_uncovered; u++) count += inside_crossed(tri_geom + (size_t)uncovered[u] * 3, f) ? 1 : 0;
+  } else {
+#pragma unroll 1
+    for (int k = 0; k < n_tri; k++) count += inside_crossed(tri_geom + (size_t)k * 3, f) ? 1 : 0;
+  }
+  return count;
+}
+struct InsideArgs {
+  const float4* tri_geom;
+  const float4* inner4;     // WALK: the 4-wide records, record 0 the root
+  const int32_t* uncovered; // WALK: triangles below no leaf
+  int32_t n_uncovered;
+  int32_t n_tri;
+  const float* points;      // n x 3
+  uint32_t n;
+  int32_t axis;             // 0..5
+  uint8_t* inside;          // n
+  int32_t* crossings;       // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void inside_kernel(InsideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const f3 p = ld3(a.points + (size_t)i * 3);
+  const int32_t count = inside_count<WALK>(a.tri_geom, a.inner4, a.uncovered, a.n_uncovered, a.n_tri, a.axis, p, lds_stack + threadIdx.x);
+  a.inside[i] = (uint8_t)(count & 1);
+  if (a.crossings) a.crossings[i] = count;
+}
+
+// ezrt_query_signed_distance_device: one launch; each lane runs the crossing walk and then the closest-point walk on the same LDS
+// stack column (launched with closest_point_kernel's 2 * (stack_need_cp + 1) rows: the crossing walk uses the first stack_need_cp of
+// them and leaves nothing pending).  The closest-point part is closest_point_kernel's loop, copied rather than shared so that
+// that kernel compiles as it did; it calls the same closest_point_box / closest_point_candidate, so tri, point and bary are that
+// kernel's on the bits and |sdist| its dist.
+struct SignedDistanceArgs {
+  ClosestPointArgs cp; // (cp.dist is sdist)
+  int32_t axis;        // 0..5
+  uint8_t* inside;     // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void signed_distance_kernel(SignedDistanceArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const ClosestPointArgs& a = sa.cp;
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const f3 p = ld3(a.points + (size_t)i * 3);
+  int* stack = lds_stack + threadIdx.x;
+  const bool in = (inside_count<WALK>(a.tri_geom, a.inner4, a.uncovered, a.n_uncovered, a.n_tri, sa.axis, p, stack) & 1) != 0;
+  const float inf = __builtin_inff();
+  ClosestBest r;
+  r.best = inf;
+  r.tri = -1;
+  r.v = r.w = 0.0f;
+  r.q = mk(0.0f, 0.0f, 0.0f);
+  bool live = ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf;
+  if (a.d_max) {
+    const float dm = a.d_max[i];
+    if (dm >= 0.0f) r.best = dm * dm;
+    else live = false; // negative or NaN: no candidates
+  }
+  if (live && WALK) {
+    int sp = 0;
+    uint32_t ref = 0u;
+    for (;;) {
+      bool descend = false;
+      if (ref & LEAF_BIT) {
+        const int first = (int)(ref & 0x00ffffffu);
+        const int n = (int)((ref >> 24) & 0x7fu) + 1;
+        for (int k = first; k < first + n; k++) closest_point_candidate(r, a.tri_geom, k, p);
+      } else {
+        const float4* rec = a.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
+        const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
+        const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
+        uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
+        float l0 = r0 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x));
+        float l1 = r1 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y));
+        float l2 = r2 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z));
+        float l3 = r3 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w));
+        auto cswap = [](float& la, uint32_t& ra, float& lb, uint32_t& rb) {
+          if (lb < la) {
+            const float tl = la;
+            la = lb, lb = tl;
+            const uint32_t tr = ra;
+            ra = rb, rb = tr;
+          }
+        };
+        cswap(l0, r0, l1, r1);
+        cswap(l2, r2, l3, r3);
+        cswap(l0, r0, l2, r2);
+        cswap(l1, r1, l3, r3);
+        cswap(l1, r1, l2, r2);
+        if (l3 <= r.best && l3 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l3);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r3;
+          sp++;
+        }
+        if (l2 <= r.best && l2 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l2);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r2;
+          sp++;
+        }
+        if (l1 <= r.best && l1 < inf) {
+          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l1);
+          stack[(2 * sp + 1) * CP_BLOCK] = (int)r1;
+          sp++;
+        }
+        if (l0 <= r.best && l0 < inf) {
+          ref = r0;
+          descend = true;
+        }
+      }
+      if (descend) continue;
+      while (sp > 0) {
+        sp--;
+        if (__uint_as_float((uint32_t)stack[(2 * sp) * CP_BLOCK]) <= r.best) {
+          ref = (uint32_t)stack[(2 * sp + 1) * CP_BLOCK];
+          descend = true;
+          break;
+        }
+      }
+      if (!descend) break;
+    }
+    for (int u = 0; u < a.n_uncovered; u++) closest_point_candidate(r, a.tri_geom, a.uncovered[u], p);
+  }
+  if (live && !WALK)
+    for (int k = 0; k < a.n_tri; k++) closest_point_candidate(r, a.tri_geom, k, p);
+  a.tri[i] = r.tri;
+  if (a.point) st3(a.point + (size_t)i * 3, r.q);
+  if (a.dist) {
+    const float d = r.tri >= 0 ? __builtin_sqrtf(r.best) : inf;
+    a.dist[i] = __uint_as_float(__float_as_uint(d) | (in ? 0x80000000u : 0u)); // the sign bit: |sdist| is dist on the bits
+  }
+  if (a.bary) {
+    a.bary[(size_t)i * 2] = r.v;
+    a.bary[(size_t)i * 2 + 1] = r.w;
+  }
+  if (sa.inside) sa.inside[i] = in ? 1u : 0u;
+}
+
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).
 // res[0] = mismatches, res[1] = the smallest mismatching pattern.
 __global__ void rcp_audit_kernel(unsigned long long* res) {

@@ -8,6 +8,7 @@
 #include "ezrt_path.h"
 #include "ezrt_multihit.h"
 #include "ezrt_closest_point.h"
+#include "ezrt_inside.h"
 #include "ezrt_nearest.h"
 #include "ezrt_kernels.h"
 #include "ezrt_wavefront.h"
@@ -1633,6 +1634,71 @@ int ezrt_closest_point_at_device(EzrtScene* s, const float* points3, const int32
                           {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(closest_point_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, point, dist,
                          bary);
+    });
+  });
+}
+
+// ---- inside and signed-distance queries on device memory (include/ezrt_inside.h): one kernel each on `st`, no scratch; checked,
+// launched and ordered against a refit by shade_call.  The route is chosen per call, by ezrt_query_closest_point_device's condition.
+int ezrt_query_inside_device(EzrtScene* s, const float* points3, int n, int axis, uint8_t* inside, int32_t* crossings, void* stream) {
+  return ezi::guarded("ezrt_query_inside_device", [&]() -> int {
+    if (!s || !points3 || !inside || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {inside, N}, {crossings, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      InsideArgs a;
+      a.tri_geom = s->tri_geom.p;
+      a.inner4 = s->inner4.p;
+      a.uncovered = s->cp_uncovered.p;
+      a.n_uncovered = s->n_cp_uncovered;
+      a.n_tri = s->n_tri;
+      a.points = points3;
+      a.n = (uint32_t)n;
+      a.axis = axis;
+      a.inside = inside;
+      a.crossings = crossings;
+      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+      // the closest-point condition (its stack column must fit the 64 KiB of a launch without opt-in); this walk's entries are bare
+      // references, one row each: half of that column
+      const size_t lds_cp = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+      if (s->prunable && s->n_inner4 > 0 && lds_cp <= 64 * 1024) hipLaunchKernelGGL(inside_kernel<true>, g, b, lds_cp / 2, st, a);
+      else hipLaunchKernelGGL(inside_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const float* d_max, int n, int axis, int32_t* tri_id,
+                                      float* point, float* sdist, float* bary, uint8_t* inside, void* stream) {
+  return ezi::guarded("ezrt_query_signed_distance_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
+                          {point, N * 3 * sizeof(float)}, {sdist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}, {inside, N}}, N, st,
+                      [&](dim3, dim3) {
+      SignedDistanceArgs a;
+      a.cp.tri_geom = s->tri_geom.p;
+      a.cp.inner4 = s->inner4.p;
+      a.cp.uncovered = s->cp_uncovered.p;
+      a.cp.n_uncovered = s->n_cp_uncovered;
+      a.cp.n_tri = s->n_tri;
+      a.cp.points = points3;
+      a.cp.d_max = d_max;
+      a.cp.n = (uint32_t)n;
+      a.cp.tri = tri_id;
+      a.cp.point = point;
+      a.cp.dist = sdist;
+      a.cp.bary = bary;
+      a.axis = axis;
+      a.inside = inside;
+      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+      // closest_point_kernel's stack column and condition; the crossing walk runs first on the same column
+      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) hipLaunchKernelGGL(signed_distance_kernel<true>, g, b, lds, st, a);
+      else hipLaunchKernelGGL(signed_distance_kernel<false>, g, b, 0, st, a);
     });
   });
 }

@@ -1,5 +1,5 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
-include/ezrt_closest_point.h, include/ezrt_nearest.h).
+include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -10,12 +10,17 @@ include/ezrt_closest_point.h, include/ezrt_nearest.h).
     tri, point, dist, bary = query.closest_point(scene, points)  # the nearest triangle, point and distance (include/ezrt_closest_point.h)
     tri, dist, count = query.nearest(scene, points, k, d_max, count=True)   # the k nearest triangles in order, and how many lie within d_max
     tri, point, dist, bary = query.closest_point_at(scene, points, tri)     # ... their nearest points and barycentrics (include/ezrt_nearest.h)
+    inside = query.inside(scene, points, axis=0)                 # is the point inside the mesh?  (bool; include/ezrt_inside.h)
+    inside, crossings = query.inside(scene, points, axis, crossings=True)   # ... and the number of triangles its axis ray crosses
+    tri, point, dist, bary, inside = query.signed_distance(scene, points)   # closest_point with dist negative inside the mesh
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
 `d_max` (optional) a float32 GPU tensor of shape points.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
 `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the rays' device) and the functions
-return without waiting for it.  There is no t_min: a triangle is accepted at t >= 0.0005 only, so a ray leaving a surface needs its
+return without waiting for it.  `axis` (0..5: +x, -x, +y, -y, +z, -z) is the direction of the ray whose crossings decide `inside`;
+on a closed mesh every axis gives the same answer, on an open one (the Bunny has holes) they may differ: vote over several.
+There is no t_min: a triangle is accepted at t >= 0.0005 only, so a ray leaving a surface needs its
 origin offset by the caller.  A miss is (-1, 114514.0): ezrt_query_hits' miss (the reference's INF).
 """
 import collections
@@ -29,6 +34,7 @@ from . import _abi, trace
 Surface = collections.namedtuple("Surface", "tri t point normal inside")
 ClosestPoint = collections.namedtuple("ClosestPoint", "tri point dist bary")
 Nearest = collections.namedtuple("Nearest", "tri dist count")
+SignedDistance = collections.namedtuple("SignedDistance", "tri point dist bary inside")
 
 
 def _scene_lib(scene, abi):
@@ -347,3 +353,55 @@ def closest_point_at(scene, points, tri, stream=None):
                                                   P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
     _keep((points, per_entry, tri, point, dist, bary), ts, points)
     return ClosestPoint(tri, point, dist, bary)
+
+
+def _check_axis(axis):
+    if not isinstance(axis, int) or isinstance(axis, bool) or not 0 <= axis <= 5:
+        raise ValueError("axis must be an int in [0, 5] (+x, -x, +y, -y, +z, -z), not %r" % (axis,))
+
+
+def inside(scene, points, axis=0, crossings=False, stream=None):
+    """bool [...]: whether each point of `points` (a contiguous float32 GPU tensor [..., 3]) is inside the mesh -- the parity of the
+    number of triangles crossed by the ray that leaves the point along `axis` (0..5: +x, -x, +y, -y, +z, -z), by a rule that is
+    consistent on shared edges and vertices and independent of the tree, of the order of the triangles and of their windings.
+    `crossings=True` returns (inside, crossings int32 [...]).  A point with a non-finite coordinate crosses nothing.  On an open mesh
+    the answer is still that parity and may differ between axes: vote over several.  The definition, on the bits:
+    include/ezrt_inside.h."""
+    _check_axis(axis)
+    n = _check_points(points, None)
+    lib = _scene_lib(scene, _abi.INSIDE_ABI)
+    lead = tuple(points.shape[:-1])
+    out = torch.empty(lead, dtype=torch.uint8, device=points.device)
+    count = torch.empty(lead, dtype=torch.int32, device=points.device) if crossings else None
+    if n > 0:
+        h, ts = _stream(points, stream)
+        P = C.c_void_p
+        _call(scene, lib.ezrt_query_inside_device(scene._h, P(points.data_ptr()), n, axis, P(out.data_ptr()),
+                                                  P(count.data_ptr()) if crossings else None, P(h)))
+        _keep((points, out, count), ts, points)
+    return (out.view(torch.bool), count) if crossings else out.view(torch.bool)
+
+
+def signed_distance(scene, points, d_max=None, axis=0, stream=None):
+    """SignedDistance(tri int32 [...], point float32 [..., 3], dist float32 [...], bary float32 [..., 2], inside bool [...]):
+    `closest_point`'s tri, point and bary on the bits, its dist with the sign bit set where the point is inside the mesh (`inside`'s
+    answer for `axis`), in one launch.  A miss (no triangle within `d_max`) is +inf outside and -inf inside.  The definition, on the
+    bits: include/ezrt_inside.h."""
+    _check_axis(axis)
+    n = _check_points(points, d_max)
+    lib = _scene_lib(scene, _abi.INSIDE_ABI)
+    lead = tuple(points.shape[:-1])
+    tri = torch.empty(lead, dtype=torch.int32, device=points.device)
+    point = torch.empty(lead + (3,), dtype=torch.float32, device=points.device)
+    dist = torch.empty(lead, dtype=torch.float32, device=points.device)
+    bary = torch.empty(lead + (2,), dtype=torch.float32, device=points.device)
+    ins = torch.empty(lead, dtype=torch.uint8, device=points.device)
+    if n == 0:
+        return SignedDistance(tri, point, dist, bary, ins.view(torch.bool))
+    h, ts = _stream(points, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_signed_distance_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None,
+                                                       n, axis, P(tri.data_ptr()), P(point.data_ptr()), P(dist.data_ptr()),
+                                                       P(bary.data_ptr()), P(ins.data_ptr()), P(h)))
+    _keep((points, d_max, tri, point, dist, bary, ins), ts, points)
+    return SignedDistance(tri, point, dist, bary, ins.view(torch.bool))
