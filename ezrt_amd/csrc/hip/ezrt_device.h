@@ -357,7 +357,7 @@ EZD void closest_point_candidate(ClosestBest& r, const float4* __restrict__ tri_
   }
 }
 // lb of a box: dot(g, g), g = max(lo - p, 0, p - hi) per axis (fmaxf: a NaN difference counts as 0).  For a finite p and a box that
-// holds the bounding box of a triangle, lb <= that triangle's dist2 on the bits (ezrt_kernels.h: closest_point_kernel).
+// holds the bounding box of a triangle, lb <= that triangle's dist2 on the bits (ezrt_point_queries.h: point_walk).
 EZD float closest_point_box(f3 p, f3 lo, f3 hi) {
   const f3 g = mk(__builtin_fmaxf(__builtin_fmaxf(lo.x - p.x, 0.0f), p.x - hi.x), __builtin_fmaxf(__builtin_fmaxf(lo.y - p.y, 0.0f), p.y - hi.y),
                   __builtin_fmaxf(__builtin_fmaxf(lo.z - p.z, 0.0f), p.z - hi.z));
@@ -516,6 +516,7 @@ struct Hit {
 };
 
 EZD f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
+EZD void st3(float* p, f3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
 
 __host__ __device__ inline void mat_derive(Mat& m) {
   const float Cdlum = 0.3f * m.baseColor.x + 0.6f * m.baseColor.y + 0.1f * m.baseColor.z;

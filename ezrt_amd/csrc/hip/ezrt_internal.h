@@ -386,7 +386,7 @@ struct EzrtScene {
   DevBuf<float4> inner4;      // 4-wide records (ezrt_traceq4.h), breadth-first; empty when the boxes are not nested
   int n_inner4 = 0;
   int stack_need4 = 1;        // LDS stack rows the 4-wide traversal can need (exact worst case over hit patterns)
-  int stack_need_cp = 1;      // entries the best-first walk of closest_point_kernel can have pending (topology only: a refit keeps it)
+  int stack_need_cp = 1;      // entries the best-first walk of the point queries (ezrt_point_queries.h: point_walk) can have pending (topology only: a refit keeps it)
   DevBuf<int32_t> cp_uncovered; // triangles no leaf of the 4-wide records holds (closest-point queries sweep them); usually empty
   int n_cp_uncovered = 0;
   // distance pruning (ezrt_traceq4.h): scene maxima of the per-triangle bound, evaluated in double at create

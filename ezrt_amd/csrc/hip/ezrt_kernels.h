@@ -636,7 +636,6 @@ EZD bool shade_mat_row(const float4* tri_shade, const float4* mat_table, int32_t
   for (int k = 0; k < MAT_REC_FLOAT4; k++) m[k] = k < ROWS ? mq[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   return true;
 }
-EZD void st3(float* p, f3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
 
 // ezrt_query_material_device: the 18 floats the row starts with (texels 0-4; mat_pack_row)
 __global__ __launch_bounds__(256) void shade_material_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
@@ -934,532 +933,6 @@ __global__ __launch_bounds__(256) void surface_at_kernel(const float4* tri_geom,
   if (point) st3(point + (size_t)i * 3, P);
   if (normal) st3(normal + (size_t)i * 3, N);
   if (inside) inside[i] = in ? 1u : 0u;
-}
-
-// ---- closest-point queries (include/ezrt_closest_point.h): one query point per lane.
-//
-// WALK = true, the pruned route (the scene prunes: boxes nested, every leaf box holds its triangles).  A best-first walk over the
-// 4-WIDE records (ezrt_records.h) -- chosen over the binary records because one 128-byte line gives four boxes, so a point needs
-// half the dependent loads on its way down, and because their boxes qualify: a slot's box is a caller's node box (nested, its
-// leaves hold their triangles) or an exact union of caller leaf boxes (retree_leaves, and every box after a refit), i.e. a
-// superset of the bounding box of every triangle below it.  The four slots are sorted by lb (closest_point_box), the walk goes on
-// with the nearest and pushes the others, farthest first, as {lb, ref} pairs on the lane's LDS stack column (two rows per entry;
-// launched with 2 * stack_need_cp rows: the exact worst case when any slot may be the nearest).  A slot is skipped only when
-// lb > best -- on equality it is descended: the tie rule needs every triangle at the minimum -- or when lb is not finite (no finite
-// dist2 below it); a popped entry is checked against the best of that moment again.
-// Why no margin is needed: for a triangle T below a box [lo, hi], q_T is clamped to T's bounding box, which lies in [lo, hi].  Per
-// axis either g = 0 <= |e|, or g = fl(lo - p) with q >= lo > p: q - p >= lo - p in the reals, rounding is monotone and
-// |fl(p - q)| = fl(q - p), so |e| >= g (the same on the hi side).  fl(x * x) is monotone in |x| and fl(fl(X + Y) + Z) in each of
-// X, Y, Z >= 0, so lb = dot(g, g) <= dot(e, e) = dist2_T ON THE BITS, overflow to +inf included.  Hence a skipped subtree holds no
-// triangle with dist2 <= best: neither a winner nor a tie is lost, and the order of the visits does not matter to
-// closest_point_candidate.  Triangles that no leaf holds (a caller's array may have some) are swept after the walk.
-// WALK = false, the sweep route: closest_point_candidate over tri_geom[0 .. n_tri), no tree, for scenes that do not prune.
-// A non-finite p misses at once: every dist2 is then inf or NaN.
-struct ClosestPointArgs {
-  const float4* tri_geom;
-  const float4* inner4;     // WALK: the 4-wide records, record 0 the root
-  const int32_t* uncovered; // WALK: triangles below no leaf
-  int32_t n_uncovered;
-  int32_t n_tri;
-  const float* points;      // n x 3
-  const float* d_max;       // n, or null
-  uint32_t n;
-  int32_t* tri;             // n
-  float* point;             // n x 3, or null
-  float* dist;              // n, or null
-  float* bary;              // n x 2, or null
-};
-constexpr int CP_BLOCK = 64; // one wave per workgroup: the stack column is 2 x 4 B per entry, and LDS is what bounds the occupancy
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void closest_point_kernel(ClosestPointArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
-  if (i >= a.n) return;
-  const f3 p = ld3(a.points + (size_t)i * 3);
-  const float inf = __builtin_inff();
-  ClosestBest r;
-  r.best = inf;
-  r.tri = -1;
-  r.v = r.w = 0.0f;
-  r.q = mk(0.0f, 0.0f, 0.0f);
-  bool live = ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf;
-  if (a.d_max) {
-    const float dm = a.d_max[i];
-    if (dm >= 0.0f) r.best = dm * dm;
-    else live = false; // negative or NaN: no candidates
-  }
-  if (live && WALK) {
-    int* stack = lds_stack + threadIdx.x;
-    int sp = 0;
-    uint32_t ref = 0u;
-    for (;;) {
-      bool descend = false;
-      if (ref & LEAF_BIT) {
-        const int first = (int)(ref & 0x00ffffffu);
-        const int n = (int)((ref >> 24) & 0x7fu) + 1;
-        for (int k = first; k < first + n; k++) closest_point_candidate(r, a.tri_geom, k, p);
-      } else {
-        const float4* rec = a.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
-        const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
-        const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
-        uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-        // (an unused slot -- an all-NaN box -- gets lb = inf: never descended)
-        float l0 = r0 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x));
-        float l1 = r1 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y));
-        float l2 = r2 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z));
-        float l3 = r3 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w));
-        auto cswap = [](float& la, uint32_t& ra, float& lb, uint32_t& rb) {
-          if (lb < la) {
-            const float tl = la;
-            la = lb, lb = tl;
-            const uint32_t tr = ra;
-            ra = rb, rb = tr;
-          }
-        };
-        cswap(l0, r0, l1, r1);
-        cswap(l2, r2, l3, r3);
-        cswap(l0, r0, l2, r2);
-        cswap(l1, r1, l3, r3);
-        cswap(l1, r1, l2, r2);
-        // ascending now: the slots worth a visit are a prefix
-        if (l3 <= r.best && l3 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l3);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r3;
-          sp++;
-        }
-        if (l2 <= r.best && l2 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l2);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r2;
-          sp++;
-        }
-        if (l1 <= r.best && l1 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l1);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r1;
-          sp++;
-        }
-        if (l0 <= r.best && l0 < inf) {
-          ref = r0;
-          descend = true;
-        }
-      }
-      if (descend) continue;
-      while (sp > 0) {
-        sp--;
-        if (__uint_as_float((uint32_t)stack[(2 * sp) * CP_BLOCK]) <= r.best) { // checked again: best may have shrunk since the push
-          ref = (uint32_t)stack[(2 * sp + 1) * CP_BLOCK];
-          descend = true;
-          break;
-        }
-      }
-      if (!descend) break;
-    }
-    for (int u = 0; u < a.n_uncovered; u++) closest_point_candidate(r, a.tri_geom, a.uncovered[u], p);
-  }
-  if (live && !WALK)
-    for (int k = 0; k < a.n_tri; k++) closest_point_candidate(r, a.tri_geom, k, p);
-  a.tri[i] = r.tri;
-  if (a.point) st3(a.point + (size_t)i * 3, r.q);
-  if (a.dist) a.dist[i] = r.tri >= 0 ? __builtin_sqrtf(r.best) : inf;
-  if (a.bary) {
-    a.bary[(size_t)i * 2] = r.v;
-    a.bary[(size_t)i * 2 + 1] = r.w;
-  }
-}
-
-// ---- nearest-K queries (include/ezrt_nearest.h): one query point per lane, a workgroup of one wave, closest_point_kernel's walk
-// carrying a K-entry sorted list instead of one winner.
-//
-// The list.  L = the candidates (finite dist2 <= B) sorted by the pair (dist2, k); the first K of them are the answer.  They live in
-// the point's own output rows, as all_hits_kernel's do (K entries in registers would cost the walk its occupancy, 64 x K in LDS do
-// not fit beside the stack): `dist` holds dist2 during the walk, `nb` entries are filled, and once the row is full `last` /
-// `last_id` hold the pair of entry K - 1.  A candidate that does not precede that pair is counted and touches no memory.  An
-// insertion shifts the entries whose PAIR is greater up one slot (the K-th falls out): the tree meets triangles in no id order, so
-// -- unlike all-hits, where arrival order is the rule -- equal dist2 are ordered by id explicitly.  The list after any sequence of
-// insertions is the first min(K, seen) pairs of what was seen, so the order of the visits does not matter.
-// Pruning, without slack (closest_point_kernel's proof: lb <= dist2 ON THE BITS for every triangle below a box).  A slot is skipped
-// only when lb > radius or lb is not finite, descended on equality, and a popped entry is checked against the radius of that moment.
-//   COUNT = false: radius = B until the row is full, then the dist2 of entry K - 1 (`last`, which starts as B).  A skipped subtree
-//     holds only triangles with dist2 > radius >= last: they precede no entry of the row -- at equal dist2 a lower id would, hence
-//     the descent on equality.
-//   COUNT = true (n_within is wanted): radius = B throughout -- every triangle within d_max must be counted, so the walk cannot
-//     shrink below B, and with d_max == NULL it visits every triangle.
-// The stack.  The walk is closest_point_kernel's: per record the slots are sorted, at most three are pushed and the nearest is
-// descended; a pop only removes.  So below a record with m slots at most m - 1 entries of it are pending while one child subtree is
-// walked -- stack_need_cp = the fold of (m - 1 + deepest child) -- whatever the radius admits: a wider radius pushes more of the
-// m - 1, never more than them.  Launched with the same 2 * (stack_need_cp + 1) rows.
-// WALK = false, the sweep route: every triangle of tri_geom[0 .. n_tri), no tree, for scenes that do not prune.
-// Afterwards each wave finishes its 64 rows together, consecutive lanes on consecutive words: a filled slot gets sqrtf(dist2), an
-// unused one {-1, +inf}.  Lanes past n take part with nb = 0 and nothing is written past row n - 1.
-struct NearestArgs {
-  const float4* tri_geom;
-  const float4* inner4;     // WALK: the 4-wide records, record 0 the root
-  const int32_t* uncovered; // WALK: triangles below no leaf
-  int32_t n_uncovered;
-  int32_t n_tri;
-  const float* points;      // n x 3
-  const float* d_max;       // n, or null
-  uint32_t n;
-  int32_t K;
-  FastDiv div_k;            // / K (the finishing pass)
-  int32_t* tri;             // n x K
-  float* dist;              // n x K (dist2 during the walk)
-  int32_t* n_within;        // n, or null (COUNT = false)
-};
-template <bool WALK, bool COUNT>
-__global__ __launch_bounds__(CP_BLOCK) void nearest_kernel(NearestArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t i = blockIdx.x * CP_BLOCK + lane;
-  const int K = a.K;
-  const float inf = __builtin_inff();
-  int nb = 0;
-  if (i < a.n) {
-    const f3 p = ld3(a.points + (size_t)i * 3);
-    float B = inf;
-    bool live = ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf;
-    if (a.d_max) {
-      const float dm = a.d_max[i];
-      if (dm >= 0.0f) B = dm * dm;
-      else live = false; // negative or NaN: no candidates
-    }
-    int32_t* ri = a.tri + (size_t)i * K;
-    float* rd = a.dist + (size_t)i * K;
-    uint32_t count = 0;
-    float last = B; // the dist2 of entry K - 1 once the row is full (a put to slot K - 1 happens only then); B before
-    int32_t last_id = -1;
-    auto put = [&](int j, int32_t id, float d2) {
-      ri[j] = id;
-      rd[j] = d2;
-      if (j == K - 1) last = d2, last_id = id;
-    };
-    auto candidate = [&](int32_t k) {
-      f3 q;
-      float v, w;
-      const float d2 = closest_point_triangle(a.tri_geom + (size_t)k * 3, p, q, v, w);
-      if (!(d2 < inf && d2 <= B)) return; // (false for a NaN d2)
-      count++;
-      if (nb == K && !(d2 < last || (d2 == last && k < last_id))) return; // behind a full row: counted only
-      int j = nb < K ? nb++ : K - 1;
-      while (j > 0) {
-        const float dp = rd[j - 1];
-        const int32_t ip = ri[j - 1];
-        if (!(dp > d2 || (dp == d2 && ip > k))) break;
-        put(j, ip, dp);
-        j--;
-      }
-      put(j, k, d2);
-    };
-    if (live && WALK) {
-      int* stack = lds_stack + lane;
-      int sp = 0;
-      uint32_t ref = 0u;
-      for (;;) {
-        bool descend = false;
-        if (ref & LEAF_BIT) {
-          const int first = (int)(ref & 0x00ffffffu);
-          const int n = (int)((ref >> 24) & 0x7fu) + 1;
-          for (int k = first; k < first + n; k++) candidate(k);
-        } else {
-          const float4* rec = a.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
-          const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
-          const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
-          uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-          // (an unused slot -- an all-NaN box -- gets lb = inf: never descended)
-          float l0 = r0 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x));
-          float l1 = r1 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y));
-          float l2 = r2 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z));
-          float l3 = r3 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w));
-          auto cswap = [](float& la, uint32_t& ra, float& lb, uint32_t& rb) {
-            if (lb < la) {
-              const float tl = la;
-              la = lb, lb = tl;
-              const uint32_t tr = ra;
-              ra = rb, rb = tr;
-            }
-          };
-          cswap(l0, r0, l1, r1);
-          cswap(l2, r2, l3, r3);
-          cswap(l0, r0, l2, r2);
-          cswap(l1, r1, l3, r3);
-          cswap(l1, r1, l2, r2);
-          // ascending now: the slots worth a visit are a prefix
-          const float radius = COUNT ? B : last;
-          if (l3 <= radius && l3 < inf) {
-            stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l3);
-            stack[(2 * sp + 1) * CP_BLOCK] = (int)r3;
-            sp++;
-          }
-          if (l2 <= radius && l2 < inf) {
-            stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l2);
-            stack[(2 * sp + 1) * CP_BLOCK] = (int)r2;
-            sp++;
-          }
-          if (l1 <= radius && l1 < inf) {
-            stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l1);
-            stack[(2 * sp + 1) * CP_BLOCK] = (int)r1;
-            sp++;
-          }
-          if (l0 <= radius && l0 < inf) {
-            ref = r0;
-            descend = true;
-          }
-        }
-        if (descend) continue;
-        while (sp > 0) {
-          sp--;
-          // checked again: the radius may have shrunk since the push (COUNT: it has not, the entry is taken)
-          if (COUNT || __uint_as_float((uint32_t)stack[(2 * sp) * CP_BLOCK]) <= last) {
-            ref = (uint32_t)stack[(2 * sp + 1) * CP_BLOCK];
-            descend = true;
-            break;
-          }
-        }
-        if (!descend) break;
-      }
-      for (int u = 0; u < a.n_uncovered; u++) candidate(a.uncovered[u]);
-    }
-    if (live && !WALK)
-      for (int k = 0; k < a.n_tri; k++) candidate(k);
-    if (COUNT) a.n_within[i] = (int32_t)count;
-  }
-  // the wave's 64 rows, one flat run of 64 K words from its first row; the rows were written by other lanes of this wave, whose
-  // accesses are performed in program order (the fence states it to the compiler and costs nothing at this scope)
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  const size_t base = (size_t)(i - lane) * K;
-  for (uint32_t e = lane; e < 64u * (uint32_t)K; e += 64u) {
-    const uint32_t row = fastdiv(e, a.div_k);
-    const uint32_t slot = e - row * (uint32_t)K;
-    const int used = __shfl(nb, (int)row);
-    if (i - lane + row < a.n) {
-      if (slot < (uint32_t)used) {
-        a.dist[base + e] = __builtin_sqrtf(a.dist[base + e]);
-      } else {
-        a.tri[base + e] = -1;
-        a.dist[base + e] = inf;
-      }
-    }
-  }
-}
-
-// ezrt_closest_point_at_device: closest_point_triangle for pairs the caller holds -- point i against triangle tri_id[i].  An id
-// outside the scene or a non-finite dist2 writes (zeros, +inf, zeros); point / dist / bary may each be null (not written).
-__global__ __launch_bounds__(256) void closest_point_at_kernel(const float4* tri_geom, int32_t n_tri, const float* points,
-                                                               const int32_t* tri_id, uint32_t n, float* point, float* dist,
-                                                               float* bary) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int32_t tri = tri_id[i];
-  f3 Q = mk(0.0f, 0.0f, 0.0f);
-  float D = __builtin_inff(), V = 0.0f, W = 0.0f;
-  if ((uint32_t)tri < (uint32_t)n_tri) {
-    f3 q;
-    float v, w;
-    const float d2 = closest_point_triangle(tri_geom + (size_t)tri * 3, ld3(points + (size_t)i * 3), q, v, w);
-    if (d2 < __builtin_inff()) Q = q, D = __builtin_sqrtf(d2), V = v, W = w; // (false for a NaN d2)
-  }
-  if (point) st3(point + (size_t)i * 3, Q);
-  if (dist) dist[i] = D;
-  if (bary) {
-    bary[(size_t)i * 2] = V;
-    bary[(size_t)i * 2 + 1] = W;
-  }
-}
-
-// ---- inside and signed-distance queries (include/ezrt_inside.h): one query point per lane, a workgroup of one wave.
-//
-// inside_count<WALK> returns crossings(p): the number of triangles with inside_crossed (ezrt_device.h: G1 .. G6 of the header).
-// WALK = true, the pruned route: a depth-first walk over the 4-wide records.  Only the rows of the record that the axis needs are
-// loaded -- lo and hi of s and t, and the far plane of u (hi for a positive axis, lo for a negative one; g * plane > p.u is
-// hi > p or lo < p, exactly) -- and a slot is descended when lo.s <= p.s <= hi.s, lo.t <= p.t <= hi.t and the far plane lies ahead.
-// These are comparisons on the stored fp32 values: G1 - G3 make a crossed triangle's own bounding box pass them, hence every box
-// that holds the triangle (the scene prunes: nested boxes, every leaf box holds its triangles), so no crossed triangle is skipped
-// and no slack is needed.  An unused slot (an all-NaN box) fails every comparison.  The count is an integer sum: the order of the
-// visits does not matter.
-// The stack.  Bare references, one row of 4 B per entry on the lane's LDS column.  Of a record with m slots the first that passes
-// is descended and the others that pass are pushed: at most m - 1 entries; a pop only removes.  So while one child subtree is
-// walked at most m - 1 entries of the record are pending, and the pending entries of any walk are bounded by the fold of
-// (m - 1 + deepest child) over the tree -- which is stack_need_cp (ezrt_scene_build.hip), the bound of every walk that descends
-// one slot and pushes at most three.  Launched with stack_need_cp + 1 rows.
-// Triangles that no leaf holds are swept after the walk.  WALK = false, the sweep route: every triangle, no tree.
-template <bool WALK>
-EZD int32_t inside_count(const float4* __restrict__ tri_geom, const float4* __restrict__ inner4, const int32_t* __restrict__ uncovered,
-                         int32_t n_uncovered, int32_t n_tri, int axis, f3 p, int* __restrict__ stack) {
-  const float inf = __builtin_inff();
-  if (!(ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf)) return 0; // a non-finite p has no crossings
-  const InsideFrame f = inside_frame(axis, p);
-  int32_t count = 0;
-  if (WALK) {
-    const int cs = f.c == 2 ? 0 : f.c + 1, ct = cs == 2 ? 0 : cs + 1;
-    const int row_u = ((axis & 1) ? N4_ROW_AA : N4_ROW_BB) + f.c;
-    int sp = 0;
-    uint32_t ref = 0u;
-    for (;;) {
-      uint32_t next = REF_EMPTY;
-      if (ref & LEAF_BIT) {
-        const int first = (int)(ref & 0x00ffffffu);
-        const int n = (int)((ref >> 24) & 0x7fu) + 1;
-#pragma unroll 1
-        for (int k = first; k < first + n; k++) count += inside_crossed(tri_geom + (size_t)k * 3, f) ? 1 : 0;
-      } else {
-        const float4* rec = inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
-        const float4 ls = rec[N4_ROW_AA + cs], lt = rec[N4_ROW_AA + ct], rf = rec[N4_ROW_REF];
-        const float4 hs = rec[N4_ROW_BB + cs], ht = rec[N4_ROW_BB + ct], fu = rec[row_u];
-        auto take = [&](float lo_s, float hi_s, float lo_t, float hi_t, float far_u, uint32_t r) {
-          if (r != REF_EMPTY && lo_s <= f.ps && f.ps <= hi_s && lo_t <= f.pt && f.pt <= hi_t && f.g * far_u > f.pu) {
-            if (next == REF_EMPTY) next = r;
-            else stack[(sp++) * CP_BLOCK] = (int)r;
-          }
-        };
-        take(ls.x, hs.x, lt.x, ht.x, fu.x, __float_as_uint(rf.x));
-        take(ls.y, hs.y, lt.y, ht.y, fu.y, __float_as_uint(rf.y));
-        take(ls.z, hs.z, lt.z, ht.z, fu.z, __float_as_uint(rf.z));
-        take(ls.w, hs.w, lt.w, ht.w, fu.w, __float_as_uint(rf.w));
-      }
-      if (next == REF_EMPTY) {
-        if (sp == 0) break;
-        next = (uint32_t)stack[(--sp) * CP_BLOCK];
-      }
-      ref = next;
-    }
-#pragma unroll 1
-    for (int u = 0; u < n_uncovered; u++) count += inside_crossed(tri_geom + (size_t)uncovered[u] * 3, f) ? 1 : 0;
-  } else {
-#pragma unroll 1
-    for (int k = 0; k < n_tri; k++) count += inside_crossed(tri_geom + (size_t)k * 3, f) ? 1 : 0;
-  }
-  return count;
-}
-struct InsideArgs {
-  const float4* tri_geom;
-  const float4* inner4;     // WALK: the 4-wide records, record 0 the root
-  const int32_t* uncovered; // WALK: triangles below no leaf
-  int32_t n_uncovered;
-  int32_t n_tri;
-  const float* points;      // n x 3
-  uint32_t n;
-  int32_t axis;             // 0..5
-  uint8_t* inside;          // n
-  int32_t* crossings;       // n, or null
-};
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void inside_kernel(InsideArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
-  if (i >= a.n) return;
-  const f3 p = ld3(a.points + (size_t)i * 3);
-  const int32_t count = inside_count<WALK>(a.tri_geom, a.inner4, a.uncovered, a.n_uncovered, a.n_tri, a.axis, p, lds_stack + threadIdx.x);
-  a.inside[i] = (uint8_t)(count & 1);
-  if (a.crossings) a.crossings[i] = count;
-}
-
-// ezrt_query_signed_distance_device: one launch; each lane runs the crossing walk and then the closest-point walk on the same LDS
-// stack column (launched with closest_point_kernel's 2 * (stack_need_cp + 1) rows: the crossing walk uses the first stack_need_cp of
-// them and leaves nothing pending).  The closest-point part is closest_point_kernel's loop, copied rather than shared so that
-// that kernel compiles as it did; it calls the same closest_point_box / closest_point_candidate, so tri, point and bary are that
-// kernel's on the bits and |sdist| its dist.
-struct SignedDistanceArgs {
-  ClosestPointArgs cp; // (cp.dist is sdist)
-  int32_t axis;        // 0..5
-  uint8_t* inside;     // n, or null
-};
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void signed_distance_kernel(SignedDistanceArgs sa) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const ClosestPointArgs& a = sa.cp;
-  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
-  if (i >= a.n) return;
-  const f3 p = ld3(a.points + (size_t)i * 3);
-  int* stack = lds_stack + threadIdx.x;
-  const bool in = (inside_count<WALK>(a.tri_geom, a.inner4, a.uncovered, a.n_uncovered, a.n_tri, sa.axis, p, stack) & 1) != 0;
-  const float inf = __builtin_inff();
-  ClosestBest r;
-  r.best = inf;
-  r.tri = -1;
-  r.v = r.w = 0.0f;
-  r.q = mk(0.0f, 0.0f, 0.0f);
-  bool live = ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf;
-  if (a.d_max) {
-    const float dm = a.d_max[i];
-    if (dm >= 0.0f) r.best = dm * dm;
-    else live = false; // negative or NaN: no candidates
-  }
-  if (live && WALK) {
-    int sp = 0;
-    uint32_t ref = 0u;
-    for (;;) {
-      bool descend = false;
-      if (ref & LEAF_BIT) {
-        const int first = (int)(ref & 0x00ffffffu);
-        const int n = (int)((ref >> 24) & 0x7fu) + 1;
-        for (int k = first; k < first + n; k++) closest_point_candidate(r, a.tri_geom, k, p);
-      } else {
-        const float4* rec = a.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
-        const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
-        const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
-        uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-        float l0 = r0 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x));
-        float l1 = r1 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y));
-        float l2 = r2 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z));
-        float l3 = r3 == REF_EMPTY ? inf : closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w));
-        auto cswap = [](float& la, uint32_t& ra, float& lb, uint32_t& rb) {
-          if (lb < la) {
-            const float tl = la;
-            la = lb, lb = tl;
-            const uint32_t tr = ra;
-            ra = rb, rb = tr;
-          }
-        };
-        cswap(l0, r0, l1, r1);
-        cswap(l2, r2, l3, r3);
-        cswap(l0, r0, l2, r2);
-        cswap(l1, r1, l3, r3);
-        cswap(l1, r1, l2, r2);
-        if (l3 <= r.best && l3 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l3);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r3;
-          sp++;
-        }
-        if (l2 <= r.best && l2 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l2);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r2;
-          sp++;
-        }
-        if (l1 <= r.best && l1 < inf) {
-          stack[(2 * sp) * CP_BLOCK] = (int)__float_as_uint(l1);
-          stack[(2 * sp + 1) * CP_BLOCK] = (int)r1;
-          sp++;
-        }
-        if (l0 <= r.best && l0 < inf) {
-          ref = r0;
-          descend = true;
-        }
-      }
-      if (descend) continue;
-      while (sp > 0) {
-        sp--;
-        if (__uint_as_float((uint32_t)stack[(2 * sp) * CP_BLOCK]) <= r.best) {
-          ref = (uint32_t)stack[(2 * sp + 1) * CP_BLOCK];
-          descend = true;
-          break;
-        }
-      }
-      if (!descend) break;
-    }
-    for (int u = 0; u < a.n_uncovered; u++) closest_point_candidate(r, a.tri_geom, a.uncovered[u], p);
-  }
-  if (live && !WALK)
-    for (int k = 0; k < a.n_tri; k++) closest_point_candidate(r, a.tri_geom, k, p);
-  a.tri[i] = r.tri;
-  if (a.point) st3(a.point + (size_t)i * 3, r.q);
-  if (a.dist) {
-    const float d = r.tri >= 0 ? __builtin_sqrtf(r.best) : inf;
-    a.dist[i] = __uint_as_float(__float_as_uint(d) | (in ? 0x80000000u : 0u)); // the sign bit: |sdist| is dist on the bits
-  }
-  if (a.bary) {
-    a.bary[(size_t)i * 2] = r.v;
-    a.bary[(size_t)i * 2 + 1] = r.w;
-  }
-  if (sa.inside) sa.inside[i] = in ? 1u : 0u;
 }
 
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).

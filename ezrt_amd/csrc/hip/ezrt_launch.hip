@@ -11,6 +11,7 @@
 #include "ezrt_inside.h"
 #include "ezrt_nearest.h"
 #include "ezrt_kernels.h"
+#include "ezrt_point_queries.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
 
@@ -1547,8 +1548,26 @@ int ezrt_surface_at_device(EzrtScene* s, const float* rays_od6, const int32_t* t
   });
 }
 
+// ---- point queries on device memory: what their kernels read of the scene, and the route of this call -- chosen per call: a refit
+// can change whether the scene prunes.  lds = the lane's stack column of the best-first walk (ezrt_point_queries.h: point_walk):
+// {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that the column exceeds the 64 KiB of a launch without opt-in
+// (> 126 entries; none of the builders comes near) is swept instead, as is a scene that does not prune.
+struct PointRoute {
+  bool walk;
+  size_t lds;
+};
+static PointRoute point_scene(const EzrtScene* s, PointScene& sc) {
+  sc.tri_geom = s->tri_geom.p;
+  sc.inner4 = s->inner4.p;
+  sc.uncovered = s->cp_uncovered.p;
+  sc.n_uncovered = s->n_cp_uncovered;
+  sc.n_tri = s->n_tri;
+  const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+  return {s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024, lds};
+}
+
 // ---- closest-point queries on device memory (include/ezrt_closest_point.h): one kernel on `st`, no scratch; checked, launched and
-// ordered against a refit by shade_call.  The route is chosen per call: a refit can change whether the scene prunes.
+// ordered against a refit by shade_call.
 int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const float* d_max, int n, int32_t* tri_id, float* point,
                                     float* dist, float* bary, void* stream) {
   return ezi::guarded("ezrt_query_closest_point_device", [&]() -> int {
@@ -1559,11 +1578,7 @@ int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const fl
     return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
                           {point, N * 3 * sizeof(float)}, {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3, dim3) {
       ClosestPointArgs a;
-      a.tri_geom = s->tri_geom.p;
-      a.inner4 = s->inner4.p;
-      a.uncovered = s->cp_uncovered.p;
-      a.n_uncovered = s->n_cp_uncovered;
-      a.n_tri = s->n_tri;
+      const PointRoute r = point_scene(s, a.sc);
       a.points = points3;
       a.d_max = d_max;
       a.n = (uint32_t)n;
@@ -1572,18 +1587,15 @@ int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const fl
       a.dist = dist;
       a.bary = bary;
       const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // the lane's stack column: {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that it exceeds the 64 KiB of a
-      // launch without opt-in (> 126 entries; none of the builders comes near) is swept instead
-      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
-      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) hipLaunchKernelGGL(closest_point_kernel<true>, g, b, lds, st, a);
+      if (r.walk) hipLaunchKernelGGL(closest_point_kernel<true>, g, b, r.lds, st, a);
       else hipLaunchKernelGGL(closest_point_kernel<false>, g, b, 0, st, a);
     });
   });
 }
 
 // ---- nearest-K queries on device memory (include/ezrt_nearest.h): one kernel each on `st`, no scratch (a point's sorted list is kept
-// in its own output rows); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by
-// ezrt_query_closest_point_device's condition; n_within selects the counting instance, which cannot shrink its radius below d_max.
+// in its own output rows); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene;
+// n_within selects the counting instance, which cannot shrink its radius below d_max.
 int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d_max, int n, int max_k, int32_t* tri_id, float* dist,
                               int32_t* n_within, void* stream) {
   return ezi::guarded("ezrt_query_nearest_device", [&]() -> int {
@@ -1595,11 +1607,7 @@ int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d
     return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
                           {dist, N * K * sizeof(float)}, {n_within, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
       NearestArgs a;
-      a.tri_geom = s->tri_geom.p;
-      a.inner4 = s->inner4.p;
-      a.uncovered = s->cp_uncovered.p;
-      a.n_uncovered = s->n_cp_uncovered;
-      a.n_tri = s->n_tri;
+      const PointRoute r = point_scene(s, a.sc);
       a.points = points3;
       a.d_max = d_max;
       a.n = (uint32_t)n;
@@ -1609,12 +1617,9 @@ int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d
       a.dist = dist;
       a.n_within = n_within;
       const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // the lane's stack column, as closest_point_kernel's: {lb, ref} per pending entry (+ 1 of slack); a tree needing more than the
-      // 64 KiB of a launch without opt-in is swept instead
-      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
-      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) {
-        if (n_within) hipLaunchKernelGGL((nearest_kernel<true, true>), g, b, lds, st, a);
-        else hipLaunchKernelGGL((nearest_kernel<true, false>), g, b, lds, st, a);
+      if (r.walk) {
+        if (n_within) hipLaunchKernelGGL((nearest_kernel<true, true>), g, b, r.lds, st, a);
+        else hipLaunchKernelGGL((nearest_kernel<true, false>), g, b, r.lds, st, a);
       } else {
         if (n_within) hipLaunchKernelGGL((nearest_kernel<false, true>), g, b, 0, st, a);
         else hipLaunchKernelGGL((nearest_kernel<false, false>), g, b, 0, st, a);
@@ -1639,7 +1644,7 @@ int ezrt_closest_point_at_device(EzrtScene* s, const float* points3, const int32
 }
 
 // ---- inside and signed-distance queries on device memory (include/ezrt_inside.h): one kernel each on `st`, no scratch; checked,
-// launched and ordered against a refit by shade_call.  The route is chosen per call, by ezrt_query_closest_point_device's condition.
+// launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene.
 int ezrt_query_inside_device(EzrtScene* s, const float* points3, int n, int axis, uint8_t* inside, int32_t* crossings, void* stream) {
   return ezi::guarded("ezrt_query_inside_device", [&]() -> int {
     if (!s || !points3 || !inside || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
@@ -1649,21 +1654,15 @@ int ezrt_query_inside_device(EzrtScene* s, const float* points3, int n, int axis
     hipStream_t st = (hipStream_t)stream;
     return shade_call(s, {{points3, N * 3 * sizeof(float)}, {inside, N}, {crossings, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
       InsideArgs a;
-      a.tri_geom = s->tri_geom.p;
-      a.inner4 = s->inner4.p;
-      a.uncovered = s->cp_uncovered.p;
-      a.n_uncovered = s->n_cp_uncovered;
-      a.n_tri = s->n_tri;
+      const PointRoute r = point_scene(s, a.sc);
       a.points = points3;
       a.n = (uint32_t)n;
       a.axis = axis;
       a.inside = inside;
       a.crossings = crossings;
       const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // the closest-point condition (its stack column must fit the 64 KiB of a launch without opt-in); this walk's entries are bare
-      // references, one row each: half of that column
-      const size_t lds_cp = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
-      if (s->prunable && s->n_inner4 > 0 && lds_cp <= 64 * 1024) hipLaunchKernelGGL(inside_kernel<true>, g, b, lds_cp / 2, st, a);
+      // this walk's entries are bare references, one row each: half of the column that decides the route
+      if (r.walk) hipLaunchKernelGGL(inside_kernel<true>, g, b, r.lds / 2, st, a);
       else hipLaunchKernelGGL(inside_kernel<false>, g, b, 0, st, a);
     });
   });
@@ -1680,11 +1679,7 @@ int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const 
                           {point, N * 3 * sizeof(float)}, {sdist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}, {inside, N}}, N, st,
                       [&](dim3, dim3) {
       SignedDistanceArgs a;
-      a.cp.tri_geom = s->tri_geom.p;
-      a.cp.inner4 = s->inner4.p;
-      a.cp.uncovered = s->cp_uncovered.p;
-      a.cp.n_uncovered = s->n_cp_uncovered;
-      a.cp.n_tri = s->n_tri;
+      const PointRoute r = point_scene(s, a.cp.sc);
       a.cp.points = points3;
       a.cp.d_max = d_max;
       a.cp.n = (uint32_t)n;
@@ -1695,9 +1690,8 @@ int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const 
       a.axis = axis;
       a.inside = inside;
       const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // closest_point_kernel's stack column and condition; the crossing walk runs first on the same column
-      const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
-      if (s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024) hipLaunchKernelGGL(signed_distance_kernel<true>, g, b, lds, st, a);
+      // the crossing walk runs first, on the same column
+      if (r.walk) hipLaunchKernelGGL(signed_distance_kernel<true>, g, b, r.lds, st, a);
       else hipLaunchKernelGGL(signed_distance_kernel<false>, g, b, 0, st, a);
     });
   });

@@ -379,7 +379,7 @@ static int scene_create_impl(const float* tri, int n_tri, const float* nodes, in
   std::vector<HostNode> hn_kept;                  // the decoded caller nodes, kept for ezrt_scene_refit_device
   bool retreed = false;
   int n_inner4 = 0, stack_need4 = 1;
-  int stack_need_cp = 1; // entries the best-first walk of closest_point_kernel can have pending (any slot may be the nearest)
+  int stack_need_cp = 1; // entries the best-first walk of the point queries (ezrt_point_queries.h: point_walk) can have pending (any slot may be the nearest)
   {
     std::vector<HostNode> hn((size_t)n_nodes);
     for (int i = 1; i < n_nodes; i++) hn[(size_t)i] = decode_node(nodes, i);
