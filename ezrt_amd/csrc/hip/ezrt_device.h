@@ -425,6 +425,81 @@ EZD bool inside_crossed(const float4* __restrict__ tg, const InsideFrame& f) {
   return __builtin_fabs(D) < __builtin_inf() && ((D < 0.0 && A > 0.0) || (D > 0.0 && A < 0.0));                 // G6
 }
 
+// ---- box-overlap queries (include/ezrt_box_overlap.h, where the definition is the contract): H1 .. H3 of one triangle against a
+// LIVE box (the caller has checked the box), in the header's order.  An edge axis has a[j] = 0: its term a[j] * d is a zero (d is
+// finite), and adding a zero changes at most the sign of a zero sum, which no comparison sees -- so those terms are left out and
+// bmin, bmax and t are sums of two products.  Only the live state of one edge is held at a time: the three edges are one loop that
+// is not unrolled, with (A, B, C) moved from one edge to the next between its rounds.
+struct BoxInterval {
+  double mn, mx;
+};
+// t_c of bmin and of bmax for one component: a * d(lo, A) and a * d(hi, A), given to bmin and bmax by the sign of a
+EZD BoxInterval box_term(double a, double dl, double dh) {
+  const double pl = a * dl, ph = a * dh;
+  const bool up = a >= 0.0;
+  return BoxInterval{up ? pl : ph, up ? ph : pl};
+}
+// does e x (box axis j) separate?  (u, w) = ((j + 1) % 3, (j + 2) % 3): a[u] = -e[w], a[w] = e[u]; q = C - A
+EZD bool box_edge_axis_separates(double eu, double ew, double dlu, double dhu, double dlw, double dhw, double qu, double qw) {
+  const double au = -ew, aw = eu;
+  const BoxInterval tu = box_term(au, dlu, dhu), tw = box_term(aw, dlw, dhw);
+  const double bmin = tu.mn + tw.mn, bmax = tu.mx + tw.mx;
+  const double t = au * qu + aw * qw;
+  return bmin > (t > 0.0 ? t : 0.0) || bmax < (t < 0.0 ? t : 0.0);
+}
+// a live box: six finite numbers and lo <= hi on every axis (false for a NaN); a box that is not live overlaps nothing
+EZD bool box_live(f3 lo, f3 hi) {
+  const float inf = __builtin_inff();
+  return ez_abs(lo.x) < inf && ez_abs(lo.y) < inf && ez_abs(lo.z) < inf && ez_abs(hi.x) < inf && ez_abs(hi.y) < inf && ez_abs(hi.z) < inf &&
+         lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z;
+}
+EZD bool box_overlaps(const float4* __restrict__ tg, f3 lo, f3 hi) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  if (!((a.x <= hi.x || b.x <= hi.x || c.x <= hi.x) && (a.x >= lo.x || b.x >= lo.x || c.x >= lo.x))) return false;   // H1
+  if (!((a.y <= hi.y || b.y <= hi.y || c.y <= hi.y) && (a.y >= lo.y || b.y >= lo.y || c.y >= lo.y))) return false;
+  if (!((a.z <= hi.z || b.z <= hi.z || c.z <= hi.z) && (a.z >= lo.z || b.z >= lo.z || c.z >= lo.z))) return false;
+  const float inf = __builtin_inff();
+  if (!(ez_abs(a.x) < inf && ez_abs(a.y) < inf && ez_abs(a.z) < inf && ez_abs(b.x) < inf && ez_abs(b.y) < inf && ez_abs(b.z) < inf &&
+        ez_abs(c.x) < inf && ez_abs(c.y) < inf && ez_abs(c.z) < inf))
+    return false; // a non-finite vertex never overlaps
+  auto cswap = [](f3& x, f3& y) {
+    if (y.x < x.x || (y.x == x.x && (y.y < x.y || (y.y == x.y && y.z < x.z)))) { // less(y, x)
+      const f3 h = x;
+      x = y, y = h;
+    }
+  };
+  cswap(a, b);
+  cswap(b, c);
+  cswap(a, b);
+  // fp64 from here: (v0 v1 v2) = (a b c)
+  {
+    const double e1x = (double)b.x - (double)a.x, e1y = (double)b.y - (double)a.y, e1z = (double)b.z - (double)a.z;
+    const double e2x = (double)c.x - (double)a.x, e2y = (double)c.y - (double)a.y, e2z = (double)c.z - (double)a.z;
+    const double Nx = e1y * e2z - e1z * e2y, Ny = e1z * e2x - e1x * e2z, Nz = e1x * e2y - e1y * e2x;
+    const BoxInterval t0 = box_term(Nx, (double)lo.x - (double)a.x, (double)hi.x - (double)a.x);
+    const BoxInterval t1 = box_term(Ny, (double)lo.y - (double)a.y, (double)hi.y - (double)a.y);
+    const BoxInterval t2 = box_term(Nz, (double)lo.z - (double)a.z, (double)hi.z - (double)a.z);
+    if (!((t0.mn + t1.mn) + t2.mn <= 0.0 && (t0.mx + t1.mx) + t2.mx >= 0.0)) return false;                              // H2
+  }
+  // H3: (A, B; C) = (v0, v1; v2), then (v1, v2; v0), then (v0, v2; v1)
+  f3 A = a, B = b, C = c;
+#pragma unroll 1
+  for (int edge = 0; edge < 3; edge++) {
+    const double ex = (double)B.x - (double)A.x, ey = (double)B.y - (double)A.y, ez = (double)B.z - (double)A.z;
+    const double qx = (double)C.x - (double)A.x, qy = (double)C.y - (double)A.y, qz = (double)C.z - (double)A.z;
+    const double lx = (double)lo.x - (double)A.x, ly = (double)lo.y - (double)A.y, lz = (double)lo.z - (double)A.z;
+    const double hx = (double)hi.x - (double)A.x, hy = (double)hi.y - (double)A.y, hz = (double)hi.z - (double)A.z;
+    if (box_edge_axis_separates(ey, ez, ly, hy, lz, hz, qy, qz)) return false; // j = 0: (u, w) = (y, z)
+    if (box_edge_axis_separates(ez, ex, lz, hz, lx, hx, qz, qx)) return false; // j = 1: (z, x)
+    if (box_edge_axis_separates(ex, ey, lx, hx, ly, hy, qx, qy)) return false; // j = 2: (x, y)
+    const f3 h = A; // (v0, v1; v2) -> (v1, v2; v0): rotate;  (v1, v2; v0) -> (v0, v2; v1): exchange A and C
+    if (edge == 0) A = B, B = C, C = h;
+    else A = C, C = h;
+  }
+  return true;
+}
+
 // hitBVH: P5/fsh:254-306 + hitArray 238-251.  Unpruned, near-first, ties go
 // right-first, strict < keeps the first-found hit -- identical visit order per
 // ray.  The traversal stack lives in LDS: `stack` points at this lane's column

@@ -10,6 +10,7 @@
 #include "ezrt_closest_point.h"
 #include "ezrt_inside.h"
 #include "ezrt_nearest.h"
+#include "ezrt_box_overlap.h"
 #include "ezrt_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_wavefront.h"
@@ -1693,6 +1694,51 @@ int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const 
       // the crossing walk runs first, on the same column
       if (r.walk) hipLaunchKernelGGL(signed_distance_kernel<true>, g, b, r.lds, st, a);
       else hipLaunchKernelGGL(signed_distance_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+
+// ---- box-overlap queries on device memory (include/ezrt_box_overlap.h): one kernel each on `st`, no scratch (a box's list is kept in
+// its own output row); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene.
+int ezrt_query_box_overlap_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, int n, int max_k, int32_t* tri_id,
+                                  int32_t* n_overlap, void* stream) {
+  return ezi::guarded("ezrt_query_box_overlap_device", [&]() -> int {
+    if (!s || !box_lo3 || !box_hi3 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 0 || max_k > EZRT_BOX_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_BOX_OVERLAP_MAX);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      BoxOverlapArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.lo = box_lo3;
+      a.hi = box_hi3;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+      // this walk's entries are bare references, one row each: half of the column that decides the route
+      if (r.walk) hipLaunchKernelGGL(box_overlap_kernel<true>, g, b, r.lds / 2, st, a);
+      else hipLaunchKernelGGL(box_overlap_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, const int32_t* tri_id, int n, uint8_t* overlaps,
+                               void* stream) {
+  return ezi::guarded("ezrt_box_overlap_at_device", [&]() -> int {
+    if (!s || !box_lo3 || !box_hi3 || !tri_id || !overlaps || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return shade_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
+                      st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(box_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, box_lo3, box_hi3, tri_id, (uint32_t)n, overlaps);
     });
   });
 }

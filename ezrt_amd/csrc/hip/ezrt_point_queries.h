@@ -1,12 +1,16 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
-// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h).  One query point per lane, a workgroup of one wave.
+// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap queries
+// (include/ezrt_box_overlap.h).  One query point or box per lane, a workgroup of one wave.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest and signed distance share
 //   closest_point_kernel<WALK>       closest_point_search + closest_point_store
 //   nearest_kernel<WALK, COUNT>      point_walk carrying a K-entry sorted list instead of one winner
 //   closest_point_at_kernel          closest_point_triangle for pairs the caller holds
-//   inside_kernel<WALK>              inside_count: a depth-first walk of its own
+//   slot_walk                        the depth-first walk over the 4-wide records that inside and box overlap share
+//   inside_kernel<WALK>              inside_count: slot_walk on the rows its axis needs
 //   signed_distance_kernel<WALK>     inside_count + closest_point_search + closest_point_store
+//   box_overlap_kernel<WALK>         slot_walk carrying a K-entry list of the lowest ids and a count
+//   box_overlap_at_kernel            box_overlaps for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -283,10 +287,45 @@ __global__ __launch_bounds__(256) void closest_point_at_kernel(const float4* tri
   }
 }
 
+// The depth-first walk over the 4-wide records that inside_count and box_overlap_kernel share (the scene prunes: boxes nested, every
+// leaf box holds its triangles).  slots(rec, take) looks at one record and calls take(pass, ref) for each of its four slots --
+// pass() says whether the slot's box may hold a triangle that counts, and is asked only for a slot in use (a callable, not a bool:
+// with the test evaluated before the call inside_kernel<true> took 100 VGPRs for its 98); visit(k) takes every triangle k below a
+// leaf that is reached.  Of a record
+// the first slot that passes is descended and the others that pass are pushed as bare references, one row of 4 B per entry on the
+// lane's LDS column (stride CP_BLOCK); an unused slot (REF_EMPTY, an all-NaN box) is never taken.  The stack bound is argued above
+// inside_count: stack_need_cp entries, launched with stack_need_cp + 1 rows.
+template <class Slots, class Visit>
+EZD void slot_walk(const float4* __restrict__ inner4, int* __restrict__ stack, Slots slots, Visit visit) {
+  int sp = 0;
+  uint32_t ref = 0u;
+  for (;;) {
+    uint32_t next = REF_EMPTY;
+    if (ref & LEAF_BIT) {
+      const int first = (int)(ref & 0x00ffffffu);
+      const int n = (int)((ref >> 24) & 0x7fu) + 1;
+#pragma unroll 1
+      for (int k = first; k < first + n; k++) visit(k);
+    } else {
+      slots(inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4, [&](auto pass, uint32_t r) {
+        if (r != REF_EMPTY && pass()) {
+          if (next == REF_EMPTY) next = r;
+          else stack[(sp++) * CP_BLOCK] = (int)r;
+        }
+      });
+    }
+    if (next == REF_EMPTY) {
+      if (sp == 0) break;
+      next = (uint32_t)stack[(--sp) * CP_BLOCK];
+    }
+    ref = next;
+  }
+}
+
 // ---- inside and signed-distance queries (include/ezrt_inside.h).
 //
 // inside_count<WALK> returns crossings(p): the number of triangles with inside_crossed (ezrt_device.h: G1 .. G6 of the header).
-// WALK = true, the pruned route: a depth-first walk over the 4-wide records, not point_walk.  Only the rows of the record that the
+// WALK = true, the pruned route: slot_walk, the depth-first walk over the 4-wide records, not point_walk.  Only the rows of the record that the
 // axis needs are loaded -- lo and hi of s and t, and the far plane of u (hi for a positive axis, lo for a negative one;
 // g * plane > p.u is hi > p or lo < p, exactly) -- and a slot is descended when lo.s <= p.s <= hi.s, lo.t <= p.t <= hi.t and the far
 // plane lies ahead.  These are comparisons on the stored fp32 values: G1 - G3 make a crossed triangle's own bounding box pass them,
@@ -308,36 +347,20 @@ EZD int32_t inside_count(const PointScene& sc, int axis, f3 p, int* __restrict__
   if (WALK) {
     const int cs = f.c == 2 ? 0 : f.c + 1, ct = cs == 2 ? 0 : cs + 1;
     const int row_u = ((axis & 1) ? N4_ROW_AA : N4_ROW_BB) + f.c;
-    int sp = 0;
-    uint32_t ref = 0u;
-    for (;;) {
-      uint32_t next = REF_EMPTY;
-      if (ref & LEAF_BIT) {
-        const int first = (int)(ref & 0x00ffffffu);
-        const int n = (int)((ref >> 24) & 0x7fu) + 1;
-#pragma unroll 1
-        for (int k = first; k < first + n; k++) count += inside_crossed(sc.tri_geom + (size_t)k * 3, f) ? 1 : 0;
-      } else {
-        const float4* rec = sc.inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
-        const float4 ls = rec[N4_ROW_AA + cs], lt = rec[N4_ROW_AA + ct], rf = rec[N4_ROW_REF];
-        const float4 hs = rec[N4_ROW_BB + cs], ht = rec[N4_ROW_BB + ct], fu = rec[row_u];
-        auto take = [&](float lo_s, float hi_s, float lo_t, float hi_t, float far_u, uint32_t r) {
-          if (r != REF_EMPTY && lo_s <= f.ps && f.ps <= hi_s && lo_t <= f.pt && f.pt <= hi_t && f.g * far_u > f.pu) {
-            if (next == REF_EMPTY) next = r;
-            else stack[(sp++) * CP_BLOCK] = (int)r;
-          }
-        };
-        take(ls.x, hs.x, lt.x, ht.x, fu.x, __float_as_uint(rf.x));
-        take(ls.y, hs.y, lt.y, ht.y, fu.y, __float_as_uint(rf.y));
-        take(ls.z, hs.z, lt.z, ht.z, fu.z, __float_as_uint(rf.z));
-        take(ls.w, hs.w, lt.w, ht.w, fu.w, __float_as_uint(rf.w));
-      }
-      if (next == REF_EMPTY) {
-        if (sp == 0) break;
-        next = (uint32_t)stack[(--sp) * CP_BLOCK];
-      }
-      ref = next;
-    }
+    slot_walk(
+        sc.inner4, stack,
+        [&](const float4* rec, auto take) {
+          const float4 ls = rec[N4_ROW_AA + cs], lt = rec[N4_ROW_AA + ct], rf = rec[N4_ROW_REF];
+          const float4 hs = rec[N4_ROW_BB + cs], ht = rec[N4_ROW_BB + ct], fu = rec[row_u];
+          auto pass = [&](float lo_s, float hi_s, float lo_t, float hi_t, float far_u) {
+            return [=, &f] { return lo_s <= f.ps && f.ps <= hi_s && lo_t <= f.pt && f.pt <= hi_t && f.g * far_u > f.pu; };
+          };
+          take(pass(ls.x, hs.x, lt.x, ht.x, fu.x), __float_as_uint(rf.x));
+          take(pass(ls.y, hs.y, lt.y, ht.y, fu.y), __float_as_uint(rf.y));
+          take(pass(ls.z, hs.z, lt.z, ht.z, fu.z), __float_as_uint(rf.z));
+          take(pass(ls.w, hs.w, lt.w, ht.w, fu.w), __float_as_uint(rf.w));
+        },
+        [&](int32_t k) { count += inside_crossed(sc.tri_geom + (size_t)k * 3, f) ? 1 : 0; });
 #pragma unroll 1
     for (int u = 0; u < sc.n_uncovered; u++) count += inside_crossed(sc.tri_geom + (size_t)sc.uncovered[u] * 3, f) ? 1 : 0;
   } else {
@@ -384,6 +407,111 @@ __global__ __launch_bounds__(CP_BLOCK) void signed_distance_kernel(SignedDistanc
   const bool in = (inside_count<WALK>(a.sc, sa.axis, p, stack) & 1) != 0;
   closest_point_store(a, i, closest_point_search<WALK>(a, i, p, stack), in ? 0x80000000u : 0u);
   if (sa.inside) sa.inside[i] = in ? 1u : 0u;
+}
+
+// ---- box-overlap queries (include/ezrt_box_overlap.h).
+//
+// box_overlap_kernel<WALK>: one box per lane.  WALK = true, the pruned route: slot_walk, descending a slot when slot.lo[c] <= hi[c]
+// && slot.hi[c] >= lo[c] on all three axes.  These are comparisons on the stored fp32 values: by H1 an overlapping triangle's own
+// bounding box passes them, hence so does every box that holds the triangle (the scene prunes), so no overlapping triangle is skipped
+// and no slack is needed; an unused slot (an all-NaN box) fails them.  Triangles that no leaf holds are swept after the walk.
+// WALK = false, the sweep route: every triangle, no tree.  Both call box_overlaps (ezrt_device.h: H1 .. H3 of the header).
+// The list, kept as nearest_kernel keeps its own: the lowest ids seen so far, ascending, in the box's own output row; `nb` entries
+// are filled, and once the row is full `last_id` holds entry K - 1.  A later overlap with a higher id is counted and touches no
+// memory; a lower one is inserted by shifting the greater entries up one slot (the K-th falls out).  With K == 0 the row is full
+// from the start and nothing is stored.
+// The visit order does not matter: the count is an integer sum over the triangles, each met once, and the row after any sequence of
+// insertions is the min(K, seen) lowest ids of what was seen.
+// Afterwards each wave finishes its 64 rows together, consecutive lanes on consecutive words: -1 into the unused slots.  Lanes past n
+// and boxes that are not live take part with nb = 0, and nothing is written past row n - 1.
+struct BoxOverlapArgs {
+  PointScene sc;
+  const float* lo;          // n x 3
+  const float* hi;          // n x 3
+  uint32_t n;
+  int32_t K;                // 0 .. 64
+  FastDiv div_k;            // / max(K, 1) (the finishing pass)
+  int32_t* tri;             // n x K (not read or written when K == 0)
+  int32_t* n_overlap;       // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t i = blockIdx.x * CP_BLOCK + lane;
+  const int K = a.K;
+  int nb = 0;
+  if (i < a.n) {
+    const f3 lo = ld3(a.lo + (size_t)i * 3), hi = ld3(a.hi + (size_t)i * 3);
+    const bool live = box_live(lo, hi);
+    int32_t* ri = a.tri + (size_t)i * K;
+    int32_t count = 0;
+    int32_t last_id = -1; // entry K - 1 once the row is full (with K == 0 it is full now, and every id is greater than -1)
+    auto put = [&](int j, int32_t id) {
+      ri[j] = id;
+      if (j == K - 1) last_id = id; // (a put to slot K - 1 happens only when the row is full)
+    };
+    auto visit = [&](int32_t k) {
+      if (!box_overlaps(a.sc.tri_geom + (size_t)k * 3, lo, hi)) return;
+      count++;
+      if (nb == K && k > last_id) return; // behind a full row: counted only
+      int j = nb < K ? nb++ : K - 1;
+      while (j > 0) {
+        const int32_t ip = ri[j - 1];
+        if (ip < k) break;
+        put(j, ip);
+        j--;
+      }
+      put(j, k);
+    };
+    if (live) {
+      if (WALK) {
+        slot_walk(
+            a.sc.inner4, lds_stack + lane,
+            [&](const float4* rec, auto take) {
+              const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
+              const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
+              auto pass = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+                return [=, &lo, &hi] { return lx <= hi.x && hx >= lo.x && ly <= hi.y && hy >= lo.y && lz <= hi.z && hz >= lo.z; };
+              };
+              take(pass(ax.x, ay.x, az.x, bx.x, by.x, bz.x), __float_as_uint(rf.x));
+              take(pass(ax.y, ay.y, az.y, bx.y, by.y, bz.y), __float_as_uint(rf.y));
+              take(pass(ax.z, ay.z, az.z, bx.z, by.z, bz.z), __float_as_uint(rf.z));
+              take(pass(ax.w, ay.w, az.w, bx.w, by.w, bz.w), __float_as_uint(rf.w));
+            },
+            visit);
+#pragma unroll 1
+        for (int u = 0; u < a.sc.n_uncovered; u++) visit(a.sc.uncovered[u]);
+      } else {
+#pragma unroll 1
+        for (int k = 0; k < a.sc.n_tri; k++) visit(k);
+      }
+    }
+    if (a.n_overlap) a.n_overlap[i] = count;
+  }
+  // the wave's 64 rows, one flat run of 64 K words from its first row; the rows were written by other lanes of this wave, whose
+  // accesses are performed in program order (the fence states it to the compiler and costs nothing at this scope)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const size_t base = (size_t)(i - lane) * K;
+  for (uint32_t e = lane; e < 64u * (uint32_t)K; e += 64u) {
+    const uint32_t row = fastdiv(e, a.div_k);
+    const uint32_t slot = e - row * (uint32_t)K;
+    const int used = __shfl(nb, (int)row);
+    if (i - lane + row < a.n && slot >= (uint32_t)used) a.tri[base + e] = -1;
+  }
+}
+
+// ezrt_box_overlap_at_device: box_overlaps for pairs the caller holds -- box i against triangle tri_id[i].  An id outside the scene
+// or a box that is not live writes 0.
+__global__ __launch_bounds__(256) void box_overlap_at_kernel(const float4* tri_geom, int32_t n_tri, const float* box_lo, const float* box_hi,
+                                                             const int32_t* tri_id, uint32_t n, uint8_t* overlaps) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  const f3 lo = ld3(box_lo + (size_t)i * 3), hi = ld3(box_hi + (size_t)i * 3);
+  bool o = false;
+  if (box_live(lo, hi) && (uint32_t)tri < (uint32_t)n_tri) o = box_overlaps(tri_geom + (size_t)tri * 3, lo, hi);
+  overlaps[i] = o ? 1u : 0u;
 }
 
 } // namespace ezd

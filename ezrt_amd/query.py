@@ -1,5 +1,5 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
-include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h).
+include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -13,10 +13,13 @@ include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h).
     inside = query.inside(scene, points, axis=0)                 # is the point inside the mesh?  (bool; include/ezrt_inside.h)
     inside, crossings = query.inside(scene, points, axis, crossings=True)   # ... and the number of triangles its axis ray crosses
     tri, point, dist, bary, inside = query.signed_distance(scene, points)   # closest_point with dist negative inside the mesh
+    tri, n_overlap = query.box_overlap(scene, lo, hi, max_k=8)   # the triangles each box [lo, hi] touches (include/ezrt_box_overlap.h)
+    touches = query.box_overlap_at(scene, lo, hi, tri)           # ... the same test for pairs already held  (bool)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
-`d_max` (optional) a float32 GPU tensor of shape points.shape[:-1].  The outputs keep the leading dimensions.  The work is enqueued on
+`d_max` (optional) a float32 GPU tensor of shape points.shape[:-1]; `lo` and `hi` are contiguous float32 GPU tensors of one shape
+[..., 3], the corners of axis-aligned boxes.  The outputs keep the leading dimensions.  The work is enqueued on
 `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the rays' device) and the functions
 return without waiting for it.  `axis` (0..5: +x, -x, +y, -y, +z, -z) is the direction of the ray whose crossings decide `inside`;
 on a closed mesh every axis gives the same answer, on an open one (the Bunny has holes) they may differ: vote over several.
@@ -35,6 +38,7 @@ Surface = collections.namedtuple("Surface", "tri t point normal inside")
 ClosestPoint = collections.namedtuple("ClosestPoint", "tri point dist bary")
 Nearest = collections.namedtuple("Nearest", "tri dist count")
 SignedDistance = collections.namedtuple("SignedDistance", "tri point dist bary inside")
+BoxOverlap = collections.namedtuple("BoxOverlap", "tri n_overlap")
 
 
 def _scene_lib(scene, abi):
@@ -405,3 +409,92 @@ def signed_distance(scene, points, d_max=None, axis=0, stream=None):
                                                        P(bary.data_ptr()), P(ins.data_ptr()), P(h)))
     _keep((points, d_max, tri, point, dist, bary, ins), ts, points)
     return SignedDistance(tri, point, dist, bary, ins.view(torch.bool))
+
+
+def _check_boxes(lo, hi):
+    """The number of boxes, after the checks every box query makes of its corners."""
+    for name, x in (("lo", lo), ("hi", hi)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise TypeError("%s must be a GPU tensor" % name)
+        if x.dtype != torch.float32:
+            raise TypeError("%s must be float32, not %s" % (name, x.dtype))
+        if x.dim() < 1 or x.shape[-1] != 3:
+            raise ValueError("%s must have shape [..., 3], not %s" % (name, tuple(x.shape)))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if hi.device != lo.device:
+        raise ValueError("hi is on %s, lo on %s" % (hi.device, lo.device))
+    if tuple(hi.shape) != tuple(lo.shape):
+        raise ValueError("hi must have shape %s, not %s" % (tuple(lo.shape), tuple(hi.shape)))
+    n = lo.numel() // 3
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 boxes per call")
+    return n
+
+
+def box_overlap(scene, lo, hi, max_k=8, count=False, stream=None):
+    """BoxOverlap(tri int32 [..., max_k], n_overlap int32 [...] or None): for every axis-aligned box [lo, hi] (contiguous float32 GPU
+    tensors of one shape [..., 3]) the triangles of the scene that touch it -- the exact separating-axis test of a closed triangle
+    against a closed box, so touching counts and a degenerate triangle overlaps as the segment or point it is.  `tri` holds the
+    lowest triangle indices in ascending order, then -1: a larger max_k (0 .. 64) only appends, and the answer depends on neither the
+    tree nor the order of the visits.  `count=True` also returns the full number of overlapping triangles, which may exceed max_k;
+    with max_k == 0 the call only counts (`tri` is empty and `count` must be True).  A box with a non-finite number or lo > hi on
+    some axis overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
+    include/ezrt_box_overlap.h; `box_overlap_at` tests pairs."""
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.BOX_OVERLAP_MAX:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.BOX_OVERLAP_MAX, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    n = _check_boxes(lo, hi)
+    lib = _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
+    lead = tuple(lo.shape[:-1])
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=lo.device)
+    total = torch.empty(lead, dtype=torch.int32, device=lo.device) if count else None
+    if n == 0:
+        return BoxOverlap(tri, total)
+    h, ts = _stream(lo, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_box_overlap_device(scene._h, P(lo.data_ptr()), P(hi.data_ptr()), n, max_k,
+                                                   P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
+    _keep((lo, hi, tri, total), ts, lo)
+    return BoxOverlap(tri, total)
+
+
+def box_overlap_at(scene, lo, hi, tri, stream=None):
+    """bool tri.shape: whether triangle tri[...] touches its box, by `box_overlap`'s test.  `tri` (int32) has the shape lo.shape[:-1],
+    or one trailing dimension more -- the output of `box_overlap` -- and every entry of a row then belongs to the row's box.  An id
+    that is no triangle of the scene (an unused slot, -1) gives False."""
+    _check_boxes(lo, hi)
+    lib = _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
+    lead = tuple(lo.shape[:-1])
+    if not isinstance(tri, torch.Tensor) or not tri.is_cuda:
+        raise TypeError("tri must be a GPU tensor")
+    if tri.dtype != torch.int32:
+        raise TypeError("tri must be int32, not %s" % tri.dtype)
+    if tri.device != lo.device:
+        raise ValueError("tri is on %s, the boxes on %s" % (tri.device, lo.device))
+    if not tri.is_contiguous():
+        raise ValueError("tri must be contiguous")
+    shape = tuple(tri.shape)
+    if shape != lead and shape[:-1] != lead:
+        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
+    n = tri.numel()
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 elements per call")
+    out = torch.empty(shape, dtype=torch.uint8, device=lo.device)
+    if n == 0:
+        return out.view(torch.bool)
+    h, ts = _stream(lo, stream)
+    per_lo, per_hi = lo, hi
+    if shape != lead:                                           # a box per entry of its row, copied on the query's own stream
+        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=lo.device)
+        with torch.cuda.stream(on):
+            per_lo = lo.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
+            per_hi = hi.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
+    P = C.c_void_p
+    _call(scene, lib.ezrt_box_overlap_at_device(scene._h, P(per_lo.data_ptr()), P(per_hi.data_ptr()), P(tri.data_ptr()), n,
+                                                P(out.data_ptr()), P(h)))
+    _keep((lo, hi, per_lo, per_hi, tri, out), ts, lo)
+    return out.view(torch.bool)
