@@ -1,6 +1,6 @@
 // ezrt_hip.hip -- libezrt_hip.so: the C ABI of include/ezrt.h implemented on hand-written gfx950 kernels.  This file: error plumbing,
 // scene lifetime, options, counters, device-resident frames.  ezrt_scene_create / ezrt_scene_set_env: ezrt_scene_build.hip; the render,
-// audit and utility entry points (everything that launches a kernel): ezrt_launch.hip.  There is no CPU compute path.
+// audit and utility entry points: ezrt_launch.hip; the one-kernel device queries: ezrt_queries.hip.  There is no CPU compute path.
 #include "ezrt_internal.h"
 
 namespace ezi {

@@ -1,9 +1,10 @@
-// ezrt_internal.h -- what the three translation units of libezrt_hip.so share (round 6: ezrt_hip.hip was one 2 800-line file):
+// ezrt_internal.h -- what the translation units of libezrt_hip.so share (round 6: ezrt_hip.hip was one 2 800-line file):
 //   ezrt_hip.hip          the C ABI's scene lifetime, options, counters, frames and error plumbing
 //   ezrt_scene_build.hip  ezrt_scene_create / ezrt_scene_set_env: the device layout of a scene -- records, the re-tree over the
 //                         reference's leaves, the 4-wide collapse, the per-triangle pruning bounds
-//   ezrt_launch.hip       every kernel launch: the launch policy of a render call (variants, LDS budgets, chunks, streams), the audit
-//                         entry points and the small utility kernels
+//   ezrt_launch.hip       the render pipeline: the launch policy of a render call (variants, LDS budgets, chunks, streams), the ray
+//                         queries that run its trace kernels, the audit entry points and the small utility kernels
+//   ezrt_queries.hip      the device queries that are one kernel on the caller's stream: shading, path, all-hits, point and box queries
 //   ezrt_refit.hip        ezrt_scene_refit_device: new vertex positions into an existing scene over the topology create kept
 // Types only -- no kernel is defined here (a __global__ function may live in one translation unit only).
 #pragma once
@@ -22,6 +23,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "ezrt.h"
@@ -475,4 +477,71 @@ namespace ezi {
 __attribute__((visibility("hidden"))) void release_chunk_scratch(Pipe& pp);
 // `bytes` of DEVICE memory of device `dev` at p (the pointer check of the stream-ordered entry points: ezrt_query.h, ezrt_refit.h)
 __attribute__((visibility("hidden"))) bool device_buffer_of(const void* p, size_t bytes, int dev);
+
+// ---- host pieces that ezrt_launch.hip and ezrt_queries.hip both use
+// the LDS traversal stack of the one-lane kernels (trace_kernel, query_kernel, radiance_query_kernel, all_hits_kernel) and of
+// traceq_kernel: a column of s->depth entries per lane
+inline size_t stack_lds_bytes(const EzrtScene* s) {
+  int entries = s->depth > 1 ? s->depth : 1; // pending far children <= depth - 1
+  return (size_t)entries * BLOCK * sizeof(int);
+}
+
+// The integrators, and the one dispatch from the runtime value to the kernels compiled for each: f(std::integral_constant<int, I>).
+// Every caller rejects an unknown integrator first (known_integrator), so the default arm only ever sees 52.
+inline bool known_integrator(int integrator) {
+  return integrator == EZRT_INTEGRATOR_P3_DIFFUSE || integrator == EZRT_INTEGRATOR_P4_DISNEY || integrator == EZRT_INTEGRATOR_P5_SOBOL ||
+         integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO;
+}
+template <class F>
+inline void with_integrator(int integrator, F&& f) {
+  switch (integrator) {
+    case EZRT_INTEGRATOR_P3_DIFFUSE: f(std::integral_constant<int, EZRT_INTEGRATOR_P3_DIFFUSE>{}); break;
+    case EZRT_INTEGRATOR_P4_DISNEY: f(std::integral_constant<int, EZRT_INTEGRATOR_P4_DISNEY>{}); break;
+    case EZRT_INTEGRATOR_P5_SOBOL: f(std::integral_constant<int, EZRT_INTEGRATOR_P5_SOBOL>{}); break;
+    case EZRT_INTEGRATOR_P5_MIS: f(std::integral_constant<int, EZRT_INTEGRATOR_P5_MIS>{}); break;
+    default: f(std::integral_constant<int, EZRT_INTEGRATOR_P5_MIS_ANISO>{}); break;
+  }
+}
+
+// What every stream-ordered entry point does around its launches: the scene's device found (where `records` lives) and made current
+// (restored on return), every buffer of `bufs` that is not NULL checked to be `bytes` of that device's memory -- `what` names them
+// and `unit` their n elements in the failure message -- then launch(grid, block) for n elements, 256 per workgroup, then `ev`, the
+// event a later refit makes its own stream wait for (ezrt_refit.h), recorded on `st` behind the call's last read of the scene's
+// records.  launch may return an int, an error code that ends the call, or nothing.
+struct DeviceBuf {
+  const void* p;
+  size_t bytes;
+};
+template <class Launch>
+inline int device_call(EzrtScene* s, const void* records, std::initializer_list<DeviceBuf> bufs, size_t n, const char* what, const char* unit,
+                       hipEvent_t QueryScratch::*ev, hipStream_t st, Launch&& launch) {
+  hipPointerAttribute_t sat;
+  if (!records || hipPointerGetAttributes(&sat, records) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EZRT_ERR_INVALID, "the scene has no device records");
+  }
+  const int dev = sat.device;
+  for (const DeviceBuf& b : bufs)
+    if (b.p && !device_buffer_of(b.p, b.bytes, dev))
+      return fail(EZRT_ERR_INVALID, "%s must be device memory of the scene's device (%d), %zu %s long", what, dev, n, unit);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  struct Restore {
+    int d;
+    ~Restore() { (void)hipSetDevice(d); }
+  } restore{prev};
+  if (dev != prev) HIP_TRY(hipSetDevice(dev));
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if constexpr (std::is_void_v<decltype(launch(grid, block))>) {
+    launch(grid, block);
+  } else {
+    const int rc = launch(grid, block);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipGetLastError());
+  hipEvent_t& e = s->query.*ev;
+  if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(e, st));
+  return 0;
+}
 } // namespace ezi

@@ -1,4 +1,5 @@
-// ezrt_kernels.h -- the gfx950 kernels of the trace path.
+// ezrt_kernels.h -- the gfx950 kernels of the trace path and of the audit entry points (ezrt_launch.hip, the only translation unit
+// that includes this).  The kernels of the device queries are in ezrt_query_kernels.h and ezrt_point_queries.h (ezrt_queries.hip).
 //
 //   trace_kernel<INTEG, FULLCTR, PATHLOG>   one thread = one pixel-sample
 //       (ray-gen + hitBVH x (1 + k*bounces) + Disney BRDF + env lookups);
@@ -6,8 +7,8 @@
 //       its four wavefronts an 8x8 sub-tile, so the 64 primary rays of a wave
 //       are coherent.  Sample radiance goes to a frame-major sample buffer.
 //       Its primary-ray arithmetic (camera_dir) and its bounce loop (path_radiance)
-//       are device functions of their own: camera_rays_kernel and
-//       radiance_query_kernel<INTEG> (include/ezrt_path.h) hand the first out
+//       are device functions of their own (ezrt_path_device.h): camera_rays_kernel
+//       and radiance_query_kernel<INTEG> (ezrt_query_kernels.h) hand the first out
 //       and run the second along caller rays, one path per lane as here.
 //   accumulate_kernel    the reference's running mean mix(last, c, 1/(k+1))
 //       (P5/fsh:943-944) applied in frame order, one thread per pixel.
@@ -23,23 +24,9 @@
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
+#include "ezrt_path_device.h"
 
 namespace ezd {
-
-// dims 0-7: the shader literal (P5/fsh:351-353); dims 8-15: include/ezrt.h, ezrt_scene_set_sampler
-__constant__ uint32_t c_sobol_v[16 * 32] = {
-#include "ezrt_sobol_v.inc"
-#include "ezrt_sobol_v16.inc"
-};
-
-// sobol(d, i): P5/fsh:361-369
-EZD float sobol(uint32_t d, uint32_t i) {
-  uint32_t result = 0, offset = d * 32u;
-  for (uint32_t j = 0; i != 0; i >>= 1, j++)
-    if (i & 1u) result ^= c_sobol_v[j + offset];
-  return (float)result * (1.0f / (float)0xFFFFFFFFu);
-}
-EZD uint32_t gray_code(uint32_t i) { return i ^ (i >> 1); }
 
 struct TraceArgs {
   DevScene sc;
@@ -99,30 +86,6 @@ EZD uint32_t queue_to_sample(uint32_t qslot, const FastDiv& n_sub_div, uint32_t 
   return ((fk * n_sub + r2) << sh) | (qslot & ((1u << sh) - 1u));
 }
 
-// The seed of pixel-sample (ix, iy, frame): P5/fsh:315-318
-EZD uint32_t pixel_seed(uint32_t ix, uint32_t iy, uint32_t frame) { return (ix * 1973u + iy * 9277u + frame * 26699u) | 1u; }
-
-// The direction of the primary ray of pixel-sample (ix, iy, frame): main() up to the hitBVH call (P5/fsh:315-318 seed, 920-925
-// jitter, camera, normalize).  `seed` returns the RNG state main() has when it reaches hitBVH: the pixel-sample's seed advanced by
-// the two jitter draws.  ONE definition for every kernel that needs the direction -- the primary stage's trace and shading kernels
-// (primary_dir), trace_kernel and ezrt_camera_rays_device -- so that the ray the trace follows, the ray the shading stage shades
-// and the ray a caller is handed are the same bits.  Of `p` it reads width, height and camera_rotate alone.
-EZD f3 camera_dir(const EzrtRenderParams& p, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t& seed) {
-  seed = pixel_seed(ix, iy, frame);
-  const float W = (float)p.width, H = (float)p.height;
-  // (x / W for a power-of-two W IS x * (1 / W) on the bits, and every BASELINE frame is one: the four divisions below as
-  // multiplications behind a uniform branch were built and measured in round 4 -- C2 -3.3 %: four more launch-invariant values
-  // in a kernel at its SGPR limit became three more VGPR spills in the refill block; profiles/r4/rcp_pow2_ab.txt)
-  float pixx = ((float)ix + 0.5f) / W * 2.0f - 1.0f;
-  float pixy = ((float)iy + 0.5f) / H * 2.0f - 1.0f;
-  float aax = (rnd(seed) - 0.5f) / W;
-  float aay = (rnd(seed) - 0.5f) / H;
-  float vx = pixx + aax, vy = pixy + aay, vz = -1.5f;
-  const float* m = p.camera_rotate;
-  f3 dir = mk(m[0] * vx + m[4] * vy + m[8] * vz, m[1] * vx + m[5] * vy + m[9] * vz, m[2] * vx + m[6] * vy + m[10] * vz);
-  return normalize(dir);
-}
-
 // The primary ray of queue position `qslot`: (dir.xyz, 1), or w = 0 for a pixel this shard does not own.
 EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const FastDiv& div_blocks, const FastDiv& div_sub, uint32_t scatter,
                        uint32_t scatter_shift, uint32_t frame_first, uint32_t qslot) {
@@ -133,129 +96,6 @@ EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const Fast
   uint32_t seed;
   const f3 dir = camera_dir(p, (uint32_t)x, (uint32_t)y, frame, seed);
   return make_float4(dir.x, dir.y, dir.z, 1.0f);
-}
-
-// Where a path's ray slots are logged (ezrt_render_paths): the 1 + 2 * max_bounce ids and distances of ONE pixel
-struct PathLog {
-  int32_t* tri;
-  float* t;
-};
-template <bool PATHLOG>
-EZD void plog(const PathLog& lg, int slot, int32_t tri, float t) {
-  if (PATHLOG) {
-    lg.tri[slot] = tri;
-    lg.t[slot] = (tri >= 0) ? t : INF;
-  }
-}
-
-// pathTracing of integrator INTEG along ONE primary ray, a whole path in this lane: main() from its hitBVH call to `color`
-// (P5/fsh:926-938 and the chapters' loops).  The ray enters through (org3, dir), used as given; the pixel-sample through
-// (ix, iy, frame) -- Cranley-Patterson offsets, Gray-coded Sobol index -- and `seed`, the RNG state behind the two jitter draws
-// (camera_dir returns it).  ONE definition of the bounce loop for every one-lane kernel: trace_kernel (the megakernel route of a
-// render call and ezrt_render_paths, which logs every ray slot through `lg`) and radiance_query_kernel (caller rays).
-template <int INTEG, bool FULLCTR, bool PATHLOG>
-EZD f3 path_radiance(const DevScene& sc, f3 org3, f3 dir, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t seed, int max_bounce,
-                     float env_clamp, int* stack, Counters& ctr, const PathLog& lg) {
-  constexpr bool P5TRI = (INTEG >= 50);
-  constexpr bool MIS = integ_mis<INTEG>();
-  constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
-  int32_t tri;
-  float t;
-  hit_bvh<FULLCTR, BLOCK>(sc, org3, dir, stack, tri, t, ctr);
-  plog<PATHLOG>(lg, 0, tri, t);
-  if (tri < 0) return hdr_color<FULLCTR>(sc, dir, env_clamp, ctr);
-  Hit hit;
-  shade_point<P5TRI>(sc, tri, t, org3, dir, hit);
-  const f3 Le0 = hit.m.emissive;
-  f3 Lo = mk(0, 0, 0), history = mk(1, 1, 1);
-  float cpu = 0.0f, cpv = 0.0f;
-  if (INTEG >= 50) cp_offsets(ix, iy, cpu, cpv);
-  const uint32_t gray = gray_code(frame + 1u);
-
-  for (int bounce = 0; bounce < max_bounce; bounce++) {
-    const f3 V = -hit.viewDir, N = hit.N;
-    f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
-    if (ANISO_IS) get_tangent(N, X, Y);
-    if (MIS) {
-      // env importance sample + shadow ray: P5/fsh:819-842
-      float h1 = rnd(seed);
-      float h2 = rnd(seed);
-      f3 Lh = sample_hdr<FULLCTR>(sc, h1, h2, ctr);
-      if (dot(N, Lh) > 0.0f) {
-        int32_t st;
-        float stt;
-        hit_bvh<FULLCTR, BLOCK>(sc, hit.P, Lh, stack, st, stt, ctr);
-        plog<PATHLOG>(lg, 1 + 2 * bounce, st, stt);
-        if (st < 0) {
-          f3 color;
-          float pdf_light;
-          hdr_color_pdf<FULLCTR>(sc, Lh, env_clamp, ctr, color, pdf_light);
-          f3 f_r;
-          float pdf_brdf;
-          brdf_evaluate_pdf<ANISO_IS>(V, N, Lh, X, Y, hit.m, f_r, pdf_brdf);
-          float w = mis_mix_weight(pdf_light, pdf_brdf);
-          Lo = Lo + (((history * w) * color) * f_r) * dot(N, Lh) / pdf_light;
-        }
-      }
-    }
-    // sample direction
-    f3 L;
-    float xi1, xi2;
-    if (INTEG >= 50) { // sobolVec2 + CP: P5/fsh:771-772, 845-846 (dims wrap at 8)
-      uint32_t d0 = ((uint32_t)bounce * 2u) & sc.sobol_mask, d1 = ((uint32_t)bounce * 2u + 1u) & sc.sobol_mask;
-      xi1 = cp_rotate(sobol(d0, gray), cpu);
-      xi2 = cp_rotate(sobol(d1, gray), cpv);
-    } else { // P3/fsh:109-114: z = rand() then phi = 2 pi rand()
-      xi1 = rnd(seed);
-      xi2 = rnd(seed);
-    }
-    float cosine, pdf;
-    f3 f_r;
-    if (MIS) {
-      float xi3 = rnd(seed);
-      L = ANISO_IS ? sample_brdf_aniso(xi1, xi2, xi3, V, N, X, Y, hit.m) : sample_brdf(xi1, xi2, xi3, V, N, hit.m);
-      cosine = dot(N, L);
-      if (cosine <= 0.0f) break;
-    } else {
-      L = to_normal_hemisphere(sample_hemisphere(xi1, xi2), N);
-      pdf = 1.0f / (2.0f * PI);
-      cosine = ez_max(0.0f, dot(L, N));
-      if (INTEG == EZRT_INTEGRATOR_P3_DIFFUSE) {
-        f_r = hit.m.baseColor / PI;
-      } else {
-        f3 tangent, bitangent;
-        get_tangent(N, tangent, bitangent);
-        f_r = brdf_evaluate<INTEG == EZRT_INTEGRATOR_P4_DISNEY>(V, N, L, tangent, bitangent, hit.m);
-      }
-    }
-    int32_t nt;
-    float ntt;
-    hit_bvh<FULLCTR, BLOCK>(sc, hit.P, L, stack, nt, ntt, ctr);
-    plog<PATHLOG>(lg, 2 + 2 * bounce, nt, ntt);
-    if (MIS) {
-      brdf_evaluate_pdf<ANISO_IS>(V, N, L, X, Y, hit.m, f_r, pdf);
-      if (pdf <= 0.0f) break;
-    }
-    if (nt < 0) {
-      f3 sky;
-      float pdf_light = 0.0f;
-      if (MIS) hdr_color_pdf<FULLCTR>(sc, L, env_clamp, ctr, sky, pdf_light);
-      else sky = hdr_color<FULLCTR>(sc, L, env_clamp, ctr);
-      if (MIS) {
-        float w = mis_mix_weight(pdf, pdf_light);
-        Lo = Lo + (((history * w) * sky) * f_r) * cosine / pdf;
-      } else {
-        Lo = Lo + ((history * sky) * f_r) * cosine / pdf;
-      }
-      break;
-    }
-    Hit nh;
-    shade_point<P5TRI>(sc, nt, ntt, hit.P, L, nh);
-    Lo = Lo + ((history * nh.m.emissive) * f_r) * cosine / pdf;
-    history = history * (f_r * cosine / pdf);
-    hit = nh;
-  }
-  return Le0 + Lo;
 }
 
 template <int INTEG, bool FULLCTR, bool PATHLOG>
@@ -617,322 +457,6 @@ __global__ __launch_bounds__(256) void fn_kernel(FnArgs q) {
   }
   float* o = q.out + (size_t)i * 3;
   o[0] = r.x, o[1] = r.y, o[2] = r.z;
-}
-
-// ---- shading queries (include/ezrt_shade.h): one element per lane, operands and results in the caller's device arrays.  The
-// material of an element is the table row of its triangle, reached as shade_point reaches it: the third texel of the triangle's
-// shade record holds the material index, and the row's 16-byte loads are issued right behind that load, ahead of the arithmetic.
-// Every kernel is specialised at compile time for what it evaluates (the integrator, the outputs asked for): no lane carries a
-// runtime switch, the registers of a lobe it never evaluates, or the loads of a row it never reads.
-//
-// The table row of triangle `tri`, or false for a miss / an id beyond the scene (the element's outputs are zeros then).  ROWS: how
-// many of the row's MAT_REC_FLOAT4 texels are loaded, from the first; the others are zeros.
-template <int ROWS>
-EZD bool shade_mat_row(const float4* tri_shade, const float4* mat_table, int32_t n_tri, int32_t tri, float4 (&m)[MAT_REC_FLOAT4]) {
-  if ((uint32_t)tri >= (uint32_t)n_tri) return false;
-  const float4 r2 = tri_shade[(size_t)tri * SHADE_REC_FLOAT4 + 2];
-  const float4* mq = mat_table + (size_t)__float_as_uint(r2.y) * MAT_REC_FLOAT4;
-#pragma unroll
-  for (int k = 0; k < MAT_REC_FLOAT4; k++) m[k] = k < ROWS ? mq[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  return true;
-}
-
-// ezrt_query_material_device: the 18 floats the row starts with (texels 0-4; mat_pack_row)
-__global__ __launch_bounds__(256) void shade_material_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
-                                                             const int32_t* tri_id, uint32_t n, float* mat18) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float4 m[MAT_REC_FLOAT4];
-  const bool ok = shade_mat_row<5>(tri_shade, mat_table, n_tri, tri_id[i], m);
-  float* o = mat18 + (size_t)i * 18;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    o[4 * k + 0] = ok ? m[k].x : 0.0f;
-    o[4 * k + 1] = ok ? m[k].y : 0.0f;
-    o[4 * k + 2] = ok ? m[k].z : 0.0f;
-    o[4 * k + 3] = ok ? m[k].w : 0.0f;
-  }
-  o[16] = ok ? m[4].x : 0.0f;
-  o[17] = ok ? m[4].y : 0.0f;
-}
-
-// ezrt_shade_eval_device: f_r and pdf of the direction L as the bounce loop of integrator INTEG computes them for its rayL
-// (ezrt_wavefront.h "start bounce b").  Integrator 3 reads baseColor alone: the row's first two texels.
-template <int INTEG, bool WANT_PDF>
-__global__ __launch_bounds__(256) void shade_eval_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
-                                                         const int32_t* tri_id, const float* Vp, const float* Np, const float* Lp,
-                                                         uint32_t n, float* f_out, float* pdf_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  constexpr bool MIS = integ_mis<INTEG>();
-  float4 q[MAT_REC_FLOAT4];
-  const bool ok = shade_mat_row<INTEG == EZRT_INTEGRATOR_P3_DIFFUSE ? 2 : MAT_REC_FLOAT4>(tri_shade, mat_table, n_tri, tri_id[i], q);
-  f3 f_r = mk(0, 0, 0);
-  float pdf = 0.0f;
-  if (ok) {
-    Mat m;
-    mat_unpack_row(m, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
-    const f3 V = ld3(Vp + (size_t)i * 3), N = ld3(Np + (size_t)i * 3), L = ld3(Lp + (size_t)i * 3);
-    if (MIS) {
-      constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
-      f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
-      if (ANISO_IS) get_tangent(N, X, Y);
-      brdf_evaluate_pdf<ANISO_IS>(V, N, L, X, Y, m, f_r, pdf);
-    } else {
-      pdf = 1.0f / (2.0f * PI);
-      if (INTEG == EZRT_INTEGRATOR_P3_DIFFUSE) {
-        f_r = m.baseColor / PI;
-      } else {
-        f3 tangent, bitangent;
-        get_tangent(N, tangent, bitangent);
-        f_r = brdf_evaluate<INTEG == EZRT_INTEGRATOR_P4_DISNEY>(V, N, L, tangent, bitangent, m);
-      }
-    }
-  }
-  st3(f_out + (size_t)i * 3, f_r);
-  if (WANT_PDF) pdf_out[i] = pdf;
-}
-
-// ezrt_shade_sample_device: the direction the bounce loop of integrator INTEG continues in.  Without MIS (3, 4, 50: one
-// instantiation) it is the uniform hemisphere about N and no material is read.
-template <int INTEG>
-__global__ __launch_bounds__(256) void shade_sample_kernel(const float4* tri_shade, const float4* mat_table, int32_t n_tri,
-                                                           const int32_t* tri_id, const float* xip, const float* Vp, const float* Np,
-                                                           uint32_t n, float* L_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  constexpr bool MIS = integ_mis<INTEG>();
-  const int32_t tri = tri_id[i];
-  f3 L = mk(0, 0, 0);
-  if (MIS) {
-    float4 q[MAT_REC_FLOAT4];
-    if (shade_mat_row<MAT_REC_FLOAT4>(tri_shade, mat_table, n_tri, tri, q)) {
-      Mat m;
-      mat_unpack_row(m, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
-      constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
-      const float* xi = xip + (size_t)i * 3;
-      const f3 V = ld3(Vp + (size_t)i * 3), N = ld3(Np + (size_t)i * 3);
-      f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);
-      if (ANISO_IS) get_tangent(N, X, Y);
-      L = ANISO_IS ? sample_brdf_aniso(xi[0], xi[1], xi[2], V, N, X, Y, m) : sample_brdf(xi[0], xi[1], xi[2], V, N, m);
-    }
-  } else if ((uint32_t)tri < (uint32_t)n_tri) {
-    const float* xi = xip + (size_t)i * 3;
-    L = to_normal_hemisphere(sample_hemisphere(xi[0], xi[1]), ld3(Np + (size_t)i * 3));
-  }
-  st3(L_out + (size_t)i * 3, L);
-}
-
-// ezrt_env_eval_device: hdr_color and / or hdr_pdf of L; both = the fused lookup of the MIS loops
-template <bool COLOUR, bool WANT_PDF>
-__global__ __launch_bounds__(256) void env_eval_kernel(DevScene sc, const float* Lp, uint32_t n, float env_clamp, float* colour,
-                                                       float* pdf_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
-  const f3 L = ld3(Lp + (size_t)i * 3);
-  f3 c = mk(0, 0, 0);
-  float pdf = 0.0f;
-  if (COLOUR && WANT_PDF) hdr_color_pdf<false>(sc, L, env_clamp, ctr, c, pdf);
-  else if (COLOUR) c = hdr_color<false>(sc, L, env_clamp, ctr);
-  else pdf = hdr_pdf<false>(sc, L, ctr);
-  if (COLOUR) st3(colour + (size_t)i * 3, c);
-  if (WANT_PDF) pdf_out[i] = pdf;
-}
-
-// ezrt_env_sample_device
-__global__ __launch_bounds__(256) void env_sample_kernel(DevScene sc, const float* xip, uint32_t n, float* L_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
-  st3(L_out + (size_t)i * 3, sample_hdr<false>(sc, xip[(size_t)i * 2], xip[(size_t)i * 2 + 1], ctr));
-}
-
-// ---- path queries (include/ezrt_path.h): one element per lane.  sample_xyf names the pixel-sample (ix, iy, frame) whose random
-// numbers an element uses.
-//
-// ezrt_camera_rays_device: (eye, camera_dir) of each pixel-sample: the primary ray a render call shoots for it
-__global__ __launch_bounds__(256) void camera_rays_kernel(EzrtRenderParams p, const uint32_t* xyf, uint32_t n, float* rays) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* q = xyf + (size_t)i * 3;
-  uint32_t seed;
-  const f3 dir = camera_dir(p, q[0], q[1], q[2], seed);
-  float* o = rays + (size_t)i * 6;
-  o[0] = p.eye[0], o[1] = p.eye[1], o[2] = p.eye[2];
-  st3(o + 3, dir);
-}
-
-// ezrt_query_radiance_device: path_radiance along the caller's ray, a whole path per lane as in trace_kernel -- the same LDS
-// traversal stack, a column per lane (the launch sizes it as the megakernel's: stack_lds_bytes).  The RNG starts where main() has
-// it at its hitBVH call: the pixel-sample's seed behind the two jitter draws.  Work counters stay in the lane and are dropped.
-struct RadianceArgs {
-  DevScene sc;
-  const float* rays;    // n x 6
-  const uint32_t* xyf;  // n x 3
-  uint32_t n;
-  int32_t max_bounce;
-  float env_clamp;
-  float* radiance;      // n x 3
-};
-template <int INTEG>
-__global__ __launch_bounds__(BLOCK) void radiance_query_kernel(RadianceArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a.n) return;
-  const float* r = a.rays + (size_t)i * 6;
-  const uint32_t* q = a.xyf + (size_t)i * 3;
-  const uint32_t ix = q[0], iy = q[1], frame = q[2];
-  uint32_t seed = pixel_seed(ix, iy, frame);
-  (void)wang_hash(seed); // the jitter draws of main(): the ray is the caller's, the state behind them the pixel-sample's
-  (void)wang_hash(seed);
-  Counters ctr = {0, 0, 0, 0, 0, 0, 0};
-  const PathLog none = {nullptr, nullptr};
-  const f3 c = path_radiance<INTEG, false, false>(a.sc, ld3(r), ld3(r + 3), ix, iy, frame, seed, a.max_bounce, a.env_clamp,
-                                                   lds_stack + threadIdx.x, ctr, none);
-  st3(a.radiance + (size_t)i * 3, c);
-}
-
-// ---- all-hits queries (include/ezrt_multihit.h): one ray per lane.
-//
-// ezrt_query_all_hits_device: hit_bvh's walk -- the reference's binary records in the reference's order, unpruned, the LDS traversal
-// stack a column per lane (launched with stack_lds_bytes, as radiance_query_kernel) -- that keeps EVERY triangle hit_triangle_t
-// accepts below the ray's bound instead of the nearest: the visit order, and with it the order of equal t, is the reference's by
-// construction.  The sorted list lives in the ray's own output row (global memory, K = max_hits entries): a ray is accepted by a
-// handful of triangles and tests hundreds, so the row is touched a few times per ray, while K * 256 entries in LDS would not fit
-// beside the stack at K = 64 (64 KiB of keys alone) and K entries in registers would cost the walk its occupancy.  `nb` entries
-// are in the row, sorted; `last` holds the t of entry K - 1 once the row is full: a candidate that is not strictly below it is
-// counted and touches no memory.  An insertion shifts the strictly greater entries up one slot (the K-th falls out), so equal t
-// stay in visit order.  HAVE_T = false (no t_hit): the keys of the entries in the row are recomputed from their ids -- t is a pure
-// function of (triangle, ray) -- by the same hit_triangle_t.
-// Afterwards each wave fills the unused slots of its 64 rows with {-1, INF} together: consecutive lanes write consecutive words.
-struct AllHitsArgs {
-  DevScene sc;
-  const float* rays;  // n x 6
-  const float* t_max; // n, or null
-  uint32_t n;
-  int32_t K;
-  FastDiv div_k;      // / K (the fill)
-  int32_t* tri;       // n x K
-  float* t;           // n x K, or null (HAVE_T = false)
-  int32_t* n_hits;    // n, or null
-};
-template <bool HAVE_T>
-__global__ __launch_bounds__(BLOCK) void all_hits_kernel(AllHitsArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  const int K = a.K;
-  int nb = 0;
-  if (i < a.n) {
-    const DevScene& sc = a.sc;
-    const float* r = a.rays + (size_t)i * 6;
-    const f3 S = ld3(r), d = ld3(r + 3);
-    // t < min(t_max, INF); a NaN t_max admits nothing (no hit has t < 0.0005)
-    float bound = INF;
-    if (a.t_max) {
-      const float tm = a.t_max[i];
-      bound = tm < INF ? tm : (tm >= INF ? INF : 0.0f);
-    }
-    int32_t* ri = a.tri + (size_t)i * K;
-    float* rt = HAVE_T ? a.t + (size_t)i * K : nullptr;
-    uint32_t count = 0;
-    float last = INF;
-    auto key = [&](int j) -> float {
-      if (HAVE_T) return rt[j];
-      float tj = INF;
-      (void)hit_triangle_t(sc.tri_geom + (size_t)ri[j] * 3, S, d, tj);
-      return tj;
-    };
-    auto put = [&](int j, int32_t id, float tj) {
-      ri[j] = id;
-      if (HAVE_T) rt[j] = tj;
-      if (j == K - 1) last = tj;
-    };
-    int* stack = lds_stack + threadIdx.x;
-    const f3 inv = mk(ez_rcp(d.x), ez_rcp(d.y), ez_rcp(d.z));
-    int sp = 0;
-    uint32_t ref = sc.root_ref;
-    for (;;) {
-      if (ref & LEAF_BIT) {
-        const int first = (int)(ref & 0x00ffffffu);
-        const int n = (int)((ref >> 24) & 0x7fu) + 1;
-        for (int k = first; k < first + n; k++) {
-          float t;
-          if (!hit_triangle_t(sc.tri_geom + (size_t)k * 3, S, d, t) || !(t < bound)) continue;
-          count++;
-          if (nb == K && !(t < last)) continue; // behind a full row: counted only
-          int j = nb < K ? nb++ : K - 1;
-          while (j > 0) {
-            const float tp = key(j - 1);
-            if (!(tp > t)) break;
-            put(j, ri[j - 1], tp);
-            j--;
-          }
-          put(j, k, t);
-        }
-      } else {
-        const float4* q = sc.inner + (size_t)ref * 4;
-        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-        const float d1 = hit_aabb(S, inv, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y));
-        const float d2 = hit_aabb(S, inv, mk(q1.z, q1.w, q2.x), mk(q2.y, q2.z, q2.w));
-        const uint32_t left = __float_as_uint(q3.x), right = __float_as_uint(q3.y);
-        if (d1 > 0.0f && d2 > 0.0f) {
-          if (d1 < d2) { // left first: push right, continue with left
-            stack[sp * BLOCK] = (int)right;
-            sp++;
-            ref = left;
-          } else {
-            stack[sp * BLOCK] = (int)left;
-            sp++;
-            ref = right;
-          }
-          continue;
-        } else if (d1 > 0.0f) {
-          ref = left;
-          continue;
-        } else if (d2 > 0.0f) {
-          ref = right;
-          continue;
-        }
-      }
-      if (sp == 0) break;
-      sp--;
-      ref = (uint32_t)stack[sp * BLOCK];
-    }
-    if (a.n_hits) a.n_hits[i] = (int32_t)count;
-  }
-  // the unused slots of the wave's 64 rows: one flat run of 64 K words from the wave's first row
-  const uint32_t lane = threadIdx.x & 63u;
-  const size_t base = (size_t)(i - lane) * K;
-  for (uint32_t e = lane; e < 64u * (uint32_t)K; e += 64u) {
-    const uint32_t row = fastdiv(e, a.div_k);
-    const uint32_t slot = e - row * (uint32_t)K;
-    const int used = __shfl(nb, (int)row);
-    if (i - lane + row < a.n && slot >= (uint32_t)used) {
-      a.tri[base + e] = -1;
-      if (HAVE_T) a.t[base + e] = INF;
-    }
-  }
-}
-
-// ezrt_surface_at_device: surface_point for hits the caller holds -- {triangle, t} of element i along ray i.  An id outside the
-// scene writes zeros; point / normal / inside may each be null (not written).
-template <bool P5TRI>
-__global__ __launch_bounds__(256) void surface_at_kernel(const float4* tri_geom, const float4* tri_shade, int32_t n_tri, const float* rays,
-                                                         const int32_t* tri_id, const float* t_hit, uint32_t n, float* point,
-                                                         float* normal, uint8_t* inside) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int32_t tri = tri_id[i];
-  f3 P = mk(0.0f, 0.0f, 0.0f), N = mk(0.0f, 0.0f, 0.0f);
-  bool in = false;
-  if ((uint32_t)tri < (uint32_t)n_tri) {
-    const float* r = rays + (size_t)i * 6;
-    surface_point<P5TRI>(tri_geom, tri_shade, tri, t_hit[i], ld3(r), ld3(r + 3), P, N, in, [](float4) {});
-  }
-  if (point) st3(point + (size_t)i * 3, P);
-  if (normal) st3(normal + (size_t)i * 3, N);
-  if (inside) inside[i] = in ? 1u : 0u;
 }
 
 // ezrt_debug_math op 18: ez_rcp(x) against the compiler's `1.0f / x` for ALL 2^32 bit patterns of x (a NaN equals a NaN).

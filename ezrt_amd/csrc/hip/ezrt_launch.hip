@@ -1,22 +1,21 @@
-// ezrt_launch.hip -- every kernel launch of libezrt_hip.so: the launch policy of a render call (which instance of which kernel, LDS
-// budgets and workgroups per CU, chunks, the two scratch sets and their streams), the audit entry points (ezrt_render_paths,
-// ezrt_query_hits, ezrt_debug_math) and the small utility kernels (tone map, Sobol, non-finite count).  DESIGN.md 5.
+// ezrt_launch.hip -- the render pipeline of libezrt_hip.so and everything that launches its kernels: the launch policy of a render call
+// (which instance of which kernel, LDS budgets and workgroups per CU, chunks, the two scratch sets and their streams), the ray queries
+// that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device), the audit
+// entry points (ezrt_render_paths, ezrt_query_hits, ezrt_debug_math) and the small utility kernels (tone map, Sobol, non-finite
+// count).  The device queries that are one kernel of their own are another translation unit, ezrt_queries.hip.  DESIGN.md 5.
 #include "ezrt_internal.h"
+#include "ezrt_lds_budget.h"
 #include "ezrt_query.h"
 #include "ezrt_surface.h"
-#include "ezrt_shade.h"
-#include "ezrt_path.h"
-#include "ezrt_multihit.h"
-#include "ezrt_closest_point.h"
-#include "ezrt_inside.h"
-#include "ezrt_nearest.h"
-#include "ezrt_box_overlap.h"
 #include "ezrt_kernels.h"
-#include "ezrt_point_queries.h"
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
 
+#include <climits>
+
 namespace {
+using ezi::stack_lds_bytes;
+using ezi::with_integrator;
 
 int validate_params(const EzrtScene* s, const EzrtRenderParams* p) {
   if (!p) return fail(EZRT_ERR_INVALID, "params is NULL");
@@ -24,8 +23,7 @@ int validate_params(const EzrtScene* s, const EzrtRenderParams* p) {
   if (p->x0 < 0 || p->y0 < 0 || p->x1 > p->width || p->y1 > p->height || p->x0 > p->x1 || p->y0 > p->y1)
     return fail(EZRT_ERR_INVALID, "pixel rect outside the image");
   if (p->max_bounce < 0 || p->max_bounce > 64) return fail(EZRT_ERR_INVALID, "max_bounce out of range [0,64]");
-  if (p->integrator != 3 && p->integrator != 4 && p->integrator != 50 && p->integrator != 51 && p->integrator != 52)
-    return fail(EZRT_ERR_INVALID, "unknown integrator");
+  if (!ezi::known_integrator(p->integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator");
   if (p->shard_count < 0 || p->shard_index < 0 || (p->shard_count > 0 && p->shard_index >= p->shard_count))
     return fail(EZRT_ERR_INVALID, "bad shard index/count");
   if (p->tile_w < 0 || p->tile_h < 0) return fail(EZRT_ERR_INVALID, "bad tile size");
@@ -73,13 +71,7 @@ void launch_trace_i(const TraceArgs& a, int mode, dim3 grid, size_t lds, hipStre
 }
 // mode: 0 timed, 1 full counters, 2 path log
 void launch_trace(const TraceArgs& a, int mode, dim3 grid, size_t lds, hipStream_t st) {
-  switch (a.p.integrator) {
-    case EZRT_INTEGRATOR_P3_DIFFUSE: launch_trace_i<EZRT_INTEGRATOR_P3_DIFFUSE>(a, mode, grid, lds, st); break;
-    case EZRT_INTEGRATOR_P4_DISNEY: launch_trace_i<EZRT_INTEGRATOR_P4_DISNEY>(a, mode, grid, lds, st); break;
-    case EZRT_INTEGRATOR_P5_SOBOL: launch_trace_i<EZRT_INTEGRATOR_P5_SOBOL>(a, mode, grid, lds, st); break;
-    case EZRT_INTEGRATOR_P5_MIS_ANISO: launch_trace_i<EZRT_INTEGRATOR_P5_MIS_ANISO>(a, mode, grid, lds, st); break;
-    default: launch_trace_i<EZRT_INTEGRATOR_P5_MIS>(a, mode, grid, lds, st); break;
-  }
+  with_integrator(a.p.integrator, [&](auto I) { launch_trace_i<decltype(I)::value>(a, mode, grid, lds, st); });
 }
 
 // Events and the shared stream pair of a scene, created on its first render call.  Idempotent and incremental: a
@@ -113,13 +105,6 @@ int ensure_events(EzrtScene* s) {
   return 0;
 }
 
-size_t stack_lds_bytes(const EzrtScene* s) {
-  int entries = s->depth > 1 ? s->depth : 1; // pending far children <= depth - 1
-  return (size_t)entries * BLOCK * sizeof(int);
-}
-
-
-
 // Launch configuration of traceq_kernel (shared by the render pipeline and the audit routes).
 // LDS per workgroup: traversal stack + lane table + as many top-of-tree records (80 B each) as fit
 // when the register budget's `trace_wps` waves/SIMD (= trace_wps workgroups of 256 per CU) are resident
@@ -138,27 +123,19 @@ int ensure_num_cus(EzrtScene* s) {
   }
   return 0;
 }
-TraceCfg trace_cfg(const EzrtScene* s) { // needs s->num_cus
+// (needs s->num_cus) stack_bytes of traversal stack, `wps` workgroups per CU wanted, the tree's n_records of rec_bytes each;
+// the LDS arithmetic is ezrt_lds_budget.h's
+TraceCfg make_trace_cfg(const EzrtScene* s, size_t stack_bytes, int wps, size_t rec_bytes, int n_records) {
   TraceCfg c;
-  const Tuning& tu = s->tune;
-  c.lds = stack_lds_bytes(s);
+  c.lds = stack_bytes;
   const size_t lds_fixed = c.lds + BLOCK * sizeof(int);
-  int blocks_per_cu = tu.trace_wps > 0 ? tu.trace_wps : 5;
-  if ((size_t)blocks_per_cu * lds_fixed > 158 * 1024) blocks_per_cu = (int)((158 * 1024) / lds_fixed);
-  if (blocks_per_cu < 1) blocks_per_cu = 1;
-  size_t lds_budget = (size_t)(158 * 1024) / blocks_per_cu;
-  if (lds_budget > 64 * 1024) lds_budget = 64 * 1024; // static cap of a dynamic-LDS launch without opt-in
-  lds_budget -= lds_budget / 16; // allocation-granule slack: a workgroup must not lose its CU slot to rounding
-  int lds_nodes = lds_budget > lds_fixed ? (int)((lds_budget - lds_fixed) / 80) : 0;
-  if (lds_nodes > s->n_inner) lds_nodes = s->n_inner;
-  if (lds_nodes > tu.lds_nodes) lds_nodes = tu.lds_nodes;
-  if (lds_nodes < 0) lds_nodes = 0;
-  c.lds_nodes = lds_nodes;
-  c.lds_t = lds_fixed + (size_t)lds_nodes * 80;
-  c.blocks_per_cu = blocks_per_cu;
-  c.grid_full = (unsigned)(s->num_cus * blocks_per_cu);
+  c.blocks_per_cu = ezi::lds_workgroups(wps > 0 ? wps : 5, lds_fixed);
+  c.lds_nodes = ezi::lds_records(c.blocks_per_cu, lds_fixed, rec_bytes, n_records, s->tune.lds_nodes);
+  c.lds_t = lds_fixed + (size_t)c.lds_nodes * rec_bytes;
+  c.grid_full = (unsigned)(s->num_cus * c.blocks_per_cu);
   return c;
 }
+TraceCfg trace_cfg(const EzrtScene* s) { return make_trace_cfg(s, stack_lds_bytes(s), s->tune.trace_wps, 80, s->n_inner); }
 // the template instance a render call uses for this scene's settings
 void launch_traceq_cfg(EzrtScene* s, const TraceCfg& c, const TraceQArgs& q, bool small, hipStream_t st) {
   const unsigned trace_grid = small ? 64u : c.grid_full; // redo lists are (nearly) empty
@@ -194,10 +171,7 @@ int stack_rows4(const EzrtScene* s) {
 }
 int records_staged4(const EzrtScene* s, int wps) {
   const size_t lds_fixed = (size_t)stack_rows4(s) * BLOCK * sizeof(int) + BLOCK * sizeof(int);
-  size_t budget = (size_t)(158 * 1024) / (size_t)(wps > 0 ? wps : 1);
-  if (budget > 64 * 1024) budget = 64 * 1024;
-  budget -= budget / 16;
-  return budget > lds_fixed ? (int)((budget - lds_fixed) / (N4_LDS_DWORDS * 4)) : 0;
+  return ezi::lds_records(wps, lds_fixed, (size_t)N4_LDS_DWORDS * 4, INT_MAX, INT_MAX);
 }
 int wps4(const EzrtScene* s, bool rel) {
   const int w = s->tune.trace_wps_rel;
@@ -214,27 +188,7 @@ int wps4(const EzrtScene* s, bool rel) {
 // rel: the launch traverses boxes translated by a common origin (traceq4_kernel<.., true>); wps > 0: workgroups per CU of a kernel
 // with another register budget (traceq4_occ_kernel) instead of wps4's
 TraceCfg trace_cfg4(const EzrtScene* s, bool rel, int wps = 0) {
-  TraceCfg c;
-  Tuning tu = s->tune;
-  tu.trace_wps = wps > 0 ? wps : wps4(s, rel);
-  c.lds = (size_t)stack_rows4(s) * BLOCK * sizeof(int);
-  const size_t lds_fixed = c.lds + BLOCK * sizeof(int);
-  int blocks_per_cu = tu.trace_wps > 0 ? tu.trace_wps : 5;
-  if ((size_t)blocks_per_cu * lds_fixed > 158 * 1024) blocks_per_cu = (int)((158 * 1024) / lds_fixed);
-  if (blocks_per_cu < 1) blocks_per_cu = 1;
-  size_t lds_budget = (size_t)(158 * 1024) / blocks_per_cu;
-  if (lds_budget > 64 * 1024) lds_budget = 64 * 1024;
-  lds_budget -= lds_budget / 16;
-  const size_t rec_bytes = (size_t)N4_LDS_DWORDS * 4;
-  int n = lds_budget > lds_fixed ? (int)((lds_budget - lds_fixed) / rec_bytes) : 0;
-  if (n > s->n_inner4) n = s->n_inner4;
-  if (n > tu.lds_nodes) n = tu.lds_nodes;
-  if (n < 0) n = 0;
-  c.lds_nodes = n;
-  c.lds_t = lds_fixed + (size_t)n * rec_bytes;
-  c.blocks_per_cu = blocks_per_cu;
-  c.grid_full = (unsigned)(s->num_cus * blocks_per_cu);
-  return c;
+  return make_trace_cfg(s, (size_t)stack_rows4(s) * BLOCK * sizeof(int), wps > 0 ? wps : wps4(s, rel), (size_t)N4_LDS_DWORDS * 4, s->n_inner4);
 }
 // whether the timed stages of this scene run traceq4_kernel
 bool use_wide4(const EzrtScene* s) {
@@ -352,6 +306,23 @@ void launch_traceq4_cfg(EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, c
   else launch_traceq4_rel<false, false>(s, c4, A, st);
 }
 
+// The redo launch of a stage whose launch was `t`: the rays on t's redo list (exact ties beyond two candidates, rays that are not tame,
+// spill areas that ran full -- normally none) traced by the binary kernel in reference order, one lane per ray, plain stores.  Its
+// queue is the list (t.redo_slots, t.redo_count long); head: its own slot of reservation counters.
+void launch_redo(EzrtScene* s, const TraceCfg& cfg, const TraceQArgs& t, uint32_t* head, hipStream_t st) {
+  TraceQArgs r = t;
+  r.steal = 0u;
+  r.count_rays = 0u;
+  r.slot_map = t.redo_slots;
+  r.n_paths = t.redo_count;
+  r.rays_per_path = 1u;
+  r.head = head;
+  r.dbg = nullptr;
+  r.wave_log = nullptr;
+  r.force_pending = 0u;
+  launch_traceq_cfg(s, cfg, r, true, st);
+}
+
 // schedule fields of a traceq launch that come from the knobs (clamped: ADVICE r1)
 void fill_trace_knobs(const EzrtScene* s, const TraceCfg& c, TraceQArgs& t) {
   const Tuning& tu = s->tune;
@@ -402,13 +373,7 @@ void launch_shade_i(const WfArgs& a, bool full, dim3 grid, hipStream_t st) {
 // line before any shading.  Until round 6 a knob could put it on a side stream under the first shading pass: the two measured the same, and the
 // cross-stream waits it needed can enter a slow state on this runtime (ezrt_streams.h); removed with its stream and events.)
 void launch_shade(const WfArgs& a, bool full, dim3 grid, hipStream_t st) {
-  switch (a.p.integrator) {
-    case EZRT_INTEGRATOR_P3_DIFFUSE: launch_shade_i<EZRT_INTEGRATOR_P3_DIFFUSE>(a, full, grid, st); break;
-    case EZRT_INTEGRATOR_P4_DISNEY: launch_shade_i<EZRT_INTEGRATOR_P4_DISNEY>(a, full, grid, st); break;
-    case EZRT_INTEGRATOR_P5_SOBOL: launch_shade_i<EZRT_INTEGRATOR_P5_SOBOL>(a, full, grid, st); break;
-    case EZRT_INTEGRATOR_P5_MIS_ANISO: launch_shade_i<EZRT_INTEGRATOR_P5_MIS_ANISO>(a, full, grid, st); break;
-    default: launch_shade_i<EZRT_INTEGRATOR_P5_MIS>(a, full, grid, st); break;
-  }
+  with_integrator(a.p.integrator, [&](auto I) { launch_shade_i<decltype(I)::value>(a, full, grid, st); });
 }
 
 // The queues of one chunk (n_slots pixel-samples in flight).  hipErrorOutOfMemory leaves the pipe consistent (a DevBuf that
@@ -612,7 +577,6 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
       HIP_TRY(hipMemsetAsync(pp.wave_log.p, 0, (size_t)trace_grid_full * (BLOCK / 64) * 8 * sizeof(unsigned long long), st));
       t.wave_log = pp.wave_log.p;
     }
-    auto launch_traceq = [&](const TraceQArgs& q, bool small = false) { launch_traceq_cfg(s, cfg, q, small, st); };
     int e = tu.launch_events ? s->n_trace_events : MAX_TRACE_EVENTS;
     if (e < MAX_TRACE_EVENTS) {
       while (s->n_trace_events_created <= e) { // (calls with more than 64 timed launches: created on first use)
@@ -628,20 +592,8 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
         const bool rel = b == 0 && tu.rel_boxes;
         launch_traceq4_cfg(s, rel ? cfg4_rel : cfg4_abs, t, rel ? pp.inner4_rel.p : nullptr, st, (rel && gen_primary) ? &a : nullptr, pp.ovf.p);
       }
-      else launch_traceq(t);
-      if (t.steal || wide) { // rays that met an exact distance tie, or (4-wide) are not tame -- normally none: reference order, plain stores
-        TraceQArgs r = t;
-        r.steal = 0u;
-        r.count_rays = 0u;
-        r.slot_map = pp.redo_slots.p;
-        r.n_paths = pp.qcounts.p + 128 + b;
-        r.rays_per_path = 1u;
-        r.head = pp.qheads.p + (size_t)(40 + b) * HEAD_SLOT;
-        r.dbg = nullptr;
-        r.wave_log = nullptr;
-        r.force_pending = 0u;
-        launch_traceq(r, true);
-      }
+      else launch_traceq_cfg(s, cfg, t, false, st);
+      if (t.steal || wide) launch_redo(s, cfg, t, pp.qheads.p + (size_t)(40 + b) * HEAD_SLOT, st);
     }
     if (e < MAX_TRACE_EVENTS) {
       HIP_TRY(hipEventRecord(s->ev_trace[e][1], st));
@@ -1095,15 +1047,7 @@ static int ezrt_query_hits_body(EzrtScene* s, const float* rays, int n_rays, int
       launch_traceq4_cfg(s, trace_cfg4(s, rel4 != nullptr), t, rel4, nullptr, nullptr, pp.ovf.p);
     }
     else launch_traceq_cfg(s, cfg, t, false, nullptr);
-    if (t.steal || wide) {
-      TraceQArgs r = t;
-      r.steal = 0u;
-      r.count_rays = 0u;
-      r.slot_map = pp.redo_slots.p;
-      r.n_paths = pp.qcounts.p + 128;
-      r.head = pp.qheads.p + (size_t)40 * HEAD_SLOT;
-      launch_traceq_cfg(s, cfg, r, true, nullptr);
-    }
+    if (t.steal || wide) launch_redo(s, cfg, t, pp.qheads.p + (size_t)40 * HEAD_SLOT, nullptr);
     HIP_TRY(hipEventRecord(s->ev_trace[0][1], nullptr));
     s->n_trace_events = 1;
     hipLaunchKernelGGL(query_unpack_kernel, dim3(g1), dim3(256), 0, nullptr, pp.hits2[0].p, (uint32_t)n, dtri.p, dt.p);
@@ -1169,120 +1113,91 @@ struct SurfaceOut {
 // query_surface_kernel takes query_answer_kernel's place and also writes the winners' surface attributes.
 static int query_device_body(EzrtScene* s, const float* rays, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,
                              uint8_t* occluded, hipStream_t st, const SurfaceOut* surf = nullptr) {
-  const size_t n = (size_t)(n_rays > 0 ? n_rays : 0);
-  // the scene's device: where its records live
-  hipPointerAttribute_t sat;
-  if (!s->tri_geom.p || hipPointerGetAttributes(&sat, s->tri_geom.p) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(EZRT_ERR_INVALID, "the scene has no device records");
-  }
-  const int dev = sat.device;
-  using ezi::device_buffer_of;
-  if (!device_buffer_of(rays, n * 6 * sizeof(float), dev) || (t_max && !device_buffer_of(t_max, n * sizeof(float), dev)) ||
-      (occluded && !device_buffer_of(occluded, n, dev)) || (tri_id && !device_buffer_of(tri_id, n * sizeof(int32_t), dev)) ||
-      (t_hit && !device_buffer_of(t_hit, n * sizeof(float), dev)) ||
-      (surf && surf->point && !device_buffer_of(surf->point, n * 3 * sizeof(float), dev)) ||
-      (surf && surf->normal && !device_buffer_of(surf->normal, n * 3 * sizeof(float), dev)) ||
-      (surf && surf->inside && !device_buffer_of(surf->inside, n, dev)))
-    return fail(EZRT_ERR_INVALID, "rays, t_max and outputs must be device memory of the scene's device (%d), %zu rays long", dev, n);
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-  } restore{prev};
-  if (dev != prev) HIP_TRY(hipSetDevice(dev));
-  int rc = ensure_num_cus(s);
-  if (rc) return rc;
+  const size_t n = (size_t)(n_rays > 0 ? n_rays : 0), f = n * sizeof(float);
+  const SurfaceOut none{nullptr, nullptr, nullptr, false};
+  const SurfaceOut& so = surf ? *surf : none;
+  // (the event recorded behind the last kernel, the surface kernel's reads of the scene's records included, is QueryScratch::ev_end)
+  return ezi::device_call(s, s->tri_geom.p, {{rays, 6 * f}, {t_max, f}, {occluded, n}, {tri_id, n * sizeof(int32_t)}, {t_hit, f},
+                                             {so.point, 3 * f}, {so.normal, 3 * f}, {so.inside, n}},
+                          n, "rays, t_max and outputs", "rays", &QueryScratch::ev_end, st, [&](dim3 g1, dim3 b1) -> int {
+      int rc = ensure_num_cus(s);
+      if (rc) return rc;
+      QueryScratch& q = s->query;
+      constexpr size_t HEAD_SLOT = (size_t)TRACE_HEADS * TRACE_HEAD_STRIDE;
+      constexpr size_t CTL_WORDS = TRACE_HEAD_STRIDE + 2 * HEAD_SLOT; // [0] queue length, [1] redo count; heads of the trace and redo launches
+      const bool wide = use_wide4(s);
+      // occlusion rays run the bounded any-hit kernel where the render calls run the nearest-first 4-wide traversal; elsewhere (binary
+      // kernel, pruning off or in slot order) they take the closest-hit route and query_answer_kernel compares with t_max: exact either way
+      const bool occ_kernel = occluded && wide && prune_mode(s) == 2;
+      const TraceCfg cfg = trace_cfg(s);
+      // (traceq4_occ_kernel runs at OCC_WPS waves per SIMD -- 90 VGPRs, no spills; at 6 it spilled 5 -- so at most that many workgroups per
+      // CU: a persistent launch must be resident all at once)
+      constexpr int OCC_WPS = 5;
+      const TraceCfg cfg4 = wide ? trace_cfg4(s, false, occ_kernel ? std::min(OCC_WPS, wps4(s, false)) : 0) : TraceCfg();
+      HIP_TRY(q.rq_o.ensure(n));
+      HIP_TRY(q.rq_d.ensure(n));
+      HIP_TRY(q.hits.ensure(n));
+      HIP_TRY(q.redo_slots.ensure(n));
+      if (q.redo_flag.n < n) {
+        HIP_TRY(q.redo_flag.ensure(n));
+        HIP_TRY(hipMemsetAsync(q.redo_flag.p, 0, q.redo_flag.n * sizeof(uint32_t), st));
+      }
+      HIP_TRY(q.ctl.ensure(CTL_WORDS));
+      if (!q.counters.p) {
+        HIP_TRY(q.counters.ensure((size_t)CTR_SLOTS * EZRT_CTR_COUNT));
+        HIP_TRY(hipMemsetAsync(q.counters.p, 0, q.counters.n * sizeof(unsigned long long), st));
+      }
+      if (wide) HIP_TRY(q.ovf.ensure((size_t)cfg4.grid_full * BLOCK * (size_t)std::max(OVF_CAP, ovf_cap4(s))));
 
-  QueryScratch& q = s->query;
-  constexpr size_t HEAD_SLOT = (size_t)TRACE_HEADS * TRACE_HEAD_STRIDE;
-  constexpr size_t CTL_WORDS = TRACE_HEAD_STRIDE + 2 * HEAD_SLOT; // [0] queue length, [1] redo count; heads of the trace and redo launches
-  const bool wide = use_wide4(s);
-  // occlusion rays run the bounded any-hit kernel where the render calls run the nearest-first 4-wide traversal; elsewhere (binary
-  // kernel, pruning off or in slot order) they take the closest-hit route and query_answer_kernel compares with t_max: exact either way
-  const bool occ_kernel = occluded && wide && prune_mode(s) == 2;
-  const TraceCfg cfg = trace_cfg(s);
-  // (traceq4_occ_kernel runs at OCC_WPS waves per SIMD -- 90 VGPRs, no spills; at 6 it spilled 5 -- so at most that many workgroups per
-  // CU: a persistent launch must be resident all at once)
-  constexpr int OCC_WPS = 5;
-  const TraceCfg cfg4 = wide ? trace_cfg4(s, false, occ_kernel ? std::min(OCC_WPS, wps4(s, false)) : 0) : TraceCfg();
-  HIP_TRY(q.rq_o.ensure(n));
-  HIP_TRY(q.rq_d.ensure(n));
-  HIP_TRY(q.hits.ensure(n));
-  HIP_TRY(q.redo_slots.ensure(n));
-  if (q.redo_flag.n < n) {
-    HIP_TRY(q.redo_flag.ensure(n));
-    HIP_TRY(hipMemsetAsync(q.redo_flag.p, 0, q.redo_flag.n * sizeof(uint32_t), st));
-  }
-  HIP_TRY(q.ctl.ensure(CTL_WORDS));
-  if (!q.counters.p) {
-    HIP_TRY(q.counters.ensure((size_t)CTR_SLOTS * EZRT_CTR_COUNT));
-    HIP_TRY(hipMemsetAsync(q.counters.p, 0, q.counters.n * sizeof(unsigned long long), st));
-  }
-  if (wide) HIP_TRY(q.ovf.ensure((size_t)cfg4.grid_full * BLOCK * (size_t)std::max(OVF_CAP, ovf_cap4(s))));
-
-  const unsigned g1 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(query_dev_pack_kernel, dim3(g1), dim3(256), 0, st, rays, t_max, (uint32_t)n, occ_kernel ? 1u : 0u, q.rq_o.p,
-                     q.rq_d.p, q.ctl.p, (uint32_t)CTL_WORDS);
-  TraceQArgs t;
-  t.sc = trace_scene(s->dev());
-  t.rq.o = q.rq_o.p;
-  t.rq.d = q.rq_d.p;
-  t.hits = q.hits.p;
-  t.n_paths = q.ctl.p;
-  t.rays_per_path = 1u;
-  t.const_origin = 0u;
-  t.inner_rel = nullptr;
-  t.origin[0] = t.origin[1] = t.origin[2] = 0.0f;
-  t.head = q.ctl.p + TRACE_HEAD_STRIDE;
-  t.counters = q.counters.p;
-  fill_trace_knobs(s, cfg, t);
-  t.dbg = nullptr;
-  t.slot_map = nullptr;
-  t.steal = s->tune.steal ? 1u : 0u;
-  t.count_rays = 0u;
-  t.redo_count = q.ctl.p + 1;
-  t.redo_slots = q.redo_slots.p;
-  t.redo_flag = q.redo_flag.p;
-  t.force_pending = 0u;
-  t.wave_log = nullptr;
-  const int launches = s->n_trace_launches; // (the launch helpers count render launches: ezrt_last_render_ms reports them)
-  if (occ_kernel) {
-    TraceQ4Args A;
-    fill_traceq4_args(s, cfg4, t, nullptr, nullptr, q.ovf.p, A);
-    hipLaunchKernelGGL((traceq4_occ_kernel<OCC_WPS>), dim3(cfg4.grid_full), dim3(BLOCK), cfg4.lds_t, st, A);
-  } else if (wide) {
-    launch_traceq4_cfg(s, cfg4, t, nullptr, st, nullptr, q.ovf.p);
-  } else {
-    launch_traceq_cfg(s, cfg, t, false, st);
-  }
-  if (t.steal || wide) { // exact ties, rays that are not tame, full spill areas: the in-order kernel, its queue length on the device
-    TraceQArgs r = t;
-    r.steal = 0u;
-    r.slot_map = q.redo_slots.p;
-    r.n_paths = q.ctl.p + 1;
-    r.head = q.ctl.p + TRACE_HEAD_STRIDE + HEAD_SLOT;
-    launch_traceq_cfg(s, cfg, r, true, st);
-  }
-  s->n_trace_launches = launches;
-  if (surf) {
-    const DevScene sc = s->dev();
-    if (surf->p5tri)
-      hipLaunchKernelGGL(query_surface_kernel<true>, dim3(g1), dim3(256), 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
-                         (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
-    else
-      hipLaunchKernelGGL(query_surface_kernel<false>, dim3(g1), dim3(256), 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
-                         (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
-  } else {
-    hipLaunchKernelGGL(query_answer_kernel, dim3(g1), dim3(256), 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
-  }
-  HIP_TRY(hipGetLastError());
-  // the end of this query on its stream (after its last read of the scene's records, the surface kernel's included): a refit of
-  // the scene (ezrt_refit.h) makes its own stream wait for it
-  if (!q.ev_end) HIP_TRY(hipEventCreateWithFlags(&q.ev_end, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(q.ev_end, st));
-  return 0;
+      hipLaunchKernelGGL(query_dev_pack_kernel, g1, b1, 0, st, rays, t_max, (uint32_t)n, occ_kernel ? 1u : 0u, q.rq_o.p,
+                         q.rq_d.p, q.ctl.p, (uint32_t)CTL_WORDS);
+      TraceQArgs t;
+      t.sc = trace_scene(s->dev());
+      t.rq.o = q.rq_o.p;
+      t.rq.d = q.rq_d.p;
+      t.hits = q.hits.p;
+      t.n_paths = q.ctl.p;
+      t.rays_per_path = 1u;
+      t.const_origin = 0u;
+      t.inner_rel = nullptr;
+      t.origin[0] = t.origin[1] = t.origin[2] = 0.0f;
+      t.head = q.ctl.p + TRACE_HEAD_STRIDE;
+      t.counters = q.counters.p;
+      fill_trace_knobs(s, cfg, t);
+      t.dbg = nullptr;
+      t.slot_map = nullptr;
+      t.steal = s->tune.steal ? 1u : 0u;
+      t.count_rays = 0u;
+      t.redo_count = q.ctl.p + 1;
+      t.redo_slots = q.redo_slots.p;
+      t.redo_flag = q.redo_flag.p;
+      t.force_pending = 0u;
+      t.wave_log = nullptr;
+      const int launches = s->n_trace_launches; // (the launch helpers count render launches: ezrt_last_render_ms reports them)
+      if (occ_kernel) {
+        TraceQ4Args A;
+        fill_traceq4_args(s, cfg4, t, nullptr, nullptr, q.ovf.p, A);
+        hipLaunchKernelGGL((traceq4_occ_kernel<OCC_WPS>), dim3(cfg4.grid_full), dim3(BLOCK), cfg4.lds_t, st, A);
+      } else if (wide) {
+        launch_traceq4_cfg(s, cfg4, t, nullptr, st, nullptr, q.ovf.p);
+      } else {
+        launch_traceq_cfg(s, cfg, t, false, st);
+      }
+      if (t.steal || wide) launch_redo(s, cfg, t, q.ctl.p + TRACE_HEAD_STRIDE + HEAD_SLOT, st); // (its queue length stays on the device)
+      s->n_trace_launches = launches;
+      if (surf) {
+        const DevScene sc = s->dev();
+        if (surf->p5tri)
+          hipLaunchKernelGGL(query_surface_kernel<true>, g1, b1, 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
+                             (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
+        else
+          hipLaunchKernelGGL(query_surface_kernel<false>, g1, b1, 0, st, sc.tri_geom, sc.tri_shade, rays, q.hits.p, t_max,
+                             (uint32_t)n, tri_id, t_hit, surf->point, surf->normal, surf->inside);
+      } else {
+        hipLaunchKernelGGL(query_answer_kernel, g1, b1, 0, st, q.hits.p, t_max, (uint32_t)n, tri_id, t_hit, occluded);
+      }
+      return 0;
+                          });
 }
 int ezrt_query_closest_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int32_t* tri_id, float* t_hit,
                               void* stream) {
@@ -1303,443 +1218,11 @@ int ezrt_query_surface_device(EzrtScene* s, const float* rays_od6, const float* 
                               float* t_hit, float* hit_point, float* normal, uint8_t* inside, void* stream) {
   return ezi::guarded("ezrt_query_surface_device", [&]() -> int {
     if (!s || !rays_od6 || !tri_id || !t_hit || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
-    // the render's choice of the smooth-normal form: P5TRI = INTEG >= 50 (ezrt_kernels.h)
-    bool p5;
-    switch (integrator) {
-    case EZRT_INTEGRATOR_P3_DIFFUSE:
-    case EZRT_INTEGRATOR_P4_DISNEY: p5 = false; break;
-    case EZRT_INTEGRATOR_P5_SOBOL:
-    case EZRT_INTEGRATOR_P5_MIS:
-    case EZRT_INTEGRATOR_P5_MIS_ANISO: p5 = true; break;
-    default: return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
-    }
+    if (!ezi::known_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    const bool p5 = integrator >= EZRT_INTEGRATOR_P5_SOBOL; // the render's choice of the smooth-normal form: P5TRI = INTEG >= 50
     if (n_rays == 0) return 0;
     const SurfaceOut surf{hit_point, normal, inside, p5};
     return query_device_body(s, rays_od6, t_max, n_rays, tri_id, t_hit, nullptr, (hipStream_t)stream, &surf);
-  });
-}
-
-// ---- shading queries on device memory (include/ezrt_shade.h): one kernel each on `st`, no scratch
-} // extern "C"
-// What every call does before and after its launch: the scene's device found and made current (restored on return), every buffer of
-// `bufs` checked to be `bytes` of that device's memory, then launch(), then the event a later refit waits for.
-struct ShadeBuf {
-  const void* p;
-  size_t bytes;
-};
-template <class Launch>
-static int shade_call(EzrtScene* s, std::initializer_list<ShadeBuf> bufs, size_t n, hipStream_t st, Launch&& launch) {
-  hipPointerAttribute_t sat;
-  if (!s->tri_shade.p || hipPointerGetAttributes(&sat, s->tri_shade.p) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(EZRT_ERR_INVALID, "the scene has no device records");
-  }
-  const int dev = sat.device;
-  for (const ShadeBuf& b : bufs)
-    if (b.p && !ezi::device_buffer_of(b.p, b.bytes, dev))
-      return fail(EZRT_ERR_INVALID, "inputs and outputs must be device memory of the scene's device (%d), %zu elements long", dev, n);
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-  } restore{prev};
-  if (dev != prev) HIP_TRY(hipSetDevice(dev));
-  launch(dim3((unsigned)((n + 255) / 256)), dim3(256));
-  HIP_TRY(hipGetLastError());
-  // the end of this call on its stream, after its last read of the per-triangle records: a refit makes its own stream wait for it
-  QueryScratch& q = s->query;
-  if (!q.ev_shade_end) HIP_TRY(hipEventCreateWithFlags(&q.ev_shade_end, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(q.ev_shade_end, st));
-  return 0;
-}
-static bool shade_integrator(int integrator) {
-  return integrator == EZRT_INTEGRATOR_P3_DIFFUSE || integrator == EZRT_INTEGRATOR_P4_DISNEY || integrator == EZRT_INTEGRATOR_P5_SOBOL ||
-         integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO;
-}
-template <int INTEG>
-static void launch_shade_eval(EzrtScene* s, dim3 g, dim3 b, hipStream_t st, const int32_t* tri_id, const float* V, const float* N,
-                              const float* L, int n, float* f_r, float* pdf) {
-  if (pdf)
-    hipLaunchKernelGGL((shade_eval_kernel<INTEG, true>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
-                       (uint32_t)n, f_r, pdf);
-  else
-    hipLaunchKernelGGL((shade_eval_kernel<INTEG, false>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
-                       (uint32_t)n, f_r, pdf);
-}
-extern "C" {
-int ezrt_query_material_device(EzrtScene* s, const int32_t* tri_id, int n, float* mat18, void* stream) {
-  return ezi::guarded("ezrt_query_material_device", [&]() -> int {
-    if (!s || !tri_id || !mat18 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{tri_id, N * sizeof(int32_t)}, {mat18, N * 18 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(shade_material_kernel, g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, (uint32_t)n, mat18);
-    });
-  });
-}
-int ezrt_shade_eval_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* V, const float* N, const float* L, int n,
-                           float* f_r, float* pdf, void* stream) {
-  return ezi::guarded("ezrt_shade_eval_device", [&]() -> int {
-    if (!s || !tri_id || !V || !N || !L || !f_r || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
-    if (n == 0) return 0;
-    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{tri_id, K * sizeof(int32_t)}, {V, v3}, {N, v3}, {L, v3}, {f_r, v3}, {pdf, K * sizeof(float)}}, K, st,
-                      [&](dim3 g, dim3 b) {
-                        switch (integrator) { // the one dispatch: each kernel is compiled for its integrator
-                        case EZRT_INTEGRATOR_P3_DIFFUSE: launch_shade_eval<EZRT_INTEGRATOR_P3_DIFFUSE>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
-                        case EZRT_INTEGRATOR_P4_DISNEY: launch_shade_eval<EZRT_INTEGRATOR_P4_DISNEY>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
-                        case EZRT_INTEGRATOR_P5_SOBOL: launch_shade_eval<EZRT_INTEGRATOR_P5_SOBOL>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
-                        case EZRT_INTEGRATOR_P5_MIS: launch_shade_eval<EZRT_INTEGRATOR_P5_MIS>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
-                        default: launch_shade_eval<EZRT_INTEGRATOR_P5_MIS_ANISO>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); break;
-                        }
-                      });
-  });
-}
-int ezrt_shade_sample_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* xi, const float* V, const float* N, int n,
-                             float* L, void* stream) {
-  return ezi::guarded("ezrt_shade_sample_device", [&]() -> int {
-    if (!s || !tri_id || !xi || !V || !N || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
-    if (n == 0) return 0;
-    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{tri_id, K * sizeof(int32_t)}, {xi, v3}, {V, v3}, {N, v3}, {L, v3}}, K, st, [&](dim3 g, dim3 b) {
-      const float4 *ts = s->tri_shade.p, *mt = s->mat_table.p;
-      const int32_t nt = (int32_t)s->n_tri;
-      if (integrator == EZRT_INTEGRATOR_P5_MIS)
-        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
-      else if (integrator == EZRT_INTEGRATOR_P5_MIS_ANISO)
-        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
-      else // 3, 4 and 50 continue in the same direction: the uniform hemisphere about N
-        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_SOBOL>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
-    });
-  });
-}
-int ezrt_env_eval_device(EzrtScene* s, const float* L, int n, float env_clamp, float* colour, float* pdf, void* stream) {
-  return ezi::guarded("ezrt_env_eval_device", [&]() -> int {
-    if (!s || !L || (!colour && !pdf) || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument (one of colour and pdf is required) or n < 0");
-    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
-    if (pdf && !s->has_cache) return fail(EZRT_ERR_INVALID, "the pdf needs the env cache (ezrt_scene_set_env)");
-    if (n == 0) return 0;
-    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{L, v3}, {colour, v3}, {pdf, K * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
-      const DevScene sc = s->dev();
-      if (colour && pdf) hipLaunchKernelGGL((env_eval_kernel<true, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
-      else if (colour) hipLaunchKernelGGL((env_eval_kernel<true, false>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
-      else hipLaunchKernelGGL((env_eval_kernel<false, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
-    });
-  });
-}
-int ezrt_env_sample_device(EzrtScene* s, const float* xi, int n, float* L, void* stream) {
-  return ezi::guarded("ezrt_env_sample_device", [&]() -> int {
-    if (!s || !xi || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
-    if (!s->has_cache) return fail(EZRT_ERR_INVALID, "sampling needs the env cache (ezrt_scene_set_env)");
-    if (n == 0) return 0;
-    const size_t K = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{xi, K * 2 * sizeof(float)}, {L, K * 3 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(env_sample_kernel, g, b, 0, st, s->dev(), xi, (uint32_t)n, L);
-    });
-  });
-}
-
-// ---- path queries on device memory (include/ezrt_path.h): one kernel each on `st`, no scratch; checked, launched and ordered
-// against a refit by shade_call
-int ezrt_camera_rays_device(EzrtScene* s, const EzrtRenderParams* p, const uint32_t* sample_xyf, int n, float* rays_od6, void* stream) {
-  return ezi::guarded("ezrt_camera_rays_device", [&]() -> int {
-    if (!s || !sample_xyf || !rays_od6 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!p) return fail(EZRT_ERR_INVALID, "params is NULL");
-    if (p->width <= 0 || p->height <= 0) return fail(EZRT_ERR_INVALID, "width/height must be positive");
-    if (n == 0) return 0;
-    const size_t K = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{sample_xyf, K * 3 * sizeof(uint32_t)}, {rays_od6, K * 6 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(camera_rays_kernel, g, b, 0, st, *p, sample_xyf, (uint32_t)n, rays_od6);
-    });
-  });
-}
-int ezrt_query_radiance_device(EzrtScene* s, int integrator, int max_bounce, float env_clamp, const float* rays_od6,
-                               const uint32_t* sample_xyf, int n, float* radiance, void* stream) {
-  return ezi::guarded("ezrt_query_radiance_device", [&]() -> int {
-    if (!s || !rays_od6 || !sample_xyf || !radiance || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    // (the states a render call rejects, in its words: validate_params)
-    if (max_bounce < 0 || max_bounce > 64) return fail(EZRT_ERR_INVALID, "max_bounce out of range [0,64]");
-    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator");
-    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
-    if ((integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO) && !s->has_cache)
-      return fail(EZRT_ERR_INVALID, "integrator 51 needs the env cache (ezrt_scene_set_env)");
-    if (n == 0) return 0;
-    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{rays_od6, 2 * v3}, {sample_xyf, K * 3 * sizeof(uint32_t)}, {radiance, v3}}, K, st, [&](dim3 g, dim3 b) {
-      RadianceArgs a;
-      a.sc = s->dev();
-      a.rays = rays_od6;
-      a.xyf = sample_xyf;
-      a.n = (uint32_t)n;
-      a.max_bounce = max_bounce;
-      a.env_clamp = env_clamp;
-      a.radiance = radiance;
-      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
-      switch (integrator) { // the one dispatch: each kernel is compiled for its integrator
-      case EZRT_INTEGRATOR_P3_DIFFUSE: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P3_DIFFUSE>, g, b, lds, st, a); break;
-      case EZRT_INTEGRATOR_P4_DISNEY: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P4_DISNEY>, g, b, lds, st, a); break;
-      case EZRT_INTEGRATOR_P5_SOBOL: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_SOBOL>, g, b, lds, st, a); break;
-      case EZRT_INTEGRATOR_P5_MIS: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, lds, st, a); break;
-      default: hipLaunchKernelGGL(radiance_query_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, lds, st, a); break;
-      }
-    });
-  });
-}
-
-// ---- all-hits queries on device memory (include/ezrt_multihit.h): one kernel each on `st`, no scratch (a ray's sorted list is kept
-// in its own output row); checked, launched and ordered against a refit by shade_call
-int ezrt_query_all_hits_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int max_hits, int32_t* tri_id,
-                               float* t_hit, int32_t* n_hits, void* stream) {
-  return ezi::guarded("ezrt_query_all_hits_device", [&]() -> int {
-    if (!s || !rays_od6 || !tri_id || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
-    if (max_hits < 1 || max_hits > EZRT_ALL_HITS_MAX) return fail(EZRT_ERR_INVALID, "max_hits out of range [1,%d]", EZRT_ALL_HITS_MAX);
-    if (n_rays == 0) return 0;
-    const size_t N = (size_t)n_rays, K = (size_t)max_hits;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{rays_od6, N * 6 * sizeof(float)}, {t_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {t_hit, N * K * sizeof(float)}, {n_hits, N * sizeof(int32_t)}}, N, st, [&](dim3 g, dim3 b) {
-      AllHitsArgs a;
-      a.sc = s->dev();
-      a.rays = rays_od6;
-      a.t_max = t_max;
-      a.n = (uint32_t)n_rays;
-      a.K = max_hits;
-      a.div_k = make_fastdiv((uint32_t)max_hits);
-      a.tri = tri_id;
-      a.t = t_hit;
-      a.n_hits = n_hits;
-      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
-      if (t_hit) hipLaunchKernelGGL(all_hits_kernel<true>, g, b, lds, st, a);
-      else hipLaunchKernelGGL(all_hits_kernel<false>, g, b, lds, st, a);
-    });
-  });
-}
-int ezrt_surface_at_device(EzrtScene* s, const float* rays_od6, const int32_t* tri_id, const float* t_hit, int n, int integrator,
-                           float* hit_point, float* normal, uint8_t* inside, void* stream) {
-  return ezi::guarded("ezrt_surface_at_device", [&]() -> int {
-    if (!s || !rays_od6 || !tri_id || !t_hit || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!hit_point && !normal && !inside) return fail(EZRT_ERR_INVALID, "one of hit_point, normal and inside is required");
-    if (!shade_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
-    if (n == 0) return 0;
-    const bool p5 = integrator >= EZRT_INTEGRATOR_P5_SOBOL; // the render's choice of the smooth-normal form, as ezrt_query_surface_device
-    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{rays_od6, 2 * v3}, {tri_id, K * sizeof(int32_t)}, {t_hit, K * sizeof(float)}, {hit_point, v3}, {normal, v3},
-                          {inside, K}}, K, st, [&](dim3 g, dim3 b) {
-      const DevScene sc = s->dev();
-      if (p5)
-        hipLaunchKernelGGL(surface_at_kernel<true>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
-                           (uint32_t)n, hit_point, normal, inside);
-      else
-        hipLaunchKernelGGL(surface_at_kernel<false>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
-                           (uint32_t)n, hit_point, normal, inside);
-    });
-  });
-}
-
-// ---- point queries on device memory: what their kernels read of the scene, and the route of this call -- chosen per call: a refit
-// can change whether the scene prunes.  lds = the lane's stack column of the best-first walk (ezrt_point_queries.h: point_walk):
-// {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that the column exceeds the 64 KiB of a launch without opt-in
-// (> 126 entries; none of the builders comes near) is swept instead, as is a scene that does not prune.
-struct PointRoute {
-  bool walk;
-  size_t lds;
-};
-static PointRoute point_scene(const EzrtScene* s, PointScene& sc) {
-  sc.tri_geom = s->tri_geom.p;
-  sc.inner4 = s->inner4.p;
-  sc.uncovered = s->cp_uncovered.p;
-  sc.n_uncovered = s->n_cp_uncovered;
-  sc.n_tri = s->n_tri;
-  const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
-  return {s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024, lds};
-}
-
-// ---- closest-point queries on device memory (include/ezrt_closest_point.h): one kernel on `st`, no scratch; checked, launched and
-// ordered against a refit by shade_call.
-int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const float* d_max, int n, int32_t* tri_id, float* point,
-                                    float* dist, float* bary, void* stream) {
-  return ezi::guarded("ezrt_query_closest_point_device", [&]() -> int {
-    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
-                          {point, N * 3 * sizeof(float)}, {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3, dim3) {
-      ClosestPointArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.points = points3;
-      a.d_max = d_max;
-      a.n = (uint32_t)n;
-      a.tri = tri_id;
-      a.point = point;
-      a.dist = dist;
-      a.bary = bary;
-      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      if (r.walk) hipLaunchKernelGGL(closest_point_kernel<true>, g, b, r.lds, st, a);
-      else hipLaunchKernelGGL(closest_point_kernel<false>, g, b, 0, st, a);
-    });
-  });
-}
-
-// ---- nearest-K queries on device memory (include/ezrt_nearest.h): one kernel each on `st`, no scratch (a point's sorted list is kept
-// in its own output rows); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene;
-// n_within selects the counting instance, which cannot shrink its radius below d_max.
-int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d_max, int n, int max_k, int32_t* tri_id, float* dist,
-                              int32_t* n_within, void* stream) {
-  return ezi::guarded("ezrt_query_nearest_device", [&]() -> int {
-    if (!s || !points3 || !tri_id || !dist || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 1 || max_k > EZRT_NEAREST_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [1,%d]", EZRT_NEAREST_MAX);
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {dist, N * K * sizeof(float)}, {n_within, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      NearestArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.points = points3;
-      a.d_max = d_max;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)max_k);
-      a.tri = tri_id;
-      a.dist = dist;
-      a.n_within = n_within;
-      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      if (r.walk) {
-        if (n_within) hipLaunchKernelGGL((nearest_kernel<true, true>), g, b, r.lds, st, a);
-        else hipLaunchKernelGGL((nearest_kernel<true, false>), g, b, r.lds, st, a);
-      } else {
-        if (n_within) hipLaunchKernelGGL((nearest_kernel<false, true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((nearest_kernel<false, false>), g, b, 0, st, a);
-      }
-    });
-  });
-}
-int ezrt_closest_point_at_device(EzrtScene* s, const float* points3, const int32_t* tri_id, int n, float* point, float* dist, float* bary,
-                                 void* stream) {
-  return ezi::guarded("ezrt_closest_point_at_device", [&]() -> int {
-    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!point && !dist && !bary) return fail(EZRT_ERR_INVALID, "one of point, dist and bary is required");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {point, N * 3 * sizeof(float)},
-                          {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(closest_point_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, point, dist,
-                         bary);
-    });
-  });
-}
-
-// ---- inside and signed-distance queries on device memory (include/ezrt_inside.h): one kernel each on `st`, no scratch; checked,
-// launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene.
-int ezrt_query_inside_device(EzrtScene* s, const float* points3, int n, int axis, uint8_t* inside, int32_t* crossings, void* stream) {
-  return ezi::guarded("ezrt_query_inside_device", [&]() -> int {
-    if (!s || !points3 || !inside || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {inside, N}, {crossings, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      InsideArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.points = points3;
-      a.n = (uint32_t)n;
-      a.axis = axis;
-      a.inside = inside;
-      a.crossings = crossings;
-      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // this walk's entries are bare references, one row each: half of the column that decides the route
-      if (r.walk) hipLaunchKernelGGL(inside_kernel<true>, g, b, r.lds / 2, st, a);
-      else hipLaunchKernelGGL(inside_kernel<false>, g, b, 0, st, a);
-    });
-  });
-}
-int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const float* d_max, int n, int axis, int32_t* tri_id,
-                                      float* point, float* sdist, float* bary, uint8_t* inside, void* stream) {
-  return ezi::guarded("ezrt_query_signed_distance_device", [&]() -> int {
-    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
-                          {point, N * 3 * sizeof(float)}, {sdist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}, {inside, N}}, N, st,
-                      [&](dim3, dim3) {
-      SignedDistanceArgs a;
-      const PointRoute r = point_scene(s, a.cp.sc);
-      a.cp.points = points3;
-      a.cp.d_max = d_max;
-      a.cp.n = (uint32_t)n;
-      a.cp.tri = tri_id;
-      a.cp.point = point;
-      a.cp.dist = sdist;
-      a.cp.bary = bary;
-      a.axis = axis;
-      a.inside = inside;
-      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // the crossing walk runs first, on the same column
-      if (r.walk) hipLaunchKernelGGL(signed_distance_kernel<true>, g, b, r.lds, st, a);
-      else hipLaunchKernelGGL(signed_distance_kernel<false>, g, b, 0, st, a);
-    });
-  });
-}
-
-// ---- box-overlap queries on device memory (include/ezrt_box_overlap.h): one kernel each on `st`, no scratch (a box's list is kept in
-// its own output row); checked, launched and ordered against a refit by shade_call.  The route is chosen per call, by point_scene.
-int ezrt_query_box_overlap_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, int n, int max_k, int32_t* tri_id,
-                                  int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_box_overlap_device", [&]() -> int {
-    if (!s || !box_lo3 || !box_hi3 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 0 || max_k > EZRT_BOX_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_BOX_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      BoxOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.lo = box_lo3;
-      a.hi = box_hi3;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      const dim3 g((unsigned)((N + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
-      // this walk's entries are bare references, one row each: half of the column that decides the route
-      if (r.walk) hipLaunchKernelGGL(box_overlap_kernel<true>, g, b, r.lds / 2, st, a);
-      else hipLaunchKernelGGL(box_overlap_kernel<false>, g, b, 0, st, a);
-    });
-  });
-}
-int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, const int32_t* tri_id, int n, uint8_t* overlaps,
-                               void* stream) {
-  return ezi::guarded("ezrt_box_overlap_at_device", [&]() -> int {
-    if (!s || !box_lo3 || !box_hi3 || !tri_id || !overlaps || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return shade_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
-                      st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(box_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, box_lo3, box_hi3, tri_id, (uint32_t)n, overlaps);
-    });
   });
 }
 

@@ -1,6 +1,6 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap queries
-// (include/ezrt_box_overlap.h).  One query point or box per lane, a workgroup of one wave.
+// (include/ezrt_box_overlap.h).  One query point or box per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest and signed distance share
 //   closest_point_kernel<WALK>       closest_point_search + closest_point_store
@@ -17,7 +17,7 @@
 
 namespace ezd {
 
-// What every point query reads of the scene (ezrt_launch.hip: point_scene fills it and chooses the route).
+// What every point query reads of the scene (ezrt_queries.hip: point_scene fills it and chooses the route).
 struct PointScene {
   const float4* tri_geom;
   const float4* inner4;     // WALK: the 4-wide records, record 0 the root

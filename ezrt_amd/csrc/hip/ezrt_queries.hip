@@ -1,0 +1,398 @@
+// ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
+// (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
+// nearest-K, inside / signed-distance and box-overlap queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h,
+// ezrt_box_overlap.h).  A translation unit of its own: none of its kernels is compiled together with the render pipeline's
+// (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run the pipeline's trace kernels
+// (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
+#include "ezrt_internal.h"
+#include "ezrt_shade.h"
+#include "ezrt_path.h"
+#include "ezrt_multihit.h"
+#include "ezrt_closest_point.h"
+#include "ezrt_inside.h"
+#include "ezrt_nearest.h"
+#include "ezrt_box_overlap.h"
+#include "ezrt_query_kernels.h"
+#include "ezrt_point_queries.h"
+
+using ezi::known_integrator;
+using ezi::stack_lds_bytes;
+
+// Every call here goes through ezi::device_call: buffers checked against the scene's device, launch(grid, block), then the event of
+// the scratch-free queries (QueryScratch::ev_shade_end), which a later refit waits for.
+template <class Launch>
+static int query_call(EzrtScene* s, std::initializer_list<ezi::DeviceBuf> bufs, size_t n, hipStream_t st, Launch&& launch) {
+  return ezi::device_call(s, s->tri_shade.p, bufs, n, "inputs and outputs", "elements", &QueryScratch::ev_shade_end, st, launch);
+}
+
+template <int INTEG>
+static void launch_shade_eval(EzrtScene* s, dim3 g, dim3 b, hipStream_t st, const int32_t* tri_id, const float* V, const float* N,
+                              const float* L, int n, float* f_r, float* pdf) {
+  if (pdf)
+    hipLaunchKernelGGL((shade_eval_kernel<INTEG, true>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
+                       (uint32_t)n, f_r, pdf);
+  else
+    hipLaunchKernelGGL((shade_eval_kernel<INTEG, false>), g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, V, N, L,
+                       (uint32_t)n, f_r, pdf);
+}
+// ---- point queries on device memory: what their kernels read of the scene, and the route of this call -- chosen per call: a refit
+// can change whether the scene prunes.  lds = the lane's stack column of the best-first walk (ezrt_point_queries.h: point_walk):
+// {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that the column exceeds the 64 KiB of a launch without opt-in
+// (> 126 entries; none of the builders comes near) is swept instead, as is a scene that does not prune.
+struct PointRoute {
+  bool walk;
+  size_t lds;
+};
+static PointRoute point_scene(const EzrtScene* s, PointScene& sc) {
+  sc.tri_geom = s->tri_geom.p;
+  sc.inner4 = s->inner4.p;
+  sc.uncovered = s->cp_uncovered.p;
+  sc.n_uncovered = s->n_cp_uncovered;
+  sc.n_tri = s->n_tri;
+  const size_t lds = ((size_t)s->stack_need_cp + 1) * 2 * CP_BLOCK * sizeof(int);
+  return {s->prunable && s->n_inner4 > 0 && lds <= 64 * 1024, lds};
+}
+// the launch of a routed kernel for n points or boxes, CP_BLOCK per workgroup: the walking instance on `lds` bytes of stack column, or
+// the sweeping one
+template <class Args>
+static void launch_routed(void (*walk)(Args), void (*sweep)(Args), const PointRoute& r, size_t lds, size_t n, hipStream_t st, const Args& a) {
+  const dim3 g((unsigned)((n + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
+  if (r.walk) hipLaunchKernelGGL(walk, g, b, lds, st, a);
+  else hipLaunchKernelGGL(sweep, g, b, 0, st, a);
+}
+
+extern "C" {
+// ---- shading queries on device memory (include/ezrt_shade.h)
+int ezrt_query_material_device(EzrtScene* s, const int32_t* tri_id, int n, float* mat18, void* stream) {
+  return ezi::guarded("ezrt_query_material_device", [&]() -> int {
+    if (!s || !tri_id || !mat18 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri_id, N * sizeof(int32_t)}, {mat18, N * 18 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(shade_material_kernel, g, b, 0, st, s->tri_shade.p, s->mat_table.p, (int32_t)s->n_tri, tri_id, (uint32_t)n, mat18);
+    });
+  });
+}
+int ezrt_shade_eval_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* V, const float* N, const float* L, int n,
+                           float* f_r, float* pdf, void* stream) {
+  return ezi::guarded("ezrt_shade_eval_device", [&]() -> int {
+    if (!s || !tri_id || !V || !N || !L || !f_r || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!known_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri_id, K * sizeof(int32_t)}, {V, v3}, {N, v3}, {L, v3}, {f_r, v3}, {pdf, K * sizeof(float)}}, K, st,
+                      [&](dim3 g, dim3 b) { // each kernel is compiled for its integrator
+                        ezi::with_integrator(integrator, [&](auto I) { launch_shade_eval<decltype(I)::value>(s, g, b, st, tri_id, V, N, L, n, f_r, pdf); });
+                      });
+  });
+}
+int ezrt_shade_sample_device(EzrtScene* s, int integrator, const int32_t* tri_id, const float* xi, const float* V, const float* N, int n,
+                             float* L, void* stream) {
+  return ezi::guarded("ezrt_shade_sample_device", [&]() -> int {
+    if (!s || !tri_id || !xi || !V || !N || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!known_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri_id, K * sizeof(int32_t)}, {xi, v3}, {V, v3}, {N, v3}, {L, v3}}, K, st, [&](dim3 g, dim3 b) {
+      const float4 *ts = s->tri_shade.p, *mt = s->mat_table.p;
+      const int32_t nt = (int32_t)s->n_tri;
+      if (integrator == EZRT_INTEGRATOR_P5_MIS)
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+      else if (integrator == EZRT_INTEGRATOR_P5_MIS_ANISO)
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_MIS_ANISO>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+      else // 3, 4 and 50 continue in the same direction: the uniform hemisphere about N
+        hipLaunchKernelGGL(shade_sample_kernel<EZRT_INTEGRATOR_P5_SOBOL>, g, b, 0, st, ts, mt, nt, tri_id, xi, V, N, (uint32_t)n, L);
+    });
+  });
+}
+int ezrt_env_eval_device(EzrtScene* s, const float* L, int n, float env_clamp, float* colour, float* pdf, void* stream) {
+  return ezi::guarded("ezrt_env_eval_device", [&]() -> int {
+    if (!s || !L || (!colour && !pdf) || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument (one of colour and pdf is required) or n < 0");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if (pdf && !s->has_cache) return fail(EZRT_ERR_INVALID, "the pdf needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{L, v3}, {colour, v3}, {pdf, K * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      const DevScene sc = s->dev();
+      if (colour && pdf) hipLaunchKernelGGL((env_eval_kernel<true, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+      else if (colour) hipLaunchKernelGGL((env_eval_kernel<true, false>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+      else hipLaunchKernelGGL((env_eval_kernel<false, true>), g, b, 0, st, sc, L, (uint32_t)n, env_clamp, colour, pdf);
+    });
+  });
+}
+int ezrt_env_sample_device(EzrtScene* s, const float* xi, int n, float* L, void* stream) {
+  return ezi::guarded("ezrt_env_sample_device", [&]() -> int {
+    if (!s || !xi || !L || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if (!s->has_cache) return fail(EZRT_ERR_INVALID, "sampling needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{xi, K * 2 * sizeof(float)}, {L, K * 3 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(env_sample_kernel, g, b, 0, st, s->dev(), xi, (uint32_t)n, L);
+    });
+  });
+}
+
+// ---- path queries on device memory (include/ezrt_path.h): one kernel each on `st`, no scratch; checked, launched and ordered
+// against a refit by query_call
+int ezrt_camera_rays_device(EzrtScene* s, const EzrtRenderParams* p, const uint32_t* sample_xyf, int n, float* rays_od6, void* stream) {
+  return ezi::guarded("ezrt_camera_rays_device", [&]() -> int {
+    if (!s || !sample_xyf || !rays_od6 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!p) return fail(EZRT_ERR_INVALID, "params is NULL");
+    if (p->width <= 0 || p->height <= 0) return fail(EZRT_ERR_INVALID, "width/height must be positive");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{sample_xyf, K * 3 * sizeof(uint32_t)}, {rays_od6, K * 6 * sizeof(float)}}, K, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(camera_rays_kernel, g, b, 0, st, *p, sample_xyf, (uint32_t)n, rays_od6);
+    });
+  });
+}
+int ezrt_query_radiance_device(EzrtScene* s, int integrator, int max_bounce, float env_clamp, const float* rays_od6,
+                               const uint32_t* sample_xyf, int n, float* radiance, void* stream) {
+  return ezi::guarded("ezrt_query_radiance_device", [&]() -> int {
+    if (!s || !rays_od6 || !sample_xyf || !radiance || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    // (the states a render call rejects, in its words: validate_params)
+    if (max_bounce < 0 || max_bounce > 64) return fail(EZRT_ERR_INVALID, "max_bounce out of range [0,64]");
+    if (!known_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator");
+    if (!s->hdr.p) return fail(EZRT_ERR_INVALID, "the scene has no environment (ezrt_scene_set_env)");
+    if ((integrator == EZRT_INTEGRATOR_P5_MIS || integrator == EZRT_INTEGRATOR_P5_MIS_ANISO) && !s->has_cache)
+      return fail(EZRT_ERR_INVALID, "integrator 51 needs the env cache (ezrt_scene_set_env)");
+    if (n == 0) return 0;
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{rays_od6, 2 * v3}, {sample_xyf, K * 3 * sizeof(uint32_t)}, {radiance, v3}}, K, st, [&](dim3 g, dim3 b) {
+      RadianceArgs a;
+      a.sc = s->dev();
+      a.rays = rays_od6;
+      a.xyf = sample_xyf;
+      a.n = (uint32_t)n;
+      a.max_bounce = max_bounce;
+      a.env_clamp = env_clamp;
+      a.radiance = radiance;
+      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
+      // each kernel is compiled for its integrator
+      ezi::with_integrator(integrator, [&](auto I) { hipLaunchKernelGGL(radiance_query_kernel<decltype(I)::value>, g, b, lds, st, a); });
+    });
+  });
+}
+
+// ---- all-hits queries on device memory (include/ezrt_multihit.h): one kernel each on `st`, no scratch (a ray's sorted list is kept
+// in its own output row); checked, launched and ordered against a refit by query_call
+int ezrt_query_all_hits_device(EzrtScene* s, const float* rays_od6, const float* t_max, int n_rays, int max_hits, int32_t* tri_id,
+                               float* t_hit, int32_t* n_hits, void* stream) {
+  return ezi::guarded("ezrt_query_all_hits_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || n_rays < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n_rays < 0");
+    if (max_hits < 1 || max_hits > EZRT_ALL_HITS_MAX) return fail(EZRT_ERR_INVALID, "max_hits out of range [1,%d]", EZRT_ALL_HITS_MAX);
+    if (n_rays == 0) return 0;
+    const size_t N = (size_t)n_rays, K = (size_t)max_hits;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{rays_od6, N * 6 * sizeof(float)}, {t_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {t_hit, N * K * sizeof(float)}, {n_hits, N * sizeof(int32_t)}}, N, st, [&](dim3 g, dim3 b) {
+      AllHitsArgs a;
+      a.sc = s->dev();
+      a.rays = rays_od6;
+      a.t_max = t_max;
+      a.n = (uint32_t)n_rays;
+      a.K = max_hits;
+      a.div_k = make_fastdiv((uint32_t)max_hits);
+      a.tri = tri_id;
+      a.t = t_hit;
+      a.n_hits = n_hits;
+      const size_t lds = stack_lds_bytes(s); // the traversal stack of the megakernel launch: s->depth entries per lane
+      if (t_hit) hipLaunchKernelGGL(all_hits_kernel<true>, g, b, lds, st, a);
+      else hipLaunchKernelGGL(all_hits_kernel<false>, g, b, lds, st, a);
+    });
+  });
+}
+int ezrt_surface_at_device(EzrtScene* s, const float* rays_od6, const int32_t* tri_id, const float* t_hit, int n, int integrator,
+                           float* hit_point, float* normal, uint8_t* inside, void* stream) {
+  return ezi::guarded("ezrt_surface_at_device", [&]() -> int {
+    if (!s || !rays_od6 || !tri_id || !t_hit || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!hit_point && !normal && !inside) return fail(EZRT_ERR_INVALID, "one of hit_point, normal and inside is required");
+    if (!known_integrator(integrator)) return fail(EZRT_ERR_INVALID, "unknown integrator %d", integrator);
+    if (n == 0) return 0;
+    const bool p5 = integrator >= EZRT_INTEGRATOR_P5_SOBOL; // the render's choice of the smooth-normal form, as ezrt_query_surface_device
+    const size_t K = (size_t)n, v3 = K * 3 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{rays_od6, 2 * v3}, {tri_id, K * sizeof(int32_t)}, {t_hit, K * sizeof(float)}, {hit_point, v3}, {normal, v3},
+                          {inside, K}}, K, st, [&](dim3 g, dim3 b) {
+      const DevScene sc = s->dev();
+      if (p5)
+        hipLaunchKernelGGL(surface_at_kernel<true>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
+                           (uint32_t)n, hit_point, normal, inside);
+      else
+        hipLaunchKernelGGL(surface_at_kernel<false>, g, b, 0, st, sc.tri_geom, sc.tri_shade, (int32_t)s->n_tri, rays_od6, tri_id, t_hit,
+                           (uint32_t)n, hit_point, normal, inside);
+    });
+  });
+}
+
+// ---- closest-point queries on device memory (include/ezrt_closest_point.h): one kernel on `st`, no scratch; checked, launched and
+// ordered against a refit by query_call.
+int ezrt_query_closest_point_device(EzrtScene* s, const float* points3, const float* d_max, int n, int32_t* tri_id, float* point,
+                                    float* dist, float* bary, void* stream) {
+  return ezi::guarded("ezrt_query_closest_point_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
+                          {point, N * 3 * sizeof(float)}, {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3, dim3) {
+      ClosestPointArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.points = points3;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.tri = tri_id;
+      a.point = point;
+      a.dist = dist;
+      a.bary = bary;
+      launch_routed(closest_point_kernel<true>, closest_point_kernel<false>, r, r.lds, N, st, a);
+    });
+  });
+}
+
+// ---- nearest-K queries on device memory (include/ezrt_nearest.h): one kernel each on `st`, no scratch (a point's sorted list is kept
+// in its own output rows); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene;
+// n_within selects the counting instance, which cannot shrink its radius below d_max.
+int ezrt_query_nearest_device(EzrtScene* s, const float* points3, const float* d_max, int n, int max_k, int32_t* tri_id, float* dist,
+                              int32_t* n_within, void* stream) {
+  return ezi::guarded("ezrt_query_nearest_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || !dist || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 1 || max_k > EZRT_NEAREST_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [1,%d]", EZRT_NEAREST_MAX);
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {dist, N * K * sizeof(float)}, {n_within, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      NearestArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.points = points3;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)max_k);
+      a.tri = tri_id;
+      a.dist = dist;
+      a.n_within = n_within;
+      if (n_within) launch_routed(nearest_kernel<true, true>, nearest_kernel<false, true>, r, r.lds, N, st, a);
+      else launch_routed(nearest_kernel<true, false>, nearest_kernel<false, false>, r, r.lds, N, st, a);
+    });
+  });
+}
+int ezrt_closest_point_at_device(EzrtScene* s, const float* points3, const int32_t* tri_id, int n, float* point, float* dist, float* bary,
+                                 void* stream) {
+  return ezi::guarded("ezrt_closest_point_at_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!point && !dist && !bary) return fail(EZRT_ERR_INVALID, "one of point, dist and bary is required");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {point, N * 3 * sizeof(float)},
+                          {dist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(closest_point_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, point, dist,
+                         bary);
+    });
+  });
+}
+
+// ---- inside and signed-distance queries on device memory (include/ezrt_inside.h): one kernel each on `st`, no scratch; checked,
+// launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_inside_device(EzrtScene* s, const float* points3, int n, int axis, uint8_t* inside, int32_t* crossings, void* stream) {
+  return ezi::guarded("ezrt_query_inside_device", [&]() -> int {
+    if (!s || !points3 || !inside || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {inside, N}, {crossings, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      InsideArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.points = points3;
+      a.n = (uint32_t)n;
+      a.axis = axis;
+      a.inside = inside;
+      a.crossings = crossings;
+      // this walk's entries are bare references, one row each: half of the column that decides the route
+      launch_routed(inside_kernel<true>, inside_kernel<false>, r, r.lds / 2, N, st, a);
+    });
+  });
+}
+int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const float* d_max, int n, int axis, int32_t* tri_id,
+                                      float* point, float* sdist, float* bary, uint8_t* inside, void* stream) {
+  return ezi::guarded("ezrt_query_signed_distance_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (axis < 0 || axis > 5) return fail(EZRT_ERR_INVALID, "axis out of range [0,5]");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
+                          {point, N * 3 * sizeof(float)}, {sdist, N * sizeof(float)}, {bary, N * 2 * sizeof(float)}, {inside, N}}, N, st,
+                      [&](dim3, dim3) {
+      SignedDistanceArgs a;
+      const PointRoute r = point_scene(s, a.cp.sc);
+      a.cp.points = points3;
+      a.cp.d_max = d_max;
+      a.cp.n = (uint32_t)n;
+      a.cp.tri = tri_id;
+      a.cp.point = point;
+      a.cp.dist = sdist;
+      a.cp.bary = bary;
+      a.axis = axis;
+      a.inside = inside;
+      // the crossing walk runs first, on the same column
+      launch_routed(signed_distance_kernel<true>, signed_distance_kernel<false>, r, r.lds, N, st, a);
+    });
+  });
+}
+
+// ---- box-overlap queries on device memory (include/ezrt_box_overlap.h): one kernel each on `st`, no scratch (a box's list is kept in
+// its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_box_overlap_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, int n, int max_k, int32_t* tri_id,
+                                  int32_t* n_overlap, void* stream) {
+  return ezi::guarded("ezrt_query_box_overlap_device", [&]() -> int {
+    if (!s || !box_lo3 || !box_hi3 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 0 || max_k > EZRT_BOX_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_BOX_OVERLAP_MAX);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      BoxOverlapArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.lo = box_lo3;
+      a.hi = box_hi3;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      // this walk's entries are bare references, one row each: half of the column that decides the route
+      launch_routed(box_overlap_kernel<true>, box_overlap_kernel<false>, r, r.lds / 2, N, st, a);
+    });
+  });
+}
+int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, const int32_t* tri_id, int n, uint8_t* overlaps,
+                               void* stream) {
+  return ezi::guarded("ezrt_box_overlap_at_device", [&]() -> int {
+    if (!s || !box_lo3 || !box_hi3 || !tri_id || !overlaps || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
+                      st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(box_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, box_lo3, box_hi3, tri_id, (uint32_t)n, overlaps);
+    });
+  });
+}
+
+} // extern "C"

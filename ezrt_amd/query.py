@@ -60,31 +60,57 @@ def _check(scene, rays, t_max):
     return lib, _check_rays(rays, t_max)
 
 
+def _tensor(name, x, dtype, shape=None, last=None, device=None, max_numel=None):
+    """x, after the checks every entry point makes of a tensor operand, in this order: a GPU tensor, of `dtype`, on `device`, of
+    `shape` or with `last` as its last dimension, contiguous, of at most `max_numel` elements.  (shade.py and path.py use it too.)"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise TypeError("%s must be a GPU tensor" % name)
+    if x.dtype != dtype:
+        raise TypeError("%s must be %s, not %s" % (name, str(dtype).replace("torch.", ""), x.dtype))
+    if device is not None and x.device != device:
+        raise ValueError("%s is on %s, not on %s" % (name, x.device, device))
+    if shape is not None and tuple(x.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, not %s" % (name, tuple(shape), tuple(x.shape)))
+    if last is not None and (x.dim() < 1 or x.shape[-1] != last):
+        raise ValueError("%s must have shape [..., %d], not %s" % (name, last, tuple(x.shape)))
+    if not x.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if max_numel is not None and x.numel() > max_numel:
+        raise ValueError("at most 2^31 - 1 floats per tensor and call")
+    return x
+
+
+def _count(x, width, what):
+    """The number of rows of `width` numbers in x: what the C ABI takes as an int."""
+    n = x.numel() // width
+    if n > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 %s per call" % what)
+    return n
+
+
 def _check_rays(rays, t_max):
     """The number of rays, after the checks every query makes of its rays and t_max."""
-    if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
-        raise TypeError("rays must be a GPU tensor")
-    if rays.dtype != torch.float32:
-        raise TypeError("rays must be float32, not %s" % rays.dtype)
-    if rays.dim() < 1 or rays.shape[-1] != 6:
-        raise ValueError("rays must have shape [..., 6], not %s" % (tuple(rays.shape),))
-    if not rays.is_contiguous():
-        raise ValueError("rays must be contiguous")
+    _tensor("rays", rays, torch.float32, last=6)
     if t_max is not None:
-        if not isinstance(t_max, torch.Tensor) or not t_max.is_cuda:
-            raise TypeError("t_max must be a GPU tensor")
-        if t_max.dtype != torch.float32:
-            raise TypeError("t_max must be float32, not %s" % t_max.dtype)
-        if t_max.device != rays.device:
-            raise ValueError("t_max is on %s, the rays on %s" % (t_max.device, rays.device))
-        if tuple(t_max.shape) != tuple(rays.shape[:-1]):
-            raise ValueError("t_max must have shape %s, not %s" % (tuple(rays.shape[:-1]), tuple(t_max.shape)))
-        if not t_max.is_contiguous():
-            raise ValueError("t_max must be contiguous")
-    n = rays.numel() // 6
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 rays per call")
-    return n
+        _tensor("t_max", t_max, torch.float32, rays.shape[:-1], device=rays.device)
+    return _count(rays, 6, "rays")
+
+
+def _row_shape(tri, lead):
+    """tri.shape, which must be `lead` -- one entry per ray, point or box -- or `lead` and one trailing dimension more: a row each."""
+    shape = tuple(tri.shape)
+    if shape != lead and shape[:-1] != lead:
+        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
+    return shape
+
+
+def _per_entry(x, lead, shape, h, ts):
+    """x [lead + (w,)] as one operand per entry of tri [shape]: x itself, or where a row has entries of its own a copy that repeats
+    x's row for each of them, made on the query's own stream."""
+    if shape == lead:
+        return x
+    with torch.cuda.stream(ts if ts is not None else torch.cuda.ExternalStream(h, device=x.device)):
+        return x.unsqueeze(-2).expand(lead + (shape[-1], x.shape[-1])).contiguous()
 
 
 def _stream(rays, stream):
@@ -204,34 +230,19 @@ def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=
     if integrator not in _SURFACE_INTEGRATORS:
         raise ValueError("integrator must be one of %s, not %r" % (_SURFACE_INTEGRATORS, integrator))
     lead = tuple(rays.shape[:-1])
-    for name, x, dtype in (("tri", tri, torch.int32), ("t", t, torch.float32)):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise TypeError("%s must be a GPU tensor" % name)
-        if x.dtype != dtype:
-            raise TypeError("%s must be %s, not %s" % (name, str(dtype).replace("torch.", ""), x.dtype))
-        if x.device != rays.device:
-            raise ValueError("%s is on %s, the rays on %s" % (name, x.device, rays.device))
-        if not x.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-    shape = tuple(tri.shape)
-    if shape != lead and shape[:-1] != lead:
-        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
+    _tensor("tri", tri, torch.int32, device=rays.device)
+    _tensor("t", t, torch.float32, device=rays.device)
+    shape = _row_shape(tri, lead)
     if tuple(t.shape) != shape:
         raise ValueError("t must have shape %s, not %s" % (shape, tuple(t.shape)))
-    n = tri.numel()
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 hits per call")
+    n = _count(tri, 1, "hits")
     point = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
     normal = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
     inside = torch.empty(shape, dtype=torch.uint8, device=rays.device)
     if n == 0:
         return point, normal, inside.view(torch.bool)
     h, ts = _stream(rays, stream)
-    per_hit = rays
-    if shape != lead:                                           # a ray per entry of its row, copied on the query's own stream
-        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=rays.device)
-        with torch.cuda.stream(on):
-            per_hit = rays.unsqueeze(-2).expand(lead + (shape[-1], 6)).contiguous()
+    per_hit = _per_entry(rays, lead, shape, h, ts)
     P = C.c_void_p
     _call(scene, lib.ezrt_surface_at_device(scene._h, P(per_hit.data_ptr()), P(tri.data_ptr()), P(t.data_ptr()), n, int(integrator),
                                             P(point.data_ptr()), P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
@@ -241,30 +252,10 @@ def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=
 
 def _check_points(points, d_max):
     """The number of points, after the checks every point query makes of its points and d_max."""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise TypeError("points must be a GPU tensor")
-    if points.dtype != torch.float32:
-        raise TypeError("points must be float32, not %s" % points.dtype)
-    if points.dim() < 1 or points.shape[-1] != 3:
-        raise ValueError("points must have shape [..., 3], not %s" % (tuple(points.shape),))
-    if not points.is_contiguous():
-        raise ValueError("points must be contiguous")
-    lead = tuple(points.shape[:-1])
+    _tensor("points", points, torch.float32, last=3)
     if d_max is not None:
-        if not isinstance(d_max, torch.Tensor) or not d_max.is_cuda:
-            raise TypeError("d_max must be a GPU tensor")
-        if d_max.dtype != torch.float32:
-            raise TypeError("d_max must be float32, not %s" % d_max.dtype)
-        if d_max.device != points.device:
-            raise ValueError("d_max is on %s, the points on %s" % (d_max.device, points.device))
-        if tuple(d_max.shape) != lead:
-            raise ValueError("d_max must have shape %s, not %s" % (lead, tuple(d_max.shape)))
-        if not d_max.is_contiguous():
-            raise ValueError("d_max must be contiguous")
-    n = points.numel() // 3
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 points per call")
-    return n
+        _tensor("d_max", d_max, torch.float32, points.shape[:-1], device=points.device)
+    return _count(points, 3, "points")
 
 
 def closest_point(scene, points, d_max=None, stream=None):
@@ -327,31 +318,16 @@ def closest_point_at(scene, points, tri, stream=None):
     _check_points(points, None)
     lib = _scene_lib(scene, _abi.NEAREST_ABI)
     lead = tuple(points.shape[:-1])
-    if not isinstance(tri, torch.Tensor) or not tri.is_cuda:
-        raise TypeError("tri must be a GPU tensor")
-    if tri.dtype != torch.int32:
-        raise TypeError("tri must be int32, not %s" % tri.dtype)
-    if tri.device != points.device:
-        raise ValueError("tri is on %s, the points on %s" % (tri.device, points.device))
-    if not tri.is_contiguous():
-        raise ValueError("tri must be contiguous")
-    shape = tuple(tri.shape)
-    if shape != lead and shape[:-1] != lead:
-        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
-    n = tri.numel()
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 elements per call")
+    _tensor("tri", tri, torch.int32, device=points.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
     point = torch.empty(shape + (3,), dtype=torch.float32, device=points.device)
     dist = torch.empty(shape, dtype=torch.float32, device=points.device)
     bary = torch.empty(shape + (2,), dtype=torch.float32, device=points.device)
     if n == 0:
         return ClosestPoint(tri, point, dist, bary)
     h, ts = _stream(points, stream)
-    per_entry = points
-    if shape != lead:                                           # a point per entry of its row, copied on the query's own stream
-        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=points.device)
-        with torch.cuda.stream(on):
-            per_entry = points.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
+    per_entry = _per_entry(points, lead, shape, h, ts)
     P = C.c_void_p
     _call(scene, lib.ezrt_closest_point_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(point.data_ptr()),
                                                   P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
@@ -413,23 +389,13 @@ def signed_distance(scene, points, d_max=None, axis=0, stream=None):
 
 def _check_boxes(lo, hi):
     """The number of boxes, after the checks every box query makes of its corners."""
-    for name, x in (("lo", lo), ("hi", hi)):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise TypeError("%s must be a GPU tensor" % name)
-        if x.dtype != torch.float32:
-            raise TypeError("%s must be float32, not %s" % (name, x.dtype))
-        if x.dim() < 1 or x.shape[-1] != 3:
-            raise ValueError("%s must have shape [..., 3], not %s" % (name, tuple(x.shape)))
-        if not x.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
+    _tensor("lo", lo, torch.float32, last=3)
+    _tensor("hi", hi, torch.float32, last=3)
     if hi.device != lo.device:
-        raise ValueError("hi is on %s, lo on %s" % (hi.device, lo.device))
+        raise ValueError("hi is on %s, not on %s" % (hi.device, lo.device))
     if tuple(hi.shape) != tuple(lo.shape):
         raise ValueError("hi must have shape %s, not %s" % (tuple(lo.shape), tuple(hi.shape)))
-    n = lo.numel() // 3
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 boxes per call")
-    return n
+    return _count(lo, 3, "boxes")
 
 
 def box_overlap(scene, lo, hi, max_k=8, count=False, stream=None):
@@ -469,30 +435,14 @@ def box_overlap_at(scene, lo, hi, tri, stream=None):
     _check_boxes(lo, hi)
     lib = _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
     lead = tuple(lo.shape[:-1])
-    if not isinstance(tri, torch.Tensor) or not tri.is_cuda:
-        raise TypeError("tri must be a GPU tensor")
-    if tri.dtype != torch.int32:
-        raise TypeError("tri must be int32, not %s" % tri.dtype)
-    if tri.device != lo.device:
-        raise ValueError("tri is on %s, the boxes on %s" % (tri.device, lo.device))
-    if not tri.is_contiguous():
-        raise ValueError("tri must be contiguous")
-    shape = tuple(tri.shape)
-    if shape != lead and shape[:-1] != lead:
-        raise ValueError("tri must have shape %s or %s, not %s" % (lead, lead + ("K",), shape))
-    n = tri.numel()
-    if n > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 elements per call")
+    _tensor("tri", tri, torch.int32, device=lo.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
     out = torch.empty(shape, dtype=torch.uint8, device=lo.device)
     if n == 0:
         return out.view(torch.bool)
     h, ts = _stream(lo, stream)
-    per_lo, per_hi = lo, hi
-    if shape != lead:                                           # a box per entry of its row, copied on the query's own stream
-        on = ts if ts is not None else torch.cuda.ExternalStream(h, device=lo.device)
-        with torch.cuda.stream(on):
-            per_lo = lo.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
-            per_hi = hi.unsqueeze(-2).expand(lead + (shape[-1], 3)).contiguous()
+    per_lo, per_hi = _per_entry(lo, lead, shape, h, ts), _per_entry(hi, lead, shape, h, ts)
     P = C.c_void_p
     _call(scene, lib.ezrt_box_overlap_at_device(scene._h, P(per_lo.data_ptr()), P(per_hi.data_ptr()), P(tri.data_ptr()), n,
                                                 P(out.data_ptr()), P(h)))

@@ -21,26 +21,14 @@ import torch
 from . import _abi
 from .query import _SURFACE_INTEGRATORS as INTEGRATORS
 from .query import _call, _keep, _scene_lib, _stream
+from .query import _tensor as _query_tensor
 
 _P = C.c_void_p
 
 
 def _tensor(name, x, dtype, shape=None, last=None, device=None):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise TypeError("%s must be a GPU tensor" % name)
-    if x.dtype != dtype:
-        raise TypeError("%s must be %s, not %s" % (name, str(dtype).replace("torch.", ""), x.dtype))
-    if device is not None and x.device != device:
-        raise ValueError("%s is on %s, not on %s" % (name, x.device, device))
-    if shape is not None and tuple(x.shape) != tuple(shape):
-        raise ValueError("%s must have shape %s, not %s" % (name, tuple(shape), tuple(x.shape)))
-    if last is not None and (x.dim() < 1 or x.shape[-1] != last):
-        raise ValueError("%s must have shape [..., %d], not %s" % (name, last, tuple(x.shape)))
-    if not x.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-    if x.numel() > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 floats per tensor and call")
-    return x
+    # query.py's checks, and a bound on the tensor as a whole
+    return _query_tensor(name, x, dtype, shape, last, device, max_numel=2**31 - 1)
 
 
 def _integrator(integrator):
