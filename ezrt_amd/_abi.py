@@ -207,6 +207,17 @@ BOX_OVERLAP_ABI = {
 BOX_OVERLAP_MAX = 64  # EZRT_BOX_OVERLAP_MAX
 
 
+# stream-ordered triangle-overlap queries on device memory, libezrt_hip.so only (include/ezrt_tri_overlap.h); pointers are device
+# addresses
+TRI_OVERLAP_ABI = {
+    # s, tris9, n, max_k, tri_id, n_overlap, stream
+    "ezrt_query_tri_overlap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, tris9, tri_id, n, overlaps, stream
+    "ezrt_tri_overlap_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+TRI_OVERLAP_MAX = 64  # EZRT_TRI_OVERLAP_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -274,7 +285,7 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      INSIDE_ABI, BOX_OVERLAP_ABI, REFIT_ABI):
+                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

@@ -500,6 +500,118 @@ EZD bool box_overlaps(const float4* __restrict__ tg, f3 lo, f3 hi) {
   return true;
 }
 
+// ---- triangle-overlap queries (include/ezrt_tri_overlap.h, where the definition is the contract): liveness, T1 and T2 of one scene
+// triangle against a LIVE query triangle (the caller has checked it with tri_live), in the header's order.  A direction g x axis_j
+// has x[j] = 0: its term x[j] * D[j] is a zero (D is finite), and adding a zero changes at most the sign of a zero sum, which no
+// comparison sees -- so those projections are sums of two products.  Only the fp64 state of one direction is held at a time: the
+// loops over edges are not unrolled, an edge's end points are picked from the sorted vertices by its index, and every difference is
+// taken from the fp32 values where it is used.
+struct TriSorted {
+  f3 v0, v1, v2; // v0 <= v1 <= v2 by value
+};
+struct TriQuery {
+  TriSorted t;
+  f3 lo, hi; // its bounding box: the gate of T1 and of the walk
+};
+EZD bool tri_less(f3 x, f3 y) { return x.x < y.x || (x.x == y.x && (x.y < y.y || (x.y == y.y && x.z < y.z))); }
+EZD bool tri_same(f3 x, f3 y) { return x.x == y.x && x.y == y.y && x.z == y.z; }
+// a live triangle: nine finite numbers and, of the sorted vertices, N != (0, 0, 0); `t` is the sorted triangle when it is live
+EZD bool tri_live(f3 a, f3 b, f3 c, TriSorted& t) {
+  const float inf = __builtin_inff();
+  if (!(ez_abs(a.x) < inf && ez_abs(a.y) < inf && ez_abs(a.z) < inf && ez_abs(b.x) < inf && ez_abs(b.y) < inf && ez_abs(b.z) < inf &&
+        ez_abs(c.x) < inf && ez_abs(c.y) < inf && ez_abs(c.z) < inf))
+    return false;
+  auto cswap = [](f3& x, f3& y) {
+    if (tri_less(y, x)) {
+      const f3 h = x;
+      x = y, y = h;
+    }
+  };
+  cswap(a, b);
+  cswap(b, c);
+  cswap(a, b);
+  t.v0 = a, t.v1 = b, t.v2 = c;
+  const double e1x = (double)b.x - (double)a.x, e1y = (double)b.y - (double)a.y, e1z = (double)b.z - (double)a.z;
+  const double e2x = (double)c.x - (double)a.x, e2y = (double)c.y - (double)a.y, e2z = (double)c.z - (double)a.z;
+  const double Nx = e1y * e2z - e1z * e2y, Ny = e1z * e2x - e1x * e2z, Nz = e1x * e2y - e1y * e2x;
+  return Nx != 0.0 || Ny != 0.0 || Nz != 0.0;
+}
+// the query triangle p1 p2 p3 as the kernels hold it; false when it is not live (q is then not to be used)
+EZD bool tri_query(f3 p1, f3 p2, f3 p3, TriQuery& q) {
+  if (!tri_live(p1, p2, p3, q.t)) return false;
+  const f3 a = q.t.v0, b = q.t.v1, c = q.t.v2;
+  q.lo = mk(a.x, ez_min(ez_min(a.y, b.y), c.y), ez_min(ez_min(a.z, b.z), c.z)); // (sorted by x first)
+  q.hi = mk(c.x, ez_max(ez_max(a.y, b.y), c.y), ez_max(ez_max(a.z, b.z), c.z));
+  return true;
+}
+// edge i of a sorted triangle: E0 = (v0, v1), E1 = (v1, v2), E2 = (v0, v2)
+EZD f3 tri_edge_from(const TriSorted& t, int i) { return i == 1 ? t.v1 : t.v0; }
+EZD f3 tri_edge_to(const TriSorted& t, int i) { return i == 0 ? t.v1 : t.v2; }
+// max(0, p1, p2) < min(p3, p4, p5) || max(p3, p4, p5) < min(0, p1, p2)
+EZD bool tri_intervals_apart(double p1, double p2, double p3, double p4, double p5) {
+  double amax = p1 > 0.0 ? p1 : 0.0, amin = p1 < 0.0 ? p1 : 0.0;
+  amax = p2 > amax ? p2 : amax, amin = p2 < amin ? p2 : amin;
+  double bmax = p4 > p3 ? p4 : p3, bmin = p4 < p3 ? p4 : p3;
+  bmax = p5 > bmax ? p5 : bmax, bmin = p5 < bmin ? p5 : bmin;
+  return amax < bmin || bmax < amin;
+}
+// does the direction x separate A and B?  p(x, D) = (x0*D[0] + x1*D[1]) + x2*D[2], D relative to a0
+EZD bool tri_axis_separates(double x0, double x1, double x2, const TriSorted& A, const TriSorted& B) {
+  const f3 o = A.v0;
+  auto p = [&](f3 X) { return (x0 * ((double)X.x - (double)o.x) + x1 * ((double)X.y - (double)o.y)) + x2 * ((double)X.z - (double)o.z); };
+  return tri_intervals_apart(p(A.v1), p(A.v2), p(B.v0), p(B.v1), p(B.v2));
+}
+// does g x axis_j separate, for the edge g = (from, to) and all three j?  (u, w) = ((j + 1) % 3, (j + 2) % 3): x[u] = -g[w], x[w] = g[u]
+EZD bool tri_edge_axes_separate(f3 from, f3 to, const TriSorted& A, const TriSorted& B) {
+  const f3 o = A.v0;
+  const double gx = (double)to.x - (double)from.x, gy = (double)to.y - (double)from.y, gz = (double)to.z - (double)from.z;
+  auto px = [&](f3 X) { return -gz * ((double)X.y - (double)o.y) + gy * ((double)X.z - (double)o.z); }; // j = 0: (u, w) = (y, z)
+  if (tri_intervals_apart(px(A.v1), px(A.v2), px(B.v0), px(B.v1), px(B.v2))) return true;
+  auto py = [&](f3 X) { return gz * ((double)X.x - (double)o.x) + -gx * ((double)X.z - (double)o.z); }; // j = 1: (z, x); x0 = g[z], x2 = -g[x]
+  if (tri_intervals_apart(py(A.v1), py(A.v2), py(B.v0), py(B.v1), py(B.v2))) return true;
+  auto pz = [&](f3 X) { return -gy * ((double)X.x - (double)o.x) + gx * ((double)X.y - (double)o.y); }; // j = 2: (x, y)
+  return tri_intervals_apart(pz(A.v1), pz(A.v2), pz(B.v0), pz(B.v1), pz(B.v2));
+}
+EZD bool tri_overlaps(const float4* __restrict__ tg, const TriQuery& q) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  // T1: q.lo is the least and q.hi the greatest coordinate of the query's vertices (a comparison with a NaN is false)
+  if (!((q.lo.x <= a.x || q.lo.x <= b.x || q.lo.x <= c.x) && (a.x <= q.hi.x || b.x <= q.hi.x || c.x <= q.hi.x))) return false;
+  if (!((q.lo.y <= a.y || q.lo.y <= b.y || q.lo.y <= c.y) && (a.y <= q.hi.y || b.y <= q.hi.y || c.y <= q.hi.y))) return false;
+  if (!((q.lo.z <= a.z || q.lo.z <= b.z || q.lo.z <= c.z) && (a.z <= q.hi.z || b.z <= q.hi.z || c.z <= q.hi.z))) return false;
+  TriSorted s;
+  if (!tri_live(a, b, c, s)) return false;
+  // (A, B): the two triangles in the order of their values
+  const bool scene_first = tri_less(s.v0, q.t.v0) ||
+                           (tri_same(s.v0, q.t.v0) && (tri_less(s.v1, q.t.v1) || (tri_same(s.v1, q.t.v1) && tri_less(s.v2, q.t.v2))));
+  const TriSorted A = scene_first ? s : q.t, B = scene_first ? q.t : s;
+  // T2: the two normals
+#pragma unroll 1
+  for (int side = 0; side < 2; side++) {
+    const TriSorted t = side ? B : A;
+    const double e1x = (double)t.v1.x - (double)t.v0.x, e1y = (double)t.v1.y - (double)t.v0.y, e1z = (double)t.v1.z - (double)t.v0.z;
+    const double e2x = (double)t.v2.x - (double)t.v0.x, e2y = (double)t.v2.y - (double)t.v0.y, e2z = (double)t.v2.z - (double)t.v0.z;
+    if (tri_axis_separates(e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x, A, B)) return false;
+  }
+  // ... g x axis_j for the edges of A, then of B
+#pragma unroll 1
+  for (int g = 0; g < 6; g++) {
+    const TriSorted t = g < 3 ? A : B;
+    const int i = g < 3 ? g : g - 3;
+    if (tri_edge_axes_separate(tri_edge_from(t, i), tri_edge_to(t, i), A, B)) return false;
+  }
+  // ... e_i x f_j
+#pragma unroll 1
+  for (int ij = 0; ij < 9; ij++) {
+    const int i = ij / 3, j = ij - 3 * i;
+    const f3 ea = tri_edge_from(A, i), eb = tri_edge_to(A, i), fa = tri_edge_from(B, j), fb = tri_edge_to(B, j);
+    const double ex = (double)eb.x - (double)ea.x, ey = (double)eb.y - (double)ea.y, ez = (double)eb.z - (double)ea.z;
+    const double fx = (double)fb.x - (double)fa.x, fy = (double)fb.y - (double)fa.y, fz = (double)fb.z - (double)fa.z;
+    if (tri_axis_separates(ey * fz - ez * fy, ez * fx - ex * fz, ex * fy - ey * fx, A, B)) return false;
+  }
+  return true;
+}
+
 // hitBVH: P5/fsh:254-306 + hitArray 238-251.  Unpruned, near-first, ties go
 // right-first, strict < keeps the first-found hit -- identical visit order per
 // ray.  The traversal stack lives in LDS: `stack` points at this lane's column

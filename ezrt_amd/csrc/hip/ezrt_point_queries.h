@@ -1,16 +1,20 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
-// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap queries
-// (include/ezrt_box_overlap.h).  One query point or box per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap and triangle-overlap
+// queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h).  One query point, box or triangle per lane, a workgroup of one
+// wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest and signed distance share
 //   closest_point_kernel<WALK>       closest_point_search + closest_point_store
 //   nearest_kernel<WALK, COUNT>      point_walk carrying a K-entry sorted list instead of one winner
 //   closest_point_at_kernel          closest_point_triangle for pairs the caller holds
-//   slot_walk                        the depth-first walk over the 4-wide records that inside and box overlap share
+//   slot_walk                        the depth-first walk over the 4-wide records that inside, box overlap and triangle overlap share
 //   inside_kernel<WALK>              inside_count: slot_walk on the rows its axis needs
 //   signed_distance_kernel<WALK>     inside_count + closest_point_search + closest_point_store
-//   box_overlap_kernel<WALK>         slot_walk carrying a K-entry list of the lowest ids and a count
+//   overlap_rows                     slot_walk carrying a K-entry list of the lowest ids and a count, and the wave's row finish
+//   box_overlap_kernel<WALK>         overlap_rows with the box as the gate and box_overlaps as the rule
 //   box_overlap_at_kernel            box_overlaps for pairs the caller holds
+//   tri_overlap_kernel<WALK>         overlap_rows with the query triangle's bounding box as the gate and tri_overlaps as the rule
+//   tri_overlap_at_kernel            tri_overlaps for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -434,16 +438,19 @@ struct BoxOverlapArgs {
   int32_t* tri;             // n x K (not read or written when K == 0)
   int32_t* n_overlap;       // n, or null
 };
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+// The body that box_overlap_kernel and tri_overlap_kernel share: the walk or the sweep of lane i's query, its list and count, and
+// the wave's row finish.  `a` has sc, n, K, div_k, tri and n_overlap; load(i, q) reads query i into q and says whether it is live;
+// q.lo and q.hi are the gate of the walk (the box itself, or the query triangle's bounding box); overlaps(tri_geom_k, q) is the
+// per-triangle rule, of which the gate is a necessary condition on the triangle's own bounding box (H1, T1).
+template <bool WALK, class Query, class Args, class Load, class Overlaps>
+EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Overlaps overlaps) {
   const uint32_t lane = threadIdx.x;
   const uint32_t i = blockIdx.x * CP_BLOCK + lane;
   const int K = a.K;
   int nb = 0;
   if (i < a.n) {
-    const f3 lo = ld3(a.lo + (size_t)i * 3), hi = ld3(a.hi + (size_t)i * 3);
-    const bool live = box_live(lo, hi);
+    Query q;
+    const bool live = load(i, q);
     int32_t* ri = a.tri + (size_t)i * K;
     int32_t count = 0;
     int32_t last_id = -1; // entry K - 1 once the row is full (with K == 0 it is full now, and every id is greater than -1)
@@ -452,7 +459,7 @@ __global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a)
       if (j == K - 1) last_id = id; // (a put to slot K - 1 happens only when the row is full)
     };
     auto visit = [&](int32_t k) {
-      if (!box_overlaps(a.sc.tri_geom + (size_t)k * 3, lo, hi)) return;
+      if (!overlaps(a.sc.tri_geom + (size_t)k * 3, q)) return;
       count++;
       if (nb == K && k > last_id) return; // behind a full row: counted only
       int j = nb < K ? nb++ : K - 1;
@@ -466,6 +473,7 @@ __global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a)
     };
     if (live) {
       if (WALK) {
+        const f3 &lo = q.lo, &hi = q.hi;
         slot_walk(
             a.sc.inner4, lds_stack + lane,
             [&](const float4* rec, auto take) {
@@ -500,6 +508,20 @@ __global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a)
     if (i - lane + row < a.n && slot >= (uint32_t)used) a.tri[base + e] = -1;
   }
 }
+struct BoxQuery {
+  f3 lo, hi;
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  overlap_rows<WALK, BoxQuery>(
+      a, lds_stack,
+      [&](uint32_t i, BoxQuery& q) {
+        q.lo = ld3(a.lo + (size_t)i * 3), q.hi = ld3(a.hi + (size_t)i * 3);
+        return box_live(q.lo, q.hi);
+      },
+      [](const float4* tg, const BoxQuery& q) { return box_overlaps(tg, q.lo, q.hi); });
+}
 
 // ezrt_box_overlap_at_device: box_overlaps for pairs the caller holds -- box i against triangle tri_id[i].  An id outside the scene
 // or a box that is not live writes 0.
@@ -511,6 +533,47 @@ __global__ __launch_bounds__(256) void box_overlap_at_kernel(const float4* tri_g
   const f3 lo = ld3(box_lo + (size_t)i * 3), hi = ld3(box_hi + (size_t)i * 3);
   bool o = false;
   if (box_live(lo, hi) && (uint32_t)tri < (uint32_t)n_tri) o = box_overlaps(tri_geom + (size_t)tri * 3, lo, hi);
+  overlaps[i] = o ? 1u : 0u;
+}
+
+// ---- triangle-overlap queries (include/ezrt_tri_overlap.h).
+//
+// tri_overlap_kernel<WALK>: one query triangle per lane, through overlap_rows as box_overlap_kernel: the gate of the walk is the query
+// triangle's own fp32 bounding box -- by T1 an overlapping triangle's bounding box passes it, hence every box that holds the
+// triangle -- and the per-triangle rule is tri_overlaps (ezrt_device.h: liveness, T1 and the 29 directions of T2).  A query triangle
+// that is not live takes part with an empty row and a count of 0.
+struct TriOverlapArgs {
+  PointScene sc;
+  const float* tris;        // n x 9
+  uint32_t n;
+  int32_t K;                // 0 .. 64
+  FastDiv div_k;            // / max(K, 1) (the finishing pass)
+  int32_t* tri;             // n x K (not read or written when K == 0)
+  int32_t* n_overlap;       // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void tri_overlap_kernel(TriOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  overlap_rows<WALK, TriQuery>(
+      a, lds_stack,
+      [&](uint32_t i, TriQuery& q) {
+        const float* t = a.tris + (size_t)i * 9;
+        return tri_query(ld3(t), ld3(t + 3), ld3(t + 6), q);
+      },
+      [](const float4* tg, const TriQuery& q) { return tri_overlaps(tg, q); });
+}
+
+// ezrt_tri_overlap_at_device: tri_overlaps for pairs the caller holds -- query triangle i against triangle tri_id[i].  An id outside
+// the scene or a query triangle that is not live writes 0.
+__global__ __launch_bounds__(256) void tri_overlap_at_kernel(const float4* tri_geom, int32_t n_tri, const float* tris, const int32_t* tri_id,
+                                                             uint32_t n, uint8_t* overlaps) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  const float* t = tris + (size_t)i * 9;
+  TriQuery q;
+  bool o = false;
+  if (tri_query(ld3(t), ld3(t + 3), ld3(t + 6), q) && (uint32_t)tri < (uint32_t)n_tri) o = tri_overlaps(tri_geom + (size_t)tri * 3, q);
   overlaps[i] = o ? 1u : 0u;
 }
 

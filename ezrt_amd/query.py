@@ -1,5 +1,6 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
-include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h).
+include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
+include/ezrt_tri_overlap.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -15,11 +16,14 @@ include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, inc
     tri, point, dist, bary, inside = query.signed_distance(scene, points)   # closest_point with dist negative inside the mesh
     tri, n_overlap = query.box_overlap(scene, lo, hi, max_k=8)   # the triangles each box [lo, hi] touches (include/ezrt_box_overlap.h)
     touches = query.box_overlap_at(scene, lo, hi, tri)           # ... the same test for pairs already held  (bool)
+    tri, n_overlap = query.tri_overlap(scene, tris, max_k=8)     # the triangles each triangle crosses (include/ezrt_tri_overlap.h)
+    crosses = query.tri_overlap_at(scene, tris, tri)             # ... the same test for pairs already held  (bool)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
 `d_max` (optional) a float32 GPU tensor of shape points.shape[:-1]; `lo` and `hi` are contiguous float32 GPU tensors of one shape
-[..., 3], the corners of axis-aligned boxes.  The outputs keep the leading dimensions.  The work is enqueued on
+[..., 3], the corners of axis-aligned boxes; `tris` is a contiguous float32 GPU tensor of shape [..., 9] (p1 p2 p3).  The outputs
+keep the leading dimensions.  The work is enqueued on
 `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the rays' device) and the functions
 return without waiting for it.  `axis` (0..5: +x, -x, +y, -y, +z, -z) is the direction of the ray whose crossings decide `inside`;
 on a closed mesh every axis gives the same answer, on an open one (the Bunny has holes) they may differ: vote over several.
@@ -39,6 +43,7 @@ ClosestPoint = collections.namedtuple("ClosestPoint", "tri point dist bary")
 Nearest = collections.namedtuple("Nearest", "tri dist count")
 SignedDistance = collections.namedtuple("SignedDistance", "tri point dist bary inside")
 BoxOverlap = collections.namedtuple("BoxOverlap", "tri n_overlap")
+TriOverlap = collections.namedtuple("TriOverlap", "tri n_overlap")
 
 
 def _scene_lib(scene, abi):
@@ -447,4 +452,62 @@ def box_overlap_at(scene, lo, hi, tri, stream=None):
     _call(scene, lib.ezrt_box_overlap_at_device(scene._h, P(per_lo.data_ptr()), P(per_hi.data_ptr()), P(tri.data_ptr()), n,
                                                 P(out.data_ptr()), P(h)))
     _keep((lo, hi, per_lo, per_hi, tri, out), ts, lo)
+    return out.view(torch.bool)
+
+
+def _check_tris(tris):
+    """The number of query triangles, after the checks every triangle query makes of them."""
+    _tensor("tris", tris, torch.float32, last=9)
+    return _count(tris, 9, "triangles")
+
+
+def tri_overlap(scene, tris, max_k=8, count=False, stream=None):
+    """TriOverlap(tri int32 [..., max_k], n_overlap int32 [...] or None): for every triangle of `tris` (a contiguous float32 GPU
+    tensor [..., 9]: p1 p2 p3) the triangles of the scene that it crosses or touches -- the exact separating-axis test of two closed
+    triangles, so touching counts (a vertex on a face, an edge or a vertex, edges that cross, coplanar triangles that share an edge or
+    a point), coplanar pairs are answered by the same rule, and swapping the two triangles gives the same answer.  `tri` holds the
+    lowest triangle indices in ascending order, then -1: a larger max_k (0 .. 64) only appends, and the answer depends on neither the
+    tree nor the order of the visits.  `count=True` also returns the full number of overlapping triangles, which may exceed max_k;
+    with max_k == 0 the call only counts (`tri` is empty and `count` must be True).  A triangle with a non-finite number or with
+    collinear or repeated vertices overlaps nothing, on either side -- unlike `box_overlap`, where a degenerate triangle overlaps as
+    the segment or point it is.  The definition, on the bits: include/ezrt_tri_overlap.h; `tri_overlap_at` tests pairs."""
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.TRI_OVERLAP_MAX:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.TRI_OVERLAP_MAX, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    n = _check_tris(tris)
+    lib = _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
+    lead = tuple(tris.shape[:-1])
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=tris.device)
+    total = torch.empty(lead, dtype=torch.int32, device=tris.device) if count else None
+    if n == 0:
+        return TriOverlap(tri, total)
+    h, ts = _stream(tris, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_tri_overlap_device(scene._h, P(tris.data_ptr()), n, max_k, P(tri.data_ptr()) if max_k else None,
+                                                   P(total.data_ptr()) if count else None, P(h)))
+    _keep((tris, tri, total), ts, tris)
+    return TriOverlap(tri, total)
+
+
+def tri_overlap_at(scene, tris, tri, stream=None):
+    """bool tri.shape: whether triangle tri[...] of the scene crosses or touches its query triangle, by `tri_overlap`'s test.  `tri`
+    (int32) has the shape tris.shape[:-1], or one trailing dimension more -- the output of `tri_overlap` -- and every entry of a row
+    then belongs to the row's query triangle.  An id that is no triangle of the scene (an unused slot, -1) gives False."""
+    _check_tris(tris)
+    lib = _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
+    lead = tuple(tris.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=tris.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    out = torch.empty(shape, dtype=torch.uint8, device=tris.device)
+    if n == 0:
+        return out.view(torch.bool)
+    h, ts = _stream(tris, stream)
+    per = _per_entry(tris, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_tri_overlap_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(out.data_ptr()), P(h)))
+    _keep((tris, per, tri, out), ts, tris)
     return out.view(torch.bool)
