@@ -218,6 +218,17 @@ TRI_OVERLAP_ABI = {
 TRI_OVERLAP_MAX = 64  # EZRT_TRI_OVERLAP_MAX
 
 
+# stream-ordered self-overlap queries on device memory, libezrt_hip.so only (include/ezrt_self_overlap.h); pointers are device
+# addresses
+SELF_OVERLAP_ABI = {
+    # s, ids, n, max_k, tri_id, n_overlap, stream
+    "ezrt_query_self_overlap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, tri_a, tri_b, n, crosses, stream
+    "ezrt_self_overlap_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+SELF_OVERLAP_MAX = 64  # EZRT_SELF_OVERLAP_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -285,7 +296,7 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, REFIT_ABI):
+                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

@@ -612,6 +612,109 @@ EZD bool tri_overlaps(const float4* __restrict__ tg, const TriQuery& q) {
   return true;
 }
 
+// ---- self-overlap queries (include/ezrt_self_overlap.h, where the definition is the contract): crosses(I, J) of one scene triangle
+// against a LIVE triangle of the scene held as a TriQuery (the caller keeps the triangle's own id out), in the header's order: the
+// number s of vertices shared by value, then tri_overlaps, the two seg_meets, the fold rule or true.  As in tri_overlaps only the
+// fp64 state of one direction is held at a time, the loops are not unrolled and every difference is taken where it is used; the
+// projections of a direction g x axis_j are sums of two products, by the argument above.
+// max(0, p1, p2) < min(p3, p4) || max(p3, p4) < min(0, p1, p2)
+EZD bool seg_intervals_apart(double p1, double p2, double p3, double p4) {
+  double tmax = p1 > 0.0 ? p1 : 0.0, tmin = p1 < 0.0 ? p1 : 0.0;
+  tmax = p2 > tmax ? p2 : tmax, tmin = p2 < tmin ? p2 : tmin;
+  const double smax = p4 > p3 ? p4 : p3, smin = p4 < p3 ? p4 : p3;
+  return tmax < smin || smax < tmin;
+}
+// does the direction x separate the segment a b from T?  p(x, D), D relative to t0
+EZD bool seg_axis_separates(double x0, double x1, double x2, f3 a, f3 b, const TriSorted& T) {
+  const f3 o = T.v0;
+  auto p = [&](f3 X) { return (x0 * ((double)X.x - (double)o.x) + x1 * ((double)X.y - (double)o.y)) + x2 * ((double)X.z - (double)o.z); };
+  return seg_intervals_apart(p(T.v1), p(T.v2), p(a), p(b));
+}
+// does g x axis_j separate, for g = (from, to) and all three j?  (as tri_edge_axes_separate)
+EZD bool seg_edge_axes_separate(f3 from, f3 to, f3 a, f3 b, const TriSorted& T) {
+  const f3 o = T.v0;
+  const double gx = (double)to.x - (double)from.x, gy = (double)to.y - (double)from.y, gz = (double)to.z - (double)from.z;
+  auto px = [&](f3 X) { return -gz * ((double)X.y - (double)o.y) + gy * ((double)X.z - (double)o.z); };
+  if (seg_intervals_apart(px(T.v1), px(T.v2), px(a), px(b))) return true;
+  auto py = [&](f3 X) { return gz * ((double)X.x - (double)o.x) + -gx * ((double)X.z - (double)o.z); };
+  if (seg_intervals_apart(py(T.v1), py(T.v2), py(a), py(b))) return true;
+  auto pz = [&](f3 X) { return -gy * ((double)X.x - (double)o.x) + gx * ((double)X.y - (double)o.y); };
+  return seg_intervals_apart(pz(T.v1), pz(T.v2), pz(a), pz(b));
+}
+// the closed segment a b, (a, b) in the order of their values, against the closed live triangle T: none of the 16 directions separates
+EZD bool seg_meets(f3 a, f3 b, const TriSorted& T) {
+  {
+    const double e1x = (double)T.v1.x - (double)T.v0.x, e1y = (double)T.v1.y - (double)T.v0.y, e1z = (double)T.v1.z - (double)T.v0.z;
+    const double e2x = (double)T.v2.x - (double)T.v0.x, e2y = (double)T.v2.y - (double)T.v0.y, e2z = (double)T.v2.z - (double)T.v0.z;
+    if (seg_axis_separates(e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x, a, b, T)) return false;
+  }
+  // ... g x axis_j for the segment, then for the edges of T
+#pragma unroll 1
+  for (int g = 0; g < 4; g++) {
+    const f3 from = g == 0 ? a : tri_edge_from(T, g - 1), to = g == 0 ? b : tri_edge_to(T, g - 1);
+    if (seg_edge_axes_separate(from, to, a, b, T)) return false;
+  }
+  // ... g_0 x f_j
+#pragma unroll 1
+  for (int j = 0; j < 3; j++) {
+    const f3 fa = tri_edge_from(T, j), fb = tri_edge_to(T, j);
+    const double dx = (double)b.x - (double)a.x, dy = (double)b.y - (double)a.y, dz = (double)b.z - (double)a.z;
+    const double fx = (double)fb.x - (double)fa.x, fy = (double)fb.y - (double)fa.y, fz = (double)fb.z - (double)fa.z;
+    if (seg_axis_separates(dy * fz - dz * fy, dz * fx - dx * fz, dx * fy - dy * fx, a, b, T)) return false;
+  }
+  return true;
+}
+// one of two vertices or triangles, chosen value by value (selects, never an address)
+EZD f3 tri_pick(bool c, f3 x, f3 y) { return mk(c ? x.x : y.x, c ? x.y : y.y, c ? x.z : y.z); }
+EZD TriSorted tri_pick(bool c, const TriSorted& x, const TriSorted& y) {
+  TriSorted r;
+  r.v0 = tri_pick(c, x.v0, y.v0), r.v1 = tri_pick(c, x.v1, y.v1), r.v2 = tri_pick(c, x.v2, y.v2);
+  return r;
+}
+// vertex i of a sorted triangle, and the two others in the order of their values
+EZD f3 tri_vertex(const TriSorted& t, int i) { return tri_pick(i == 0, t.v0, tri_pick(i == 1, t.v1, t.v2)); }
+EZD f3 tri_rest_lo(const TriSorted& t, int i) { return tri_pick(i == 0, t.v1, t.v0); }
+EZD f3 tri_rest_hi(const TriSorted& t, int i) { return tri_pick(i == 2, t.v1, t.v2); }
+EZD bool tri_holds(const TriSorted& t, f3 x) { return tri_same(x, t.v0) || tri_same(x, t.v1) || tri_same(x, t.v2); }
+EZD bool self_crosses(const float4* __restrict__ tg, const TriQuery& q) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  // s, on the vertices as they are stored: a NaN equals nothing, and a triangle with a repeated vertex is not live
+  const int s = (tri_holds(q.t, a) ? 1 : 0) + (tri_holds(q.t, b) ? 1 : 0) + (tri_holds(q.t, c) ? 1 : 0);
+  if (s == 0) return tri_overlaps(tg, q);
+  TriSorted t;
+  if (!tri_live(a, b, c, t)) return false; // (T1 holds: the shared value is in both bounding boxes)
+  if (s == 3) return true;
+  if (s == 1) {
+    // the place of the shared vertex in each sorted triangle; each triangle's opposite edge against the other triangle
+    const int iq = tri_holds(t, q.t.v0) ? 0 : tri_holds(t, q.t.v1) ? 1 : 2;
+    const int it = tri_holds(q.t, t.v0) ? 0 : tri_holds(q.t, t.v1) ? 1 : 2;
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+      const TriSorted S = tri_pick(side != 0, t, q.t), T = tri_pick(side != 0, q.t, t);
+      const int i = side ? it : iq;
+      if (seg_meets(tri_rest_lo(S, i), tri_rest_hi(S, i), T)) return true;
+    }
+    return false;
+  }
+  // s == 2: the place of the apex in each sorted triangle, (A, B) the two in the order of their values
+  const int iq = !tri_holds(t, q.t.v0) ? 0 : !tri_holds(t, q.t.v1) ? 1 : 2;
+  const int it = !tri_holds(q.t, t.v0) ? 0 : !tri_holds(q.t, t.v1) ? 1 : 2;
+  const bool scene_first = tri_less(t.v0, q.t.v0) ||
+                           (tri_same(t.v0, q.t.v0) && (tri_less(t.v1, q.t.v1) || (tri_same(t.v1, q.t.v1) && tri_less(t.v2, q.t.v2))));
+  const TriSorted A = tri_pick(scene_first, t, q.t);
+  const int ia = scene_first ? it : iq;
+  const f3 u = tri_rest_lo(A, ia), v = tri_rest_hi(A, ia), pa = tri_vertex(A, ia), pb = tri_pick(scene_first, tri_vertex(q.t, iq), tri_vertex(t, it));
+  const double ex = (double)v.x - (double)u.x, ey = (double)v.y - (double)u.y, ez = (double)v.z - (double)u.z;
+  const double ax = (double)pa.x - (double)u.x, ay = (double)pa.y - (double)u.y, az = (double)pa.z - (double)u.z;
+  const double bx = (double)pb.x - (double)u.x, by = (double)pb.y - (double)u.y, bz = (double)pb.z - (double)u.z;
+  const double Xax = ey * az - ez * ay, Xay = ez * ax - ex * az, Xaz = ex * ay - ey * ax;
+  if (!((Xax * bx + Xay * by) + Xaz * bz == 0.0)) return false; // coplanar
+  const double Xbx = ey * bz - ez * by, Xby = ez * bx - ex * bz, Xbz = ex * by - ey * bx;
+  return (Xax > 0.0 && Xbx > 0.0) || (Xax < 0.0 && Xbx < 0.0) || (Xay > 0.0 && Xby > 0.0) || (Xay < 0.0 && Xby < 0.0) ||
+         (Xaz > 0.0 && Xbz > 0.0) || (Xaz < 0.0 && Xbz < 0.0); // same_side
+}
+
 // hitBVH: P5/fsh:254-306 + hitArray 238-251.  Unpruned, near-first, ties go
 // right-first, strict < keeps the first-found hit -- identical visit order per
 // ray.  The traversal stack lives in LDS: `stack` points at this lane's column

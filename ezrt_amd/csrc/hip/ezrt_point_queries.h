@@ -1,7 +1,7 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
-// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap and triangle-overlap
-// queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h).  One query point, box or triangle per lane, a workgroup of one
-// wave.  Included by ezrt_queries.hip alone.
+// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap and
+// self-overlap queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h).  One query point, box
+// or triangle per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest and signed distance share
 //   closest_point_kernel<WALK>       closest_point_search + closest_point_store
@@ -15,6 +15,8 @@
 //   box_overlap_at_kernel            box_overlaps for pairs the caller holds
 //   tri_overlap_kernel<WALK>         overlap_rows with the query triangle's bounding box as the gate and tri_overlaps as the rule
 //   tri_overlap_at_kernel            tri_overlaps for pairs the caller holds
+//   self_overlap_kernel<WALK>        overlap_rows with a scene triangle's bounding box as the gate and self_crosses as the rule
+//   self_overlap_at_kernel           self_crosses for pairs of ids the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -575,6 +577,57 @@ __global__ __launch_bounds__(256) void tri_overlap_at_kernel(const float4* tri_g
   bool o = false;
   if (tri_query(ld3(t), ld3(t + 3), ld3(t + 6), q) && (uint32_t)tri < (uint32_t)n_tri) o = tri_overlaps(tri_geom + (size_t)tri * 3, q);
   overlaps[i] = o ? 1u : 0u;
+}
+
+// ---- self-overlap queries (include/ezrt_self_overlap.h).
+//
+// self_overlap_kernel<WALK>: one triangle of the scene per lane -- triangle ids[i], or triangle i when ids is null -- through
+// overlap_rows as tri_overlap_kernel: the gate of the walk is that triangle's own fp32 bounding box (T1 is part of the rule where the
+// two triangles share nothing and holds by itself where they share a value), and the per-triangle rule is self_crosses (ezrt_device.h)
+// for every triangle but the query's own.  An id outside the scene and a triangle that is not live take part with an empty row and a
+// count of 0.
+struct SelfQuery : TriQuery {
+  int32_t id; // the query's own triangle
+};
+struct SelfOverlapArgs {
+  PointScene sc;
+  const int32_t* ids;       // n, or null: query i is triangle i
+  uint32_t n;
+  int32_t K;                // 0 .. 64
+  FastDiv div_k;            // / max(K, 1) (the finishing pass)
+  int32_t* tri;             // n x K (not read or written when K == 0)
+  int32_t* n_overlap;       // n, or null
+};
+// triangle `id` of the scene as a query; false when the id is outside the scene or the triangle is not live
+EZD bool self_query(const PointScene& sc, int32_t id, TriQuery& q) {
+  if ((uint32_t)id >= (uint32_t)sc.n_tri) return false;
+  const float4* g = sc.tri_geom + (size_t)id * 3;
+  const float4 ga = g[0], gb = g[1], gc = g[2];
+  return tri_query(mk(ga.x, ga.y, ga.z), mk(gb.x, gb.y, gb.z), mk(gc.x, gc.y, gc.z), q);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void self_overlap_kernel(SelfOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  overlap_rows<WALK, SelfQuery>(
+      a, lds_stack,
+      [&](uint32_t i, SelfQuery& q) {
+        q.id = a.ids ? a.ids[i] : (int32_t)i;
+        return self_query(a.sc, q.id, q);
+      },
+      [&](const float4* tg, const SelfQuery& q) { return tg != a.sc.tri_geom + (size_t)q.id * 3 && self_crosses(tg, q); });
+}
+
+// ezrt_self_overlap_at_device: self_crosses for pairs the caller holds -- triangle tri_a[i] against triangle tri_b[i].  An id outside
+// the scene, equal ids and a triangle that is not live write 0.
+__global__ __launch_bounds__(256) void self_overlap_at_kernel(PointScene sc, const int32_t* tri_a, const int32_t* tri_b, uint32_t n,
+                                                              uint8_t* crosses) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t ta = tri_a[i], tb = tri_b[i];
+  TriQuery q;
+  bool o = false;
+  if (ta != tb && (uint32_t)tb < (uint32_t)sc.n_tri && self_query(sc, ta, q)) o = self_crosses(sc.tri_geom + (size_t)tb * 3, q);
+  crosses[i] = o ? 1u : 0u;
 }
 
 } // namespace ezd

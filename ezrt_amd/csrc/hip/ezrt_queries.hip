@@ -1,7 +1,7 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap and triangle-overlap queries (include/ezrt_closest_point.h, ezrt_nearest.h,
-// ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h).  A translation unit of its own: none of its kernels is compiled together
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap and self-overlap queries (include/ezrt_closest_point.h,
+// ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h).  A translation unit of its own: none of its kernels is compiled together
 // with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run
 // the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in
 // ezrt_launch.hip.  DESIGN.md 5.
@@ -14,6 +14,7 @@
 #include "ezrt_nearest.h"
 #include "ezrt_box_overlap.h"
 #include "ezrt_tri_overlap.h"
+#include "ezrt_self_overlap.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -433,6 +434,49 @@ int ezrt_tri_overlap_at_device(EzrtScene* s, const float* tris9, const int32_t* 
     hipStream_t st = (hipStream_t)stream;
     return query_call(s, {{tris9, N * 9 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(tri_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tris9, tri_id, (uint32_t)n, overlaps);
+    });
+  });
+}
+
+// ---- self-overlap queries on device memory (include/ezrt_self_overlap.h): one kernel each on `st`, no scratch (a query's list is
+// kept in its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by
+// point_scene.
+int ezrt_query_self_overlap_device(EzrtScene* s, const int32_t* ids, int n, int max_k, int32_t* tri_id, int32_t* n_overlap, void* stream) {
+  return ezi::guarded("ezrt_query_self_overlap_device", [&]() -> int {
+    if (!s || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!ids && (size_t)n > (size_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n exceeds the scene's %d triangles (ids is NULL)", (int)s->n_tri);
+    if (max_k < 0 || max_k > EZRT_SELF_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_SELF_OVERLAP_MAX);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{ids, N * sizeof(int32_t)}, {tri_id, N * K * sizeof(int32_t)}, {n_overlap, N * sizeof(int32_t)}}, N, st,
+                      [&](dim3, dim3) {
+      SelfOverlapArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.ids = ids;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      // this walk's entries are bare references, one row each: half of the column that decides the route
+      launch_routed(self_overlap_kernel<true>, self_overlap_kernel<false>, r, r.lds / 2, N, st, a);
+    });
+  });
+}
+int ezrt_self_overlap_at_device(EzrtScene* s, const int32_t* tri_a, const int32_t* tri_b, int n, uint8_t* crosses, void* stream) {
+  return ezi::guarded("ezrt_self_overlap_at_device", [&]() -> int {
+    if (!s || !tri_a || !tri_b || !crosses || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri_a, N * sizeof(int32_t)}, {tri_b, N * sizeof(int32_t)}, {crosses, N}}, N, st, [&](dim3 g, dim3 b) {
+      PointScene sc;
+      point_scene(s, sc);
+      hipLaunchKernelGGL(self_overlap_at_kernel, g, b, 0, st, sc, tri_a, tri_b, (uint32_t)n, crosses);
     });
   });
 }

@@ -1,6 +1,6 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
-include/ezrt_tri_overlap.h).
+include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -18,6 +18,8 @@ include/ezrt_tri_overlap.h).
     touches = query.box_overlap_at(scene, lo, hi, tri)           # ... the same test for pairs already held  (bool)
     tri, n_overlap = query.tri_overlap(scene, tris, max_k=8)     # the triangles each triangle crosses (include/ezrt_tri_overlap.h)
     crosses = query.tri_overlap_at(scene, tris, tri)             # ... the same test for pairs already held  (bool)
+    tri, n_overlap = query.self_overlap(scene, max_k=8)          # where the mesh crosses itself (include/ezrt_self_overlap.h)
+    crosses = query.self_overlap_at(scene, a, b)                 # ... the same test for pairs of triangle ids already held  (bool)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -44,6 +46,7 @@ Nearest = collections.namedtuple("Nearest", "tri dist count")
 SignedDistance = collections.namedtuple("SignedDistance", "tri point dist bary inside")
 BoxOverlap = collections.namedtuple("BoxOverlap", "tri n_overlap")
 TriOverlap = collections.namedtuple("TriOverlap", "tri n_overlap")
+SelfOverlap = collections.namedtuple("SelfOverlap", "tri n_overlap")
 
 
 def _scene_lib(scene, abi):
@@ -510,4 +513,61 @@ def tri_overlap_at(scene, tris, tri, stream=None):
     P = C.c_void_p
     _call(scene, lib.ezrt_tri_overlap_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(out.data_ptr()), P(h)))
     _keep((tris, per, tri, out), ts, tris)
+    return out.view(torch.bool)
+
+
+def self_overlap(scene, ids=None, max_k=8, count=False, stream=None):
+    """SelfOverlap(tri int32 [..., max_k], n_overlap int32 [...] or None): for every triangle id of `ids` (a contiguous int32 GPU
+    tensor of any shape; None: every triangle of the scene, in order, on the current device -- the scene's when it was created there)
+    the OTHER triangles of the scene that meet it anywhere except in what the two share by value: nothing for neighbours that
+    share a vertex or an edge and are otherwise apart, the crossing for two that pierce each other from a shared vertex or fold onto
+    each other over a shared edge, a duplicated face, and `tri_overlap`'s test for two that share nothing.  A mesh that does not
+    cross itself has empty rows: what `inside` and `signed_distance` assume, to be checked between two refits.  `tri` holds the
+    lowest triangle indices in ascending order, then -1: a larger max_k (0 .. 64) only appends, a pair appears in both triangles'
+    rows, and the answer depends on neither the tree nor the order or winding of any triangle.  `count=True` also returns the full
+    number of crossing triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count` must be
+    True).  An id that is no triangle of the scene, or a triangle that is not live, has an empty row.  The definition, on the bits:
+    include/ezrt_self_overlap.h; `self_overlap_at` tests pairs."""
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.SELF_OVERLAP_MAX:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.SELF_OVERLAP_MAX, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    if ids is not None:
+        _tensor("ids", ids, torch.int32)
+    lib = _scene_lib(scene, _abi.SELF_OVERLAP_ABI)
+    if ids is None:
+        lead, device = (scene.stats()["n_tri"],), torch.device("cuda", torch.cuda.current_device())
+        n = lead[0]
+    else:
+        lead, device = tuple(ids.shape), ids.device
+        n = _count(ids, 1, "triangle ids")
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=device)
+    total = torch.empty(lead, dtype=torch.int32, device=device) if count else None
+    if n == 0:
+        return SelfOverlap(tri, total)
+    h, ts = _stream(tri, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_self_overlap_device(scene._h, P(ids.data_ptr()) if ids is not None else None, n, max_k,
+                                                    P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
+    _keep((ids, tri, total), ts, tri)
+    return SelfOverlap(tri, total)
+
+
+def self_overlap_at(scene, a, b, stream=None):
+    """bool a.shape: whether triangles a[...] and b[...] of the scene cross, by `self_overlap`'s test.  `a` and `b` are contiguous
+    int32 GPU tensors of one shape.  Equal ids, an id that is no triangle of the scene (an unused slot, -1) and a triangle that is
+    not live give False."""
+    _tensor("a", a, torch.int32)
+    lib = _scene_lib(scene, _abi.SELF_OVERLAP_ABI)
+    _tensor("b", b, torch.int32, shape=a.shape, device=a.device)
+    n = _count(a, 1, "pairs")
+    out = torch.empty(tuple(a.shape), dtype=torch.uint8, device=a.device)
+    if n == 0:
+        return out.view(torch.bool)
+    h, ts = _stream(a, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_self_overlap_at_device(scene._h, P(a.data_ptr()), P(b.data_ptr()), n, P(out.data_ptr()), P(h)))
+    _keep((a, b, out), ts, a)
     return out.view(torch.bool)

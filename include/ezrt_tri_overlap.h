@@ -92,7 +92,8 @@
  * -- exactly the list of ezrt_query_box_overlap_device: a row of K entries is a prefix of every longer one, the answer does not
  * depend on the tree, and it survives a retree or a refit of unchanged geometry.  max_k is in 0 .. EZRT_TRI_OVERLAP_MAX; with
  * max_k == 0 tri_id is ignored and n_overlap is required: a count-only call.  A query triangle that is a triangle of the scene
- * overlaps itself and every triangle that shares a vertex with it; a self-intersection check discards those by their ids.
+ * overlaps itself and every triangle that shares a vertex with it; a self-intersection check is ezrt_self_overlap.h, whose rule
+ * leaves out what two triangles share by value and nothing else.
  *
  * ezrt_tri_overlap_at_device writes overlaps[i] = overlaps(query triangle i, triangle tri_id[i]) as 0 / 1; an id outside the scene
  * writes 0.  It narrows candidates the caller already holds -- rows of ezrt_query_box_overlap_device, or rows of this query after
