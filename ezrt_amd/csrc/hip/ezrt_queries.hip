@@ -41,7 +41,8 @@ static void launch_shade_eval(EzrtScene* s, dim3 g, dim3 b, hipStream_t st, cons
 // ---- point queries on device memory: what their kernels read of the scene, and the route of this call -- chosen per call: a refit
 // can change whether the scene prunes.  lds = the lane's stack column of the best-first walk (ezrt_point_queries.h: point_walk):
 // {lb, ref} per pending entry (+ 1 of slack).  A tree so lopsided that the column exceeds the 64 KiB of a launch without opt-in
-// (> 126 entries; none of the builders comes near) is swept instead, as is a scene that does not prune.
+// (> 127 entries: (need + 1) * 512 B <= 65 536 B admits 127; none of the builders comes near, and under the depth cap of 63 no
+// caller's tree does -- at most 3 entries per two levels of its 62: 93) is swept instead, as is a scene that does not prune.
 struct PointRoute {
   bool walk;
   size_t lds;

@@ -1,0 +1,199 @@
+"""The tree shapes of tests/tree_shapes.py, on the CPU: every pair of arrays is one that ezrt_scene_create accepts, every shape has the
+property it is named for, and -- on the numpy restatements alone -- the queries of tests/test_gpu_tree_shapes.py are no
+comparison of nothing: the triangles that no leaf holds decide a share of the answers, the points at the chain's deep end reach
+every triangle, and misses and empty rows are the smaller half of every batch.  (The LBVH shapes need the device: they are checked
+where they are made, in the GPU test.)"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import closest_point_expected as E  # noqa: E402
+import nearest_expected as NE  # noqa: E402
+import tree_shapes as T  # noqa: E402
+
+
+@pytest.mark.parametrize("name", T.HOST_SHAPES)
+def test_scene_create_accepts_the_arrays(name):
+    tri, nodes, expect = T.shape(name)
+    facts = T.check_valid(tri, nodes)                                  # parent < child < m, ranges inside, depth <= 63, leaf <= 128
+    assert tri.dtype == np.float32 and tri.shape[1] == 36 and tri.shape[0] <= 1500
+    assert expect["walk"] == (facts["nested"] and facts["holds"] and nodes.shape[0] > 2)
+    Q = T.shape_queries(name)
+    assert all(T.N_QUERIES <= Q[k].shape[0] <= 300 for k in ("points", "lo", "hi", "tris"))
+
+
+def test_the_base_set():
+    tri = T.base()
+    assert 1000 <= tri.shape[0] <= 1500
+    V = T.vertices(tri)
+    twice = [V[k].tobytes() for k in range(V.shape[0])]
+    assert len(twice) - len(set(twice)) == T.N_DUPLICATES              # exact duplicates: ties
+    W = T.shape_expected("sah8")
+    inside = W["inside0"][:T.N_QUERIES - 16]
+    assert 0.1 < inside.mean() < 0.9                                   # closed solids: inside is no constant
+    assert (W["self8.n"] > 0).mean() > 0.5 and (W["self8.n"] > 8).any()
+
+
+def test_each_shape_has_the_property_it_is_named_for():
+    facts = {name: T.check_valid(*T.shape(name)[:2]) for name in T.HOST_SHAPES}
+    for name in T.HOST_SHAPES:
+        assert facts[name]["nested"], name                             # every shape is nested; one leaf box misses a vertex
+        assert facts[name]["holds"] == (name != "leaf_misses"), name
+        assert facts[name]["uncovered"].size == (39 if name == "uncovered" else 0), name
+    assert facts["sah8"]["max_leaf"] == 8 and facts["sah8"]["depth"] < 20
+    tri, nodes, expect = T.shape("median1")
+    assert facts["median1"]["max_leaf"] == 1 and facts["median1"]["n_leaves"] == tri.shape[0]
+    tri, nodes, expect = T.shape("leaf128")
+    assert facts["leaf128"]["max_leaf"] == 128 and expect["n128"] >= 1 and (nodes[1:, 3] == 128).sum() == expect["n128"]
+    tri, nodes, expect = T.shape("chain")
+    assert facts["chain"]["depth"] == 63 == expect["depth"] and nodes.shape[0] == 2 * 62 + 2 and tri.shape[0] == 280
+    inner = [i for i in range(1, nodes.shape[0]) if nodes[i, 3] == 0]
+    assert len(inner) == 62 and all(nodes[int(nodes[i, 0]), 3] > 0 for i in inner)          # a leaf on the left of every inner node
+    assert all(nodes[int(nodes[i, 1]), 3] == 0 for i in inner[:-1]) and nodes[int(nodes[inner[-1], 1]), 3] > 0
+    assert [int(nodes[int(nodes[i, 0]), 3]) for i in inner[:9]] == [1, 2, 3, 4, 5, 6, 7, 8, 1]
+    for name, n in (("root_leaf_1", 1), ("root_leaf_8", 8)):
+        tri, nodes, expect = T.shape(name)
+        assert nodes.shape[0] == 2 and nodes[1, 3] == n == tri.shape[0] and facts[name]["depth"] == 1
+    tri, nodes, expect = T.shape("two_leaves")
+    assert nodes.shape[0] == 4 and sorted(nodes[2:, 3]) == [3, 5]
+    tri, nodes, expect = T.shape("loose")
+    tight = T.shape("sah8")[1]
+    assert np.array_equal(nodes[:, :6], tight[:, :6]) and (nodes[1:, 6:9] <= tight[1:, 6:9]).all() and (nodes[1:, 9:12] >= tight[1:, 9:12]).all()
+    assert ((nodes[1:, 6:9] < tight[1:, 6:9]) | (nodes[1:, 9:12] > tight[1:, 9:12])).any(1).all()   # every box is looser
+    tri, nodes, expect = T.shape("leaf_misses")
+    i = expect["missing_leaf"]
+    v = T.vertices(tri)[int(nodes[i, 4]):int(nodes[i, 4] + nodes[i, 3]), :, 0].max()
+    assert nodes[i, 9] < v and np.nextafter(nodes[i, 9], np.float32(np.inf)) == v            # by one ulp
+    changed = np.nonzero((nodes != T.shape("sah8")[1]).any(1))[0]
+    assert list(changed) == [i]
+
+
+def test_the_uncovered_triangles_lie_among_the_others_and_copy_lower_indices():
+    tri, nodes, expect = T.shape("uncovered")
+    unc = expect["uncovered"]
+    assert np.array_equal(T.check_valid(tri, nodes)["uncovered"], unc) and unc.size == 39
+    assert (unc >= tri.shape[0] - T.N_APPENDED).sum() == T.N_APPENDED and (unc < expect["n_covered_by_builder"]).sum() == 2
+    i = expect["cut_leaf"]                                             # the cut leaf keeps a box that still holds what it lost
+    lost = T.vertices(tri)[unc[:2]].reshape(-1, 3)
+    assert (lost >= nodes[i, 6:9]).all() and (lost <= nodes[i, 9:12]).all() and 1 < i < nodes.shape[0] - 1
+    V = T.vertices(tri)
+    covered = np.setdiff1d(np.arange(tri.shape[0]), unc)
+    assert expect["copies"].size >= 10 and np.isin(expect["copies"], unc).all() and np.isin(expect["originals"], covered).all()
+    assert (expect["originals"] < expect["copies"]).all() and np.array_equal(V[expect["originals"]], V[expect["copies"]])
+    lo, hi = V[covered].reshape(-1, 3).min(0), V[covered].reshape(-1, 3).max(0)
+    c = V[unc].mean(1)
+    assert (c > lo).all() and (c < hi).all()                           # not off to one side ...
+    d2 = NE.dist2_all(c, tri[covered])
+    assert (np.sqrt(d2.min(1)) <= 1.0).all()                           # ... a covered triangle within one voxel of each
+
+
+def _uses(rows, ids):
+    return np.isin(rows, ids).any(1)
+
+
+def test_a_lost_sweep_would_change_the_answers():
+    """On the restatement alone: what the uncovered triangles decide.  Removing them from the array is modelled by making them
+    non-finite, which keeps the indices of the others: a non-finite triangle is no candidate of any query."""
+    tri, nodes, expect = T.shape("uncovered")
+    Q, W = T.shape_queries("uncovered"), T.shape_expected("uncovered")
+    unc = expect["uncovered"]
+    n = Q["points"].shape[0]
+    won = np.isin(W["cp.tri"], unc)
+    assert won.sum() >= 0.1 * n, won.sum()
+    for key in ("box64", "trio64"):
+        rows, count = W[key + ".tri"], W[key + ".n"]
+        assert _uses(rows, unc)[count > 0].mean() >= 0.1, key
+    by_covered = ~np.isin(W["_ids"], unc) & (W["self_ids64.n"] > 0)     # the rows of covered queries: only the sweep lists an uncovered id there
+    assert _uses(W["self_ids64.tri"], unc)[by_covered].mean() >= 0.1
+    assert (np.isin(W["_ids"], unc) & (W["self_ids64.n"] > 0)).sum() >= 10             # and uncovered triangles as the queries
+    assert np.isin(unc, W["_ids"]).all()                               # the id subset has every uncovered triangle as a query
+    assert (_uses(W["near51.tri"], unc) & ~won).sum() >= 10            # lists that change where the winner does not: the duplicates
+    gone = np.array(tri)
+    gone[unc, :9] = np.nan
+    L = T.expected(gone, Q, W["_ids"])
+    covered = {"self8.n": ~np.isin(np.arange(tri.shape[0]), unc), "self_ids64.tri": ~np.isin(W["_ids"], unc)}
+    for key, least in (("cp.tri", 10), ("near51.tri", 10), ("near51.count", 10), ("crossings0", 10), ("crossings4", 10), ("sd.dist", 10),
+                       ("box8.tri", 10), ("box0.n", 10), ("trio8.tri", 10), ("trio0.n", 10), ("self8.n", 10), ("self_ids64.tri", 10)):
+        a, b = W[key].reshape(W[key].shape[0], -1), L[key].reshape(W[key].shape[0], -1)
+        rows = (a.view(np.uint32) != b.view(np.uint32)).any(1) if a.dtype == np.float32 else (a != b).any(1)
+        changed = int((rows & covered.get(key, True)).sum())           # (self-overlap: a row whose own triangle is gone does not count)
+        assert changed >= least, (key, changed)
+
+
+def test_the_deep_end_points_reach_every_triangle_with_three_entries_pending_per_record():
+    tri, nodes, expect = T.shape("chain")
+    Q, W = T.shape_queries("chain"), T.shape_expected("chain")
+    deep = Q["deep"]
+    assert deep.stop - deep.start == 16 and deep.start == T.N_QUERIES
+    assert (W["near_all.count"][deep] == tri.shape[0]).all()           # d_max = None, count = True: every triangle is counted
+    assert (Q["lo"][-1] == T.vertices(tri).reshape(-1, 3).min(0)).all() and W["box0.n"][-1] == tri.shape[0]   # the box over everything
+    # with the re-tree off the records are {leaf k, leaf k + 1, leaf k + 2, inner k + 3} for k = 0, 3 .. 57 (tree_shapes' docstring).
+    # For these points the inner slot's box -- everything deeper -- is strictly nearer than each of the three leaves, so the walk
+    # descends it first and pushes the three leaves (each within the radius, which is still +inf: the first triangle is met at
+    # the bottom), and the last record {leaf 60, 61, 62} adds two: 20 * 3 + 2 = 62 entries pending there
+    p = Q["points"][deep]
+    lb = lambda i: (np.maximum(np.maximum(nodes[i, 6:9] - p, p - nodes[i, 9:12]), 0) ** 2).sum(1)
+    inner, leaf = (lambda k: 1 + 2 * k), (lambda k: 2 + 2 * k)
+    for k in range(0, 58, 3):
+        assert nodes[inner(k + 3), 3] == 0 and all(nodes[leaf(k + j), 3] > 0 for j in range(3))
+        assert all((lb(inner(k + 3)) < lb(leaf(k + j))).all() for j in range(3)), k
+    assert expect["stack_need_cp"] == 20 * 3 + 2 and (expect["stack_need_cp"] + 1) * 2 * 64 * 4 == 32256 <= 64 * 1024
+
+
+@pytest.mark.parametrize("name", T.HOST_SHAPES)
+def test_misses_and_empty_rows_are_the_smaller_half(name):
+    """Where the GPU test accepts a miss or an empty row, at most half of the batch is one -- for the seeds of tree_shapes.SEEDS."""
+    tri, nodes, expect = T.shape(name)
+    W = T.shape_expected(name)
+    share = {"closest_point": (W["cp.tri"] < 0).mean(), "closest_point, d_max": (W["cpd.tri"] < 0).mean(),
+             "box_overlap": (W["box0.n"] == 0).mean(), "tri_overlap": (W["trio0.n"] == 0).mean(),
+             "self_overlap": (W["self8.n"] == 0).mean(), "self_overlap, ids": (W["self_ids0.n"] == 0).mean(),
+             "inside": (np.stack([W["crossings%d" % a] for a in T.AXES]).sum(0) == 0).mean()}     # no crossing on any axis
+    for k, count in T.NEAREST:
+        share["nearest %d %s" % (k, count)] = (W["near%d%d.tri" % (k, count)][:, 0] < 0).mean()
+    if tri.shape[0] == 1:                                              # one triangle crosses no other: the rows are empty by definition
+        assert share.pop("self_overlap") == 1.0 and share.pop("self_overlap, ids") == 1.0
+    if tri.shape[0] <= 8:
+        # a handful of triangles: the axis rays of the 257 points of the generator cross none of them, and 300 points a call leave
+        # room for 40 more -- so not half of the batch, but every one of the 40 points next to the triangles has a crossing, and
+        # both answers occur on an axis
+        near = T.shape_queries(name)["near"]
+        crossed = np.stack([W["crossings%d" % a][near] for a in T.AXES])
+        assert near.stop - near.start == T.N_NEAR == 40 and (crossed.sum(0) > 0).all()
+        assert any(8 <= W["inside%d" % a][near].sum() <= 32 for a in T.AXES)
+        assert share.pop("inside") <= 0.9
+    assert max(share.values()) <= 0.5, share
+    assert (W["cp.tri"] < 0).sum() == 16                               # the 16 points that are not finite, and only they
+    assert (W["_d_max.near"] == np.float32(0.75)).sum() >= 64 and np.isfinite(W["_d_max.near"]).mean() > 0.9
+    ties = E.closest_point(T.shape_queries(name)["points"], tri, with_ties=True)[4]
+    if tri.shape[0] > 8:
+        assert (ties > 1).mean() > 0.2                                 # winners decided by the lowest index
+
+
+@pytest.mark.parametrize("name", [n for n in T.HOST_SHAPES if n not in ("root_leaf_1", "root_leaf_8", "two_leaves")])
+def test_the_tie_points_have_boxes_at_the_radius(name):
+    """The tie points: the distance h, the radius h * h of d_max = h, the winner's dist2 and the lb of the winner's own bounding box
+    are one float32.  With leaves of one triangle (median1) the leaf boxes are those bounding boxes: EVERY candidate within the
+    radius is then below a box at lb == radius, so a walk that skipped on lb >= radius would answer with a miss."""
+    tri, nodes, expect = T.shape(name)
+    Q, W = T.shape_queries(name), T.shape_expected(name)
+    ties = Q["ties"]
+    p, h = Q["points"][ties], Q["tie_h"]
+    assert p.shape[0] == T.N_TIES and set(h) == {np.float32(0.25), np.float32(0.5)}
+    assert np.array_equal(W["cp.dist"][ties], h) and np.array_equal(W["_d_max.cp"][ties], h) and np.array_equal(W["_d_max.near"][ties], h)
+    assert (W["cp.tri"][ties] >= 0).all() and np.array_equal(W["cpd.tri"][ties], W["cp.tri"][ties])
+    V = T.vertices(tri)
+    d2 = NE.dist2_all(p, tri)
+    lb = T.box_lb(p[:, None, :], V.min(1)[None], V.max(1)[None])
+    within = d2 <= (h * h)[:, None]
+    assert np.array_equal(within.sum(1), W["near51.count"][ties]) and (within.sum(1) >= 1).all()
+    assert (lb[within] == np.broadcast_to((h * h)[:, None], lb.shape)[within]).all()   # every one of them at lb == radius, none below
+    if name not in ("chain", "uncovered"):                             # (their strip and their subset keep fewer of the copies)
+        assert (within.sum(1) >= 2).sum() >= T.N_TIES // 2             # an exact copy shares the distance: the lowest id wins
+    if name == "median1":
+        leaf = nodes[1:][nodes[1:, 3] == 1]
+        first = leaf[:, 4].astype(int)
+        assert leaf.shape[0] == tri.shape[0] and np.array_equal(leaf[:, 6:9], V.min(1)[first]) and np.array_equal(leaf[:, 9:12], V.max(1)[first])
