@@ -229,6 +229,18 @@ SELF_OVERLAP_ABI = {
 SELF_OVERLAP_MAX = 64  # EZRT_SELF_OVERLAP_MAX
 
 
+# stream-ordered triangle-distance queries on device memory, libezrt_hip.so only (include/ezrt_tri_distance.h); pointers are device
+# addresses
+TRI_DISTANCE_ABI = {
+    # s, tris9, d_max, n, tri_id, dist, point_query, point_scene, crosses, stream
+    "ezrt_query_tri_distance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, tris9, tri_id, n, dist, point_query, point_scene, crosses, stream
+    "ezrt_tri_distance_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -296,7 +308,7 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, REFIT_ABI):
+                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

@@ -292,9 +292,8 @@ EZD bool hit_triangle_t(const float4* __restrict__ g, f3 S, f3 d, float& t_out) 
 // ---- closest-point queries (include/ezrt_closest_point.h, where the definition is the contract): the region form of the
 // point-triangle projection, case by case in the header's order, then q clamped to the triangle's bounding box.  Returns dist2 =
 // dot(p - q, p - q); q and the barycentrics (v, w) of the projection come back by reference.
-EZD float closest_point_triangle(const float4* __restrict__ g, f3 p, f3& q, float& v, float& w) {
-  const float4 ga = g[0], gb = g[1], gc = g[2];
-  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+// (closest_point_abc: the same on vertices held in registers -- the triangle-distance rule below asks it with the roles swapped)
+EZD float closest_point_abc(f3 a, f3 b, f3 c, f3 p, f3& q, float& v, float& w) {
   const f3 ab = b - a, ac = c - a, ap = p - a;
   const float d1 = dot(ab, ap), d2 = dot(ac, ap);
   const f3 bp = p - b;
@@ -335,6 +334,10 @@ EZD float closest_point_triangle(const float4* __restrict__ g, f3 p, f3& q, floa
   const f3 e = p - q;
   return dot(e, e);
 }
+EZD float closest_point_triangle(const float4* __restrict__ g, f3 p, f3& q, float& v, float& w) {
+  const float4 ga = g[0], gb = g[1], gc = g[2];
+  return closest_point_abc(mk(ga.x, ga.y, ga.z), mk(gb.x, gb.y, gb.z), mk(gc.x, gc.y, gc.z), p, q, v, w);
+}
 // The running answer of one query point.  A candidate is a triangle with a finite dist2 <= the bound; the smallest dist2 wins and,
 // among equal dist2, the smallest index -- whatever the order in which the triangles are met.  `best` starts as the bound B
 // (tri = -1): it is the pruning radius of the walk from the first step on.
@@ -361,6 +364,41 @@ EZD void closest_point_candidate(ClosestBest& r, const float4* __restrict__ tri_
 EZD float closest_point_box(f3 p, f3 lo, f3 hi) {
   const f3 g = mk(__builtin_fmaxf(__builtin_fmaxf(lo.x - p.x, 0.0f), p.x - hi.x), __builtin_fmaxf(__builtin_fmaxf(lo.y - p.y, 0.0f), p.y - hi.y),
                   __builtin_fmaxf(__builtin_fmaxf(lo.z - p.z, 0.0f), p.z - hi.z));
+  return dot(g, g);
+}
+// ... and of a box against the query triangle's bounding box [qlo, qhi] (include/ezrt_tri_distance.h): g = max(lo - qhi, 0, qlo - hi)
+// per axis.  For a box that holds the bounding box of a triangle, lb <= that pair's dist2 on the bits (ezrt_point_queries.h:
+// tri_distance_kernel).
+EZD float tri_distance_box(f3 qlo, f3 qhi, f3 lo, f3 hi) {
+  const f3 g = mk(__builtin_fmaxf(__builtin_fmaxf(lo.x - qhi.x, 0.0f), qlo.x - hi.x), __builtin_fmaxf(__builtin_fmaxf(lo.y - qhi.y, 0.0f), qlo.y - hi.y),
+                  __builtin_fmaxf(__builtin_fmaxf(lo.z - qhi.z, 0.0f), qlo.z - hi.z));
+  return dot(g, g);
+}
+// The closest points of the closed segments [P1, Q1] and [P2, Q2], in the order of include/ezrt_tri_distance.h: x on the first, y on
+// the second, each clamped to its segment's bounding box.  Returns dot(x - y, x - y).
+EZD float seg_clamp01(float v) { return ez_min(ez_max(v, 0.0f), 1.0f); }
+EZD f3 seg_point(f3 P, f3 Q, f3 d, float s) {
+  const f3 r = P + d * s;
+  const f3 lo = mk(ez_min(P.x, Q.x), ez_min(P.y, Q.y), ez_min(P.z, Q.z)), hi = mk(ez_max(P.x, Q.x), ez_max(P.y, Q.y), ez_max(P.z, Q.z));
+  return mk(r.x < lo.x ? lo.x : (r.x > hi.x ? hi.x : r.x), r.y < lo.y ? lo.y : (r.y > hi.y ? hi.y : r.y),
+            r.z < lo.z ? lo.z : (r.z > hi.z ? hi.z : r.z));
+}
+EZD float segment_segment_closest(f3 P1, f3 Q1, f3 P2, f3 Q2, f3& x, f3& y) {
+  const f3 d1 = Q1 - P1, d2 = Q2 - P2, r = P1 - P2;
+  const float a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r), c = dot(d1, r), b = dot(d1, d2);
+  const float den = a * e - b * b;
+  float s = den > 0.0f ? seg_clamp01((b * f - c * e) / den) : 0.0f;
+  float t = (b * s + f) / e;
+  if (t < 0.0f) {
+    t = 0.0f;
+    s = seg_clamp01(-c / a);
+  } else if (t > 1.0f) {
+    t = 1.0f;
+    s = seg_clamp01((b - c) / a);
+  }
+  x = seg_point(P1, Q1, d1, s);
+  y = seg_point(P2, Q2, d2, t);
+  const f3 g = x - y;
   return dot(g, g);
 }
 
@@ -781,6 +819,65 @@ EZD void hit_bvh(const DevScene& sc, f3 S, f3 d, int* __restrict__ stack, int32_
     sp--;
     ref = (uint32_t)stack[sp * STRIDE];
   }
+}
+
+// ---- triangle-distance queries (include/ezrt_tri_distance.h, where the definition is the contract): the pair rule of one scene
+// triangle against a LIVE query triangle -- q from tri_query, p1 p2 p3 its vertices as the caller gave them.  The 15 sub-candidates in
+// the header's order (vertices of Q against the triangle, its vertices against Q, the nine edge pairs with Q's edge outer), the first
+// smallest finite d2 wins and supplies (x, y); then the crossing step.  False: the pair is no candidate (the triangle is not live, or
+// no d2 is finite).  The loops are not unrolled and a vertex or an edge is picked from the registers by its index, as in
+// tri_overlaps: one sub-candidate's state is held at a time.
+EZD f3 tri_corner(int i, f3 a, f3 b, f3 c) { return mk(i == 0 ? a.x : (i == 1 ? b.x : c.x), i == 0 ? a.y : (i == 1 ? b.y : c.y), i == 0 ? a.z : (i == 1 ? b.z : c.z)); }
+EZD bool tri_distance_pair(const float4* __restrict__ tg, const TriQuery& q, f3 p1, f3 p2, f3 p3, float& dist2, f3& x, f3& y, bool& crosses) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  TriSorted s;
+  if (!tri_live(a, b, c, s)) return false;
+  const float inf = __builtin_inff();
+  float best = inf;
+  bool found = false;
+  auto take = [&](float d2, f3 cx, f3 cy) {
+    if (d2 < inf && (!found || d2 < best)) best = d2, x = cx, y = cy, found = true; // (false for a NaN d2; the first wins on equality)
+  };
+#pragma unroll 1
+  for (int i = 0; i < 6; i++) {
+    const bool scene = i >= 3; // the vertices of Q against the triangle, then the triangle's against Q
+    const int j = scene ? i - 3 : i;
+    const f3 p = tri_corner(j, scene ? a : p1, scene ? b : p2, scene ? c : p3);
+    f3 qq;
+    float v, w;
+    const float d2 = closest_point_abc(scene ? p1 : a, scene ? p2 : b, scene ? p3 : c, p, qq, v, w);
+    take(d2, scene ? qq : p, scene ? p : qq);
+  }
+#pragma unroll 1
+  for (int ij = 0; ij < 9; ij++) {
+    const int i = ij / 3, j = ij - 3 * i;
+    f3 cx, cy;
+    const float d2 = segment_segment_closest(tri_corner(i, p1, p2, p3), tri_corner(i, p2, p3, p1), tri_corner(j, a, b, c), tri_corner(j, b, c, a), cx, cy);
+    take(d2, cx, cy);
+  }
+  if (!found) return false;
+  crosses = tri_overlaps(tg, q);
+  dist2 = crosses ? 0.0f : best;
+  return true;
+}
+// The running answer of one query triangle, as ClosestBest is a point's: `best` starts as the bound B (tri = -1) and is the pruning
+// radius of the walk from the first step on.  The smallest dist2 wins; among equal dist2 a pair that crosses comes before one that
+// does not (possible at dist2 = 0 alone: a sub-candidate of a pair that is apart by less than fp32 resolves may round to 0), then the
+// smallest index -- whatever the order in which the triangles are met.
+struct TriDistanceBest {
+  float best;
+  int32_t tri;
+  f3 x, y;
+  bool crosses;
+};
+EZD void tri_distance_candidate(TriDistanceBest& r, const float4* __restrict__ tri_geom, int32_t k, const TriQuery& q, f3 p1, f3 p2, f3 p3) {
+  f3 x, y;
+  float d2;
+  bool crosses;
+  if (!tri_distance_pair(tri_geom + (size_t)k * 3, q, p1, p2, p3, d2, x, y, crosses)) return;
+  if (d2 < r.best || (d2 == r.best && (r.tri < 0 || (crosses && !r.crosses) || (crosses == r.crosses && k < r.tri))))
+    r.best = d2, r.tri = k, r.x = x, r.y = y, r.crosses = crosses;
 }
 
 // ---------------------------------------------------------------------------

@@ -1,9 +1,10 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
-// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap and
-// self-overlap queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h).  One query point, box
-// or triangle per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
+// self-overlap and triangle-distance queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h,
+// include/ezrt_tri_distance.h).  One query point, box or triangle per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
-//   point_walk                       the best-first walk over the 4-wide records that closest point, nearest and signed distance share
+//   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
+//                                    triangle distance share: the lower bound of a slot's box is the caller's
 //   closest_point_kernel<WALK>       closest_point_search + closest_point_store
 //   nearest_kernel<WALK, COUNT>      point_walk carrying a K-entry sorted list instead of one winner
 //   closest_point_at_kernel          closest_point_triangle for pairs the caller holds
@@ -17,6 +18,8 @@
 //   tri_overlap_at_kernel            tri_overlaps for pairs the caller holds
 //   self_overlap_kernel<WALK>        overlap_rows with a scene triangle's bounding box as the gate and self_crosses as the rule
 //   self_overlap_at_kernel           self_crosses for pairs of ids the caller holds
+//   tri_distance_kernel<WALK>        point_walk with tri_distance_box as the bound and tri_distance_pair as the rule
+//   tri_distance_at_kernel           tri_distance_pair for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -52,7 +55,8 @@ EZD bool point_bound(f3 p, const float* d_max, uint32_t i, float& B) {
 // 4-WIDE records (ezrt_records.h) -- chosen over the binary records because one 128-byte line gives four boxes, so a point needs
 // half the dependent loads on its way down, and because their boxes qualify: a slot's box is a caller's node box (nested, its
 // leaves hold their triangles) or an exact union of caller leaf boxes (retree_leaves, and every box after a refit), i.e. a
-// superset of the bounding box of every triangle below it.  The four slots are sorted by lb (closest_point_box), the walk goes on
+// superset of the bounding box of every triangle below it.  The four slots are sorted by lb = bound(lo, hi) -- the caller's lower
+// bound of the dist2 of every triangle below the box: closest_point_box for a point, tri_distance_box for a triangle --, the walk goes on
 // with the nearest and pushes the others, farthest first, as {lb, ref} pairs on the lane's LDS stack column (two rows per entry:
 // entry sp at rows 2 sp and 2 sp + 1, stride CP_BLOCK; launched with 2 * (stack_need_cp + 1) rows: the exact worst case when any
 // slot may be the nearest, + 1 of slack).  A slot is skipped only when lb > radius -- on equality it is descended: the tie rules
@@ -63,12 +67,13 @@ EZD bool point_bound(f3 p, const float* d_max, uint32_t i, float& B) {
 // |fl(p - q)| = fl(q - p), so |e| >= g (the same on the hi side).  fl(x * x) is monotone in |x| and fl(fl(X + Y) + Z) in each of
 // X, Y, Z >= 0, so lb = dot(g, g) <= dot(e, e) = dist2_T ON THE BITS, overflow to +inf included.  Hence a skipped subtree holds no
 // triangle with dist2 <= radius: with a radius that no candidate's dist2 exceeds, neither a winner nor a tie is lost, and the order
-// of the visits is the caller's to be indifferent to.  p is finite.
+// of the visits is the caller's to be indifferent to.  p is finite.  (The same for a query triangle, with its bounding box in the
+// place of p: tri_distance_kernel.)
 // The stack: a pop only removes, so below a record with m slots at most m - 1 entries of it are pending while one child subtree is
 // walked -- stack_need_cp = the fold of (m - 1 + deepest child) -- whatever the radius admits: a wider radius pushes more of the
 // m - 1, never more than them.
-template <bool RECHECK, class Radius, class Visit>
-EZD void point_walk(const float4* __restrict__ inner4, f3 p, int* __restrict__ stack, Radius radius, Visit visit) {
+template <bool RECHECK, class Bound, class Radius, class Visit>
+EZD void point_walk(const float4* __restrict__ inner4, Bound bound, int* __restrict__ stack, Radius radius, Visit visit) {
   const float inf = __builtin_inff();
   int sp = 0;
   uint32_t ref = 0u;
@@ -82,8 +87,8 @@ EZD void point_walk(const float4* __restrict__ inner4, f3 p, int* __restrict__ s
       const float4* rec = inner4 + (size_t)(ref & REF_INDEX) * N4_FLOAT4;
       const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
       const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
-      float l[4] = {closest_point_box(p, mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x)), closest_point_box(p, mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y)),
-                    closest_point_box(p, mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z)), closest_point_box(p, mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w))};
+      float l[4] = {bound(mk(ax.x, ay.x, az.x), mk(bx.x, by.x, bz.x)), bound(mk(ax.y, ay.y, az.y), mk(bx.y, by.y, bz.y)),
+                    bound(mk(ax.z, ay.z, az.z), mk(bx.z, by.z, bz.z)), bound(mk(ax.w, ay.w, az.w), mk(bx.w, by.w, bz.w))};
       uint32_t r[4] = {__float_as_uint(rf.x), __float_as_uint(rf.y), __float_as_uint(rf.z), __float_as_uint(rf.w)};
       // (an unused slot -- an all-NaN box -- gets lb = inf: never descended)
 #pragma unroll
@@ -129,14 +134,20 @@ EZD void point_walk(const float4* __restrict__ inner4, f3 p, int* __restrict__ s
 }
 // visit(k) for every triangle that may hold a candidate.  WALK = true, the pruned route: point_walk, then the triangles that no leaf
 // holds (a caller's array may have some).  WALK = false, the sweep route: tri_geom[0 .. n_tri), no tree, for scenes that do not prune.
-template <bool WALK, bool RECHECK, class Radius, class Visit>
-EZD void point_visit(const PointScene& sc, f3 p, int* __restrict__ stack, Radius radius, Visit visit) {
+// bound(lo, hi) is the walk's lower bound of a box.
+template <bool WALK, bool RECHECK, class Bound, class Radius, class Visit>
+EZD void bound_visit(const PointScene& sc, Bound bound, int* __restrict__ stack, Radius radius, Visit visit) {
   if (WALK) {
-    point_walk<RECHECK>(sc.inner4, p, stack, radius, visit);
+    point_walk<RECHECK>(sc.inner4, bound, stack, radius, visit);
     for (int u = 0; u < sc.n_uncovered; u++) visit(sc.uncovered[u]);
   } else {
     for (int k = 0; k < sc.n_tri; k++) visit(k);
   }
+}
+// ... for a query point p: the bound is closest_point_box
+template <bool WALK, bool RECHECK, class Radius, class Visit>
+EZD void point_visit(const PointScene& sc, f3 p, int* __restrict__ stack, Radius radius, Visit visit) {
+  bound_visit<WALK, RECHECK>(sc, [&](f3 lo, f3 hi) { return closest_point_box(p, lo, hi); }, stack, radius, visit);
 }
 
 // ---- closest-point queries (include/ezrt_closest_point.h).  The radius of the walk is the best dist2 of the moment, which
@@ -628,6 +639,93 @@ __global__ __launch_bounds__(256) void self_overlap_at_kernel(PointScene sc, con
   bool o = false;
   if (ta != tb && (uint32_t)tb < (uint32_t)sc.n_tri && self_query(sc, ta, q)) o = self_crosses(sc.tri_geom + (size_t)tb * 3, q);
   crosses[i] = o ? 1u : 0u;
+}
+
+// ---- triangle-distance queries (include/ezrt_tri_distance.h).
+//
+// tri_distance_kernel<WALK>: one query triangle per lane.  WALK = true, the pruned route: point_walk on the lane's stack column of
+// 2 * (stack_need_cp + 1) rows, with the running best dist2 as the radius (RECHECK) and, as the lower bound of a slot's box [lo, hi],
+// tri_distance_box against the query triangle's own fp32 bounding box [q.lo, q.hi]: lb = dot(g, g), g = max(lo - q.hi, 0, q.lo - hi).
+// Why no margin is needed: every x of tri_distance_pair is a vertex of Q or a point clamped to the bounding box of Q or of one of its
+// edges, so x lies in [q.lo, q.hi] per axis; every y is a vertex of the scene triangle or clamped to its bounding box or an edge's,
+// which lies in every box above the triangle (the scene prunes).  Per axis either g = 0 <= |e|, or g = fl(lo - q.hi) with
+// y >= lo > q.hi >= x: y - x >= lo - q.hi in the reals, rounding is monotone and |fl(x - y)| = fl(y - x), so |e| >= g (the same on
+// the other side).  fl(x * x) is monotone in |x| and fl(fl(X + Y) + Z) in each of X, Y, Z >= 0, so lb <= d2 ON THE BITS for every
+// finite sub-candidate, overflow included, hence lb <= the smallest of them; and a pair that crosses (dist2 = 0) passes T1, so its
+// boxes overlap on every axis and lb = 0.  A skipped subtree therefore holds no pair with dist2 <= radius, neither a winner nor a tie.
+// The pair gate: before the 15 sub-candidates and the fp64 tri_overlaps, the same lb of triangle k's OWN bounding box; a triangle
+// with lb > best cannot win or tie, by the same inequality, so skipping it changes no result.  (A NaN lb -- a NaN vertex -- fails the
+// comparison and goes on to tri_distance_pair, which finds the triangle not live.)
+// Triangles that no leaf holds are swept after the walk.  WALK = false, the sweep route: every triangle, no tree.
+struct TriDistanceArgs {
+  PointScene sc;
+  const float* tris;        // n x 9
+  const float* d_max;       // n, or null
+  uint32_t n;
+  int32_t* tri;             // n
+  float* dist;              // n, or null
+  float* point_query;       // n x 3, or null
+  float* point_scene;       // n x 3, or null
+  uint8_t* crosses;         // n, or null
+};
+// row i of the outputs; tri < 0 writes the miss (-1, +inf, zeros, zeros, 0: the caller keeps x, y and crosses zero then)
+EZD void tri_distance_store(float* dist, float* point_query, float* point_scene, uint8_t* crosses, uint32_t i, const TriDistanceBest& r) {
+  if (dist) dist[i] = r.tri >= 0 ? __builtin_sqrtf(r.best) : __builtin_inff();
+  if (point_query) st3(point_query + (size_t)i * 3, r.x);
+  if (point_scene) st3(point_scene + (size_t)i * 3, r.y);
+  if (crosses) crosses[i] = r.crosses ? 1u : 0u;
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void tri_distance_kernel(TriDistanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const float* t = a.tris + (size_t)i * 9;
+  const f3 p1 = ld3(t), p2 = ld3(t + 3), p3 = ld3(t + 6);
+  TriDistanceBest r;
+  r.tri = -1;
+  r.x = r.y = mk(0.0f, 0.0f, 0.0f);
+  r.crosses = false;
+  r.best = __builtin_inff();
+  bool live = true;
+  if (a.d_max) { // B = d_max^2; a negative or NaN d_max gives no candidates
+    const float dm = a.d_max[i];
+    if (dm >= 0.0f) r.best = dm * dm;
+    else live = false;
+  }
+  TriQuery q;
+  if (live && tri_query(p1, p2, p3, q))
+    bound_visit<WALK, true>(
+        a.sc, [&](f3 lo, f3 hi) { return tri_distance_box(q.lo, q.hi, lo, hi); }, lds_stack + threadIdx.x, [&] { return r.best; },
+        [&](int32_t k) {
+          const float4* g = a.sc.tri_geom + (size_t)k * 3;
+          const float4 ga = g[0], gb = g[1], gc = g[2];
+          const f3 lo = mk(ez_min(ez_min(ga.x, gb.x), gc.x), ez_min(ez_min(ga.y, gb.y), gc.y), ez_min(ez_min(ga.z, gb.z), gc.z));
+          const f3 hi = mk(ez_max(ez_max(ga.x, gb.x), gc.x), ez_max(ez_max(ga.y, gb.y), gc.y), ez_max(ez_max(ga.z, gb.z), gc.z));
+          if (tri_distance_box(q.lo, q.hi, lo, hi) > r.best) return; // the pair gate
+          tri_distance_candidate(r, a.sc.tri_geom, k, q, p1, p2, p3);
+        });
+  a.tri[i] = r.tri;
+  tri_distance_store(a.dist, a.point_query, a.point_scene, a.crosses, i, r);
+}
+
+// ezrt_tri_distance_at_device: tri_distance_pair for pairs the caller holds -- query triangle i against triangle tri_id[i].  An id
+// outside the scene, a triangle that is not live on either side or a pair without a finite sub-candidate writes (+inf, zeros, zeros, 0).
+__global__ __launch_bounds__(256) void tri_distance_at_kernel(const float4* tri_geom, int32_t n_tri, const float* tris, const int32_t* tri_id,
+                                                              uint32_t n, float* dist, float* point_query, float* point_scene, uint8_t* crosses) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  const float* t = tris + (size_t)i * 9;
+  const f3 p1 = ld3(t), p2 = ld3(t + 3), p3 = ld3(t + 6);
+  TriDistanceBest r;
+  r.tri = -1;
+  r.x = r.y = mk(0.0f, 0.0f, 0.0f);
+  r.crosses = false;
+  r.best = __builtin_inff();
+  TriQuery q;
+  if ((uint32_t)tri < (uint32_t)n_tri && tri_query(p1, p2, p3, q)) tri_distance_candidate(r, tri_geom, tri, q, p1, p2, p3);
+  tri_distance_store(dist, point_query, point_scene, crosses, i, r);
 }
 
 } // namespace ezd

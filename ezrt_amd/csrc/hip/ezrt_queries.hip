@@ -1,7 +1,8 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap, triangle-overlap and self-overlap queries (include/ezrt_closest_point.h,
-// ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h).  A translation unit of its own: none of its kernels is compiled together
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap and triangle-distance queries
+// (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h,
+// ezrt_tri_distance.h).  A translation unit of its own: none of its kernels is compiled together
 // with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run
 // the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in
 // ezrt_launch.hip.  DESIGN.md 5.
@@ -15,6 +16,7 @@
 #include "ezrt_box_overlap.h"
 #include "ezrt_tri_overlap.h"
 #include "ezrt_self_overlap.h"
+#include "ezrt_tri_distance.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -478,6 +480,48 @@ int ezrt_self_overlap_at_device(EzrtScene* s, const int32_t* tri_a, const int32_
       PointScene sc;
       point_scene(s, sc);
       hipLaunchKernelGGL(self_overlap_at_kernel, g, b, 0, st, sc, tri_a, tri_b, (uint32_t)n, crosses);
+    });
+  });
+}
+
+// ---- triangle-distance queries on device memory (include/ezrt_tri_distance.h): one kernel each on `st`, no scratch; checked,
+// launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_tri_distance_device(EzrtScene* s, const float* tris9, const float* d_max, int n, int32_t* tri_id, float* dist,
+                                   float* point_query, float* point_scene, uint8_t* crosses, void* stream) {
+  return ezi::guarded("ezrt_query_tri_distance_device", [&]() -> int {
+    if (!s || !tris9 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tris9, N * 9 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {dist, N * sizeof(float)},
+                          {point_query, N * 3 * sizeof(float)}, {point_scene, N * 3 * sizeof(float)}, {crosses, N}}, N, st, [&](dim3, dim3) {
+      TriDistanceArgs a;
+      const PointRoute r = ::point_scene(s, a.sc); // (the function: the parameter of that name is the output)
+      a.tris = tris9;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.tri = tri_id;
+      a.dist = dist;
+      a.point_query = point_query;
+      a.point_scene = point_scene;
+      a.crosses = crosses;
+      launch_routed(tri_distance_kernel<true>, tri_distance_kernel<false>, r, r.lds, N, st, a);
+    });
+  });
+}
+int ezrt_tri_distance_at_device(EzrtScene* s, const float* tris9, const int32_t* tri_id, int n, float* dist, float* point_query,
+                                float* point_scene, uint8_t* crosses, void* stream) {
+  return ezi::guarded("ezrt_tri_distance_at_device", [&]() -> int {
+    if (!s || !tris9 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!dist && !point_query && !point_scene && !crosses)
+      return fail(EZRT_ERR_INVALID, "one of dist, point_query, point_scene and crosses is required");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tris9, N * 9 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {dist, N * sizeof(float)},
+                          {point_query, N * 3 * sizeof(float)}, {point_scene, N * 3 * sizeof(float)}, {crosses, N}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(tri_distance_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tris9, tri_id, (uint32_t)n, dist, point_query,
+                         point_scene, crosses);
     });
   });
 }

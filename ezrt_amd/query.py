@@ -1,6 +1,6 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
-include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h).
+include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -20,10 +20,12 @@ include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h).
     crosses = query.tri_overlap_at(scene, tris, tri)             # ... the same test for pairs already held  (bool)
     tri, n_overlap = query.self_overlap(scene, max_k=8)          # where the mesh crosses itself (include/ezrt_self_overlap.h)
     crosses = query.self_overlap_at(scene, a, b)                 # ... the same test for pairs of triangle ids already held  (bool)
+    tri, dist, point_query, point_scene, crosses = query.tri_distance(scene, tris, d_max)   # how close each triangle comes to the mesh
+    tri, dist, point_query, point_scene, crosses = query.tri_distance_at(scene, tris, tri)  # ... for pairs already held (include/ezrt_tri_distance.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
-`d_max` (optional) a float32 GPU tensor of shape points.shape[:-1]; `lo` and `hi` are contiguous float32 GPU tensors of one shape
+`d_max` (optional) a float32 GPU tensor of shape points.shape[:-1] (tris.shape[:-1] for `tri_distance`); `lo` and `hi` are contiguous float32 GPU tensors of one shape
 [..., 3], the corners of axis-aligned boxes; `tris` is a contiguous float32 GPU tensor of shape [..., 9] (p1 p2 p3).  The outputs
 keep the leading dimensions.  The work is enqueued on
 `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the rays' device) and the functions
@@ -47,6 +49,7 @@ SignedDistance = collections.namedtuple("SignedDistance", "tri point dist bary i
 BoxOverlap = collections.namedtuple("BoxOverlap", "tri n_overlap")
 TriOverlap = collections.namedtuple("TriOverlap", "tri n_overlap")
 SelfOverlap = collections.namedtuple("SelfOverlap", "tri n_overlap")
+TriDistance = collections.namedtuple("TriDistance", "tri dist point_query point_scene crosses")
 
 
 def _scene_lib(scene, abi):
@@ -571,3 +574,62 @@ def self_overlap_at(scene, a, b, stream=None):
     _call(scene, lib.ezrt_self_overlap_at_device(scene._h, P(a.data_ptr()), P(b.data_ptr()), n, P(out.data_ptr()), P(h)))
     _keep((a, b, out), ts, a)
     return out.view(torch.bool)
+
+
+def tri_distance(scene, tris, d_max=None, stream=None):
+    """TriDistance(tri int32 [...], dist float32 [...], point_query float32 [..., 3], point_scene float32 [..., 3], crosses bool
+    [...]): for every triangle of `tris` (a contiguous float32 GPU tensor [..., 9]: p1 p2 p3) the nearest triangle of the scene, the
+    distance between the two, and the points where they come closest -- `point_query` on the query triangle, `point_scene` on the
+    scene's.  The distance is taken over vertex against face, both ways, and edge against edge; where the two triangles cross or
+    touch by `tri_overlap`'s test it is 0 and `crosses` is set, and the two points are then the nearest features, not a common
+    point.  `d_max` (optional, float32, of shape tris.shape[:-1]) admits only triangles within that distance: a clearance check.  A
+    miss is (-1, +inf, zeros, zeros, False).  Equal distances: a triangle that crosses first, then the lowest triangle index, so
+    `crosses` is True exactly where `tri_overlap` finds something, and `tri` is then its row's first entry.  A triangle with a non-finite number or with
+    collinear or repeated vertices misses as a query and is never found in the scene.  The definition, on the bits:
+    include/ezrt_tri_distance.h; `tri_distance_at` evaluates pairs."""
+    n = _check_tris(tris)
+    if d_max is not None:
+        _tensor("d_max", d_max, torch.float32, tris.shape[:-1], device=tris.device)
+    lead = tuple(tris.shape[:-1])
+    lib = _scene_lib(scene, _abi.TRI_DISTANCE_ABI)
+    tri = torch.empty(lead, dtype=torch.int32, device=tris.device)
+    dist = torch.empty(lead, dtype=torch.float32, device=tris.device)
+    point_query = torch.empty(lead + (3,), dtype=torch.float32, device=tris.device)
+    point_scene = torch.empty(lead + (3,), dtype=torch.float32, device=tris.device)
+    crosses = torch.empty(lead, dtype=torch.uint8, device=tris.device)
+    if n == 0:
+        return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+    h, ts = _stream(tris, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_tri_distance_device(scene._h, P(tris.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n,
+                                                    P(tri.data_ptr()), P(dist.data_ptr()), P(point_query.data_ptr()),
+                                                    P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
+    _keep((tris, d_max, tri, dist, point_query, point_scene, crosses), ts, tris)
+    return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+
+
+def tri_distance_at(scene, tris, tri, stream=None):
+    """TriDistance(tri, dist float32 tri.shape, point_query float32 tri.shape + (3,), point_scene float32 tri.shape + (3,), crosses
+    bool tri.shape): for triangle tri[...] of the scene and its query triangle, what `tri_distance` gives for its winner.  `tri`
+    (int32) has the shape tris.shape[:-1], or one trailing dimension more -- rows of `tri_overlap` or `nearest` -- and every entry of
+    a row then belongs to the row's query triangle.  An id that is no triangle of the scene (an unused slot, -1) or a triangle that
+    is not live on either side gives (+inf, zeros, zeros, False).  `tri` is returned as given."""
+    _check_tris(tris)
+    lib = _scene_lib(scene, _abi.TRI_DISTANCE_ABI)
+    lead = tuple(tris.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=tris.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    dist = torch.empty(shape, dtype=torch.float32, device=tris.device)
+    point_query = torch.empty(shape + (3,), dtype=torch.float32, device=tris.device)
+    point_scene = torch.empty(shape + (3,), dtype=torch.float32, device=tris.device)
+    crosses = torch.empty(shape, dtype=torch.uint8, device=tris.device)
+    if n == 0:
+        return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+    h, ts = _stream(tris, stream)
+    per = _per_entry(tris, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_tri_distance_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(dist.data_ptr()),
+                                                 P(point_query.data_ptr()), P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
+    _keep((tris, per, tri, dist, point_query, point_scene, crosses), ts, tris)
+    return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
