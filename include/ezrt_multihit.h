@@ -11,7 +11,8 @@
  *
  * The list of a ray.  The reference's hitBVH (P5/fsh:254-306) does not prune: which triangles a ray is tested against is fixed by
  * the tree, and in which order by the ray.  Let V be the sequence of triangles hitBVH hands to hitTriangle for ray i, in the order
- * it reaches them: the nearer child first (a tie: the right one), a leaf's range in ascending index, no pruning of any kind.  Let H
+ * it reaches them: the nearer child first (a tie: the right one), a leaf's range in ascending index, no pruning of any kind.  A ray
+ * sees only the triangles below a leaf: a triangle below no leaf of the caller's node array is in no V and in no list.  Let H
  * be the members of V with isHit and t < min(t_max[i], EZ_INF) (EZ_INF = 114514, ezrt_detmath.h; t_max == NULL: the bound is
  * EZ_INF; a NaN t_max: H is empty), sorted by t ascending with a STABLE sort: equal t keep their visit order.
  *

@@ -6,7 +6,10 @@
  * boxes are not nested) and return exactly the reference's answers.
  *
  * "The reference's hit" of a ray means exactly what ezrt_query_hits (ezrt.h) returns for it: {tri, t}, and on a miss tri = -1 and
- * t = EZ_INF (114514, the reference's "infinity", ezrt_detmath.h).  Every hit has t < EZ_INF.
+ * t = EZ_INF (114514, the reference's "infinity", ezrt_detmath.h).  Every hit has t < EZ_INF.  That is hitBVH on the caller's node
+ * array: a ray sees only the triangles below a leaf it reaches -- a triangle below no leaf is never hit (the point and overlap
+ * queries sweep such triangles; the ray queries do not) -- and of two triangles at one distance the one whose leaf the reference's
+ * walk reaches first wins.
  *
  *   rays_od6   n_rays x 6 floats: origin, direction (any length; not normalised by the library)
  *   t_max      n_rays floats, or NULL (= +inf for every ray)

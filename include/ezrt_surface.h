@@ -18,6 +18,8 @@
  *   inside[i]                1 if dot(N_geom, d) > 0 (the ray meets the triangle's back), else 0; N_geom = normalize(cross(p2 - p1,
  *                            p3 - p1))
  * For a miss -- including a hit at t >= t_max and a ray whose t_max no hit can beat -- hit_point, normal and inside are zeros.
+ * As in ezrt_query.h a ray sees only the triangles below a leaf of the caller's node array: a triangle below no leaf is never the
+ * winner.  (ezrt_surface_at_device, ezrt_multihit.h, takes any triangle id of the scene: it walks no tree.)
  *
  * There is no material output: the winner's material is tri36[tri_id * 36 + 18 .. + 36) of the caller's own triangle array.
  *

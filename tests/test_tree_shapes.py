@@ -197,3 +197,101 @@ def test_the_tie_points_have_boxes_at_the_radius(name):
         leaf = nodes[1:][nodes[1:, 3] == 1]
         first = leaf[:, 4].astype(int)
         assert leaf.shape[0] == tri.shape[0] and np.array_equal(leaf[:, 6:9], V.min(1)[first]) and np.array_equal(leaf[:, 9:12], V.max(1)[first])
+
+
+# ---- the rays of tests/test_gpu_tree_shapes_rays.py: conditions on the inputs, on the CPU oracle alone -- they hit, the tie rays tie
+# (across leaves, and for the higher index on the median tree), slot 0 of the restated all-hits list is the oracle's closest hit, the
+# triangles that no leaf holds change the answers, and the chain's rays leave 48 entries pending
+
+LARGE = [n for n in T.HOST_SHAPES if n not in ("root_leaf_1", "root_leaf_8", "two_leaves")]
+TIES_AT_LEAST = dict(sah8=0.5, median1=0.5, leaf128=0.5, chain=0.5, loose=0.5, leaf_misses=0.5, uncovered=0.4)
+
+
+_same = T.RS.same_bits                                                  # equal on the bits, NaN equal to NaN
+
+
+def _leaf_of(nodes, n_tri):
+    """int [n_tri]: the node whose leaf holds each triangle (-1: none)"""
+    leaf = np.full(n_tri, -1)
+    for i in range(1, nodes.shape[0]):
+        if nodes[i, 3] > 0:
+            leaf[int(nodes[i, 4]):int(nodes[i, 4] + nodes[i, 3])] = i
+    return leaf
+
+
+@pytest.mark.parametrize("name", T.HOST_SHAPES)
+def test_the_rays_hit_and_slot_0_is_the_oracles_closest_hit(oracle, name):
+    tri, nodes, expect = T.shape(name)
+    Q, X = T.ray_queries(name), T.ray_expected(oracle, name)
+    n = Q["rays"].shape[0]
+    sizes = {k: v.stop - v.start for k, v in Q.items() if isinstance(v, slice)}
+    assert n % 64 == 1 and 500 <= n <= 1100 and sum(sizes.values()) == n, sizes
+    large = tri.shape[0] > 8
+    assert sizes["broad"] == T.N_BROAD and sizes["near"] == T.N_NEAR_RAYS
+    assert sizes["ties"] == (T.N_TIE_RAYS if large else 0) and sizes["on_uncovered"] == (T.N_ON_UNCOVERED if name == "uncovered" else 0)
+    assert (sizes["deep"], sizes["shallow"]) == ((T.N_CHAIN_DEEP, T.N_CHAIN_SHALLOW) if name == "chain" else (0, 0)) and sizes["pad"] < 64
+    hit = X["closest.tri"] >= 0
+    count = X["all64.count"]
+    print("%s: %d rays %s; hits: near %.3f, batch %.3f; all-hits count > 5: %.3f, largest %d" % (
+        name, n, sizes, hit[Q["near"]].mean(), hit.mean(), (count > 5).mean(), count.max()))
+    assert hit[Q["near"]].mean() >= 0.95 and 0.2 <= hit.mean() <= 0.99
+    assert count.max() <= 64
+    if large:
+        assert (count > 5).mean() >= 0.05
+    # slot 0 of the restated list is the oracle's own closest hit, on every ray: the restatement is pinned to ezrt_query_hits here
+    assert np.array_equal(X["all64.tri"][:, 0], X["closest.tri"]) and _same(X["all64.t"][:, 0], X["closest.t"])
+    assert np.array_equal(count > 0, X["occluded"]) and np.array_equal(X["all1.count"], count)
+    for key in T.T_MAX:                                                # ... and under every derived t_max
+        assert np.array_equal(X["all64[%s].tri" % key][:, 0], X["closest[%s].tri" % key]), key
+        assert _same(X["all64[%s].t" % key][:, 0], X["closest[%s].t" % key]) and np.array_equal(X["all2[%s].count" % key] > 0, X["occluded[%s]" % key])
+    assert not X["occluded[own]"].any() and np.array_equal(X["occluded[above]"], hit) and not X["occluded[nan]"].any()
+    if large:
+        assert 0 < X["occluded[second]"].sum() < hit.sum()             # the second hit's t: admits the first unless the two tie
+
+
+@pytest.mark.parametrize("name", LARGE)
+def test_the_tie_rays_tie_at_the_nearest_hit(oracle, name):
+    tri, nodes, expect = T.shape(name)
+    Q, X = T.ray_queries(name), T.ray_expected(oracle, name)
+    ties = Q["ties"]
+    ids, t = X["all64.tri"][ties], X["all64.t"][ties]
+    tied = (ids[:, 1] >= 0) & (t[:, 0] == t[:, 1])
+    leaf = _leaf_of(nodes, tri.shape[0])
+    across = tied & (leaf[ids[:, 0]] != leaf[np.maximum(ids[:, 1], 0)])
+    higher = across & (ids[:, 0] > ids[:, 1])
+    print("%s: of %d tie rays, tied at the nearest hit %.3f, partners in different leaves %.3f, and the winner has the higher index %.3f"
+          % (name, tied.size, tied.mean(), across.mean(), higher.mean()))
+    assert tied.mean() >= TIES_AT_LEAST[name]
+    if name == "median1":
+        assert higher.mean() >= 0.5                                    # where "the lower index wins" is the wrong answer
+    if name == "chain":
+        assert across.mean() >= 0.3
+
+
+def test_the_ray_contract_differs_from_the_point_queries_on_triangles_that_no_leaf_holds(oracle):
+    """A ray sees the triangles below a leaf and no others: for a share of the rays aimed at the uncovered triangles, a brute force
+    over ALL triangles has an uncovered one nearest while hitBVH on the caller's tree answers another distance (or a miss)."""
+    tri, nodes, expect = T.shape("uncovered")
+    Q, X = T.ray_queries("uncovered"), T.ray_expected(oracle, "uncovered")
+    on = Q["on_uncovered"]
+    table = T.AE._tables(oracle, tri, nodes, Q["rays"][on])[1]         # hitTriangle's t of every triangle, EZ_INF: no hit
+    nearest = table.argmin(1)
+    differs = np.isin(nearest, expect["uncovered"]) & (table.min(1) < T.MISS_T) & (table.min(1) != X["closest.t"][on])
+    print("uncovered: %d of %d aimed rays have an uncovered triangle nearest and another answer from the tree" % (differs.sum(), differs.size))
+    assert differs.size == 128 and differs.sum() >= 32
+    assert not np.isin(X["all64.tri"], expect["uncovered"]).any()     # no list names a triangle that no leaf holds
+
+
+def test_the_chain_rays_leave_entries_pending_on_the_callers_nodes(oracle):
+    tri, nodes, expect = T.shape("chain")
+    Q = T.ray_queries("chain")
+    depth = {}
+    for key in ("deep", "shallow"):
+        rays = Q["rays"][Q[key]]
+        assert (rays[:, 4:] == 0).all() and (np.abs(rays[:, 3]) == 1).all()   # parallel to x
+        depth[key] = T.pending_depth(nodes, T.AE._tables(oracle, tri, nodes, rays)[0])
+        assert np.array_equal(depth[key], T.pending_depth(nodes, T.slab(rays, nodes)))   # (the numpy slab test that chose them agrees)
+    both = np.concatenate([depth["deep"], depth["shallow"]])
+    print("chain: deepest pending count %d from the deep end, %d from the shallow end; %d rays at 40 or more"
+          % (depth["deep"].max(), depth["shallow"].max(), (both >= 40).sum()))
+    assert (both >= 40).sum() >= 16 and both.max() <= expect["depth"] - 1

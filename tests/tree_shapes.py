@@ -528,3 +528,172 @@ def differing(got, want):
         if not same:
             bad.append("%s (%d of %d)" % (key, int((a != b).sum()) if a.shape == b.shape else -1, b.size))
     return bad
+
+
+# ---- the rays (tests/test_tree_shapes.py on the CPU, tests/test_gpu_tree_shapes_rays.py on the device)
+#
+# The ray contract is hitBVH on the CALLER's arrays: unlike the point and overlap queries above, the answer depends on the leaves --
+# a triangle that no leaf holds is never seen, and of two triangles at one distance the one whose leaf the reference reaches first
+# wins.  ray_queries(name) -> dict: rays [n, 6] (n = a whole number of waves plus one ray) and the index range of every part:
+#   broad   257 rays of allhits_scenes.broad_rays (random, axis-parallel and one-zero-component rays with origins on vertex planes,
+#           unnormalised directions, rays that are not tame); the scenes of 8 triangles or fewer, which such rays hit 4 to 9 % of the
+#           time, get 257 near rays in their place, every eighth of them reversed (it leaves its triangle behind: the misses)
+#   near    256 rays aimed at a random interior point (barycentrics >= 0.1: hitTriangle is strict, a point on an edge is a miss) of a
+#           random triangle, in a random direction, from 0.05 to 0.6 in front of it
+#   ties    128 rays aimed the same way at triangles that have a byte-identical copy (shapes of more than 8 triangles)
+#   on_uncovered   128 rays aimed the same way at the triangles that no leaf holds (`uncovered`)
+#   deep, shallow   64 + 32 rays parallel to x that enter the chain from beyond its deep and its shallow end, on the lines of a 1/8
+#           grid (offset by 0.03: on no vertex plane) over the strip's y / z extent whose walk by the reference's rule leaves the most
+#           entries pending on the caller's nodes (pending_depth)
+#   pad     near rays up to the next whole number of waves plus one (`chain`: 641 + 96 = 737 rays, 32 more)
+# ray_expected(oracle, name) -> dict name -> array: every answer of the GPU test from the CPU oracle's query_hits and the restated
+# all-hits lists on the caller's arrays; the entries that begin with "_" are the t_max arrays derived from the answers.
+import allhits_expected as AE  # noqa: E402
+import allhits_scenes as AS  # noqa: E402
+import test_surface_restatement as RS  # noqa: E402
+
+N_BROAD, N_NEAR_RAYS, N_TIE_RAYS, N_ON_UNCOVERED, N_CHAIN_DEEP, N_CHAIN_SHALLOW = 257, 256, 128, 128, 64, 32
+ALL_HITS_K = (64, 1, 2, 5)
+SURFACE_FORMS = (3, 4, 50)
+T_MAX = ("own", "below", "above", "second", "inf", "nan", "zero", "negative")
+MISS_T = AE.EZ_INF
+
+
+def copied(tri):
+    """int [k]: the lowest index of every triangle that has a byte-identical copy in the array"""
+    V, first, twice = vertices(tri), {}, set()
+    for t in range(V.shape[0]):
+        if first.setdefault(V[t].tobytes(), t) != t:
+            twice.add(first[V[t].tobytes()])
+    return np.array(sorted(twice), int)
+
+
+def aimed_rays(V, ids, rng):
+    """float32 [n, 6]: ray i crosses triangle ids[i] at an interior point, in a random direction, 0.05 to 0.6 from its origin"""
+    n = len(ids)
+    w = 0.1 + 0.7 * rng.dirichlet((1, 1, 1), n)
+    p = (V[ids].astype(np.float64) * w[:, :, None]).sum(1)
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.concatenate([p - d * rng.uniform(0.05, 0.6, (n, 1)), d], 1).astype(F)
+
+
+def slab(rays, nodes):
+    """float32 [n_rays, n_nodes]: hitAABB restated in numpy, for choosing rays only (the tests use the oracle's own table)"""
+    with np.errstate(all="ignore"):
+        S, inv = rays[:, None, :3], (F(1) / rays[:, 3:])[:, None, :]
+        f, n = (nodes[None, :, 9:12] - S) * inv, (nodes[None, :, 6:9] - S) * inv
+        t1, t0 = np.maximum(f, n).min(2), np.minimum(f, n).max(2)
+        return np.where(t1 >= t0, np.where(t0 > 0, t0, t1), F(-1)).astype(F)
+
+
+def pending_depth(nodes, A):
+    """int [n_rays]: the most entries the reference's walk (near child first, ties right-first; allhits_expected.visit_lists) has
+    pending on the nodes, per row of the hitAABB table A [n_rays, n_nodes]"""
+    left, right, cnt = (nodes[:, k].astype(int).tolist() for k in (0, 1, 3))
+    out = []
+    for a in A.tolist():
+        stack, deepest = [1], 0
+        while stack:
+            top = stack.pop()
+            deepest = max(deepest, len(stack))
+            if cnt[top] > 0:
+                continue
+            l, r = left[top], right[top]
+            if a[l] > 0.0 and a[r] > 0.0:
+                stack += [r, l] if a[l] < a[r] else [l, r]
+            elif a[l] > 0.0 or a[r] > 0.0:
+                stack.append(l if a[l] > 0.0 else r)
+        out.append(deepest)
+    return np.array(out)
+
+
+def _chain_lines(V, nodes):
+    """(deep [64, 6], shallow [32, 6]): the lines along x with the most entries pending, entered from either end"""
+    flat = V.reshape(-1, 3)
+    lo, hi = flat.min(0), flat.max(0)
+    y, z = np.meshgrid(np.arange(lo[1] + 0.03, hi[1], 0.125), np.arange(lo[2] + 0.03, hi[2], 0.125), indexing="ij")
+    out = []
+    for x, dx, n in ((hi[0] + 1.0, -1.0, N_CHAIN_DEEP), (lo[0] - 1.0, 1.0, N_CHAIN_SHALLOW)):
+        rays = np.zeros((y.size, 6), F)
+        rays[:, 0], rays[:, 1], rays[:, 2], rays[:, 3] = x, y.ravel(), z.ravel(), dx
+        out.append(rays[np.argsort(-pending_depth(nodes, slab(rays, nodes)), kind="stable")[:n]])
+    return out
+
+
+def ray_queries(name):
+    if ("R", name) not in _cache:
+        tri, nodes, expect = shape(name)
+        V, rng = vertices(tri), np.random.default_rng(SEEDS[name] + 500)
+        parts, Q, n = [], {}, 0
+
+        def add(key, rays):
+            nonlocal n
+            Q[key] = slice(n, n + rays.shape[0])
+            parts.append(rays)
+            n += rays.shape[0]
+
+        near = lambda k: aimed_rays(V, rng.integers(0, V.shape[0], k), rng)  # noqa: E731
+        if V.shape[0] > 8:
+            add("broad", AS.broad_rays(tri, rng, N_BROAD))
+        else:
+            away = near(N_BROAD)
+            away[::8, 3:] *= F(-1)                                                  # every eighth leaves its triangle behind: misses
+            add("broad", away)
+        add("near", near(N_NEAR_RAYS))
+        twice = copied(tri)
+        add("ties", aimed_rays(V, rng.choice(twice, N_TIE_RAYS), rng) if V.shape[0] > 8 else near(0))
+        unc = expect.get("uncovered", np.zeros(0, int))
+        plain = np.setdiff1d(unc, expect.get("copies", []))                       # first those that no covered triangle equals
+        add("on_uncovered", aimed_rays(V, np.resize(np.concatenate([plain, plain, unc]), N_ON_UNCOVERED), rng) if unc.size else near(0))
+        deep, shallow = _chain_lines(V, nodes) if expect.get("chain") else (near(0), near(0))
+        add("deep", deep)
+        add("shallow", shallow)
+        add("pad", near(-(n - 1) % 64))
+        Q["rays"] = np.ascontiguousarray(np.concatenate(parts), F)
+        Q["rays"].setflags(write=False)
+        assert Q["rays"].shape == (n, 6) and n % 64 == 1
+        _cache[("R", name)] = Q
+    return _cache[("R", name)]
+
+
+def filtered(tri, t, t_max):
+    """the contract's closest (tri, t) and occluded from the oracle's hits: tri >= 0 and t < t_max"""
+    with np.errstate(invalid="ignore"):
+        hit = (tri >= 0) if t_max is None else (tri >= 0) & (t < t_max)
+    return np.where(hit, tri, -1).astype(np.int32), np.where(hit, t, MISS_T).astype(F), hit
+
+
+def ray_lists(oracle, name):
+    """the visit lists of the shape's rays (allhits_expected.visit_lists), computed once"""
+    if ("V", name) not in _cache:
+        tri, nodes, _ = shape(name)
+        _cache[("V", name)] = AE.visit_lists(oracle, tri, nodes, ray_queries(name)["rays"])
+    return _cache[("V", name)]
+
+
+def ray_expected(oracle, name):
+    if ("X", name) in _cache:
+        return _cache[("X", name)]
+    tri, nodes, _ = shape(name)
+    rays = ray_queries(name)["rays"]
+    n = rays.shape[0]
+    to, do = oracle.scene_create(tri, nodes).query_hits(rays)
+    visits = ray_lists(oracle, name)
+    lists = AE.expected_all_hits(oracle, tri, nodes, rays, None, visits=visits)
+    up, down = F(np.inf), F(-np.inf)
+    X = {"_t_max.own": do.copy(), "_t_max.below": np.nextafter(do, down), "_t_max.above": np.nextafter(do, up),
+         "_t_max.second": np.array([t[1] if t.size > 1 else (t[0] if t.size else F(1)) for ids, t in lists], F),
+         "_t_max.inf": np.full(n, np.inf, F), "_t_max.nan": np.full(n, np.nan, F), "_t_max.zero": np.zeros(n, F),
+         "_t_max.negative": -np.random.default_rng(SEEDS[name] + 600).uniform(0.0, 3.0, n).astype(F)}
+    for key in (None,) + T_MAX:
+        t_max = None if key is None else X["_t_max." + key]
+        tag = "" if key is None else "[%s]" % key
+        X["closest%s.tri" % tag], X["closest%s.t" % tag], X["occluded%s" % tag] = filtered(to, do, t_max)
+        bounded = lists if key is None else AE.expected_all_hits(oracle, tri, nodes, rays, t_max, visits=visits)
+        for K in ALL_HITS_K:
+            X["all%d%s.tri" % (K, tag)], X["all%d%s.t" % (K, tag)], X["all%d%s.count" % (K, tag)] = AE.rows(bounded, K)
+    for form in SURFACE_FORMS:
+        X["surface%d.point" % form], X["surface%d.normal" % form], X["surface%d.inside" % form] = RS.restate(tri, rays, to, do, form >= 50)
+    _cache[("X", name)] = X
+    return X
