@@ -241,6 +241,17 @@ TRI_DISTANCE_ABI = {
 }
 
 
+# stream-ordered sphere-cast queries on device memory, libezrt_hip.so only (include/ezrt_sphere_cast.h); pointers are device addresses
+SPHERE_CAST_ABI = {
+    # s, rays6, radius, t_max, n, tri_id, t, point, touching, stream
+    "ezrt_query_sphere_cast_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, rays6, radius, tri_id, n, t, point, touching, stream
+    "ezrt_sphere_cast_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -308,7 +319,8 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, REFIT_ABI):
+                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI,
+                      REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

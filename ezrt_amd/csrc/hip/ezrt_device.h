@@ -821,6 +821,150 @@ EZD void hit_bvh(const DevScene& sc, f3 S, f3 d, int* __restrict__ stack, int32_
   }
 }
 
+// ---- sphere-cast queries (include/ezrt_sphere_cast.h, where the definition is the contract): a sphere of radius r whose centre
+// moves along o + d t, against one scene triangle.  sphere_cast_live is the query's liveness, sphere_cast_slab the gate -- the slab
+// test of the ray against a box inflated by r, which is also the walk's bound of a node box (sphere_cast_box) --, sphere_cast_pair
+// the seven sub-candidates in the header's order (face, edges ab bc ca, vertices a b c), the first smallest finite t, clamped up to
+// the gate's tnear.  The edge and vertex loops are not unrolled and pick their vertices from the registers by index, as
+// tri_distance_pair does: one sub-candidate's state is held at a time.
+struct SphereRay {
+  f3 o, d, inv; // inv = 1 / d per axis (used where d != 0 alone)
+  float r, rr, dd; // rr = r * r, dd = dot(d, d)
+};
+EZD bool sphere_cast_live(f3 o, f3 d, float r, SphereRay& q) {
+  const float inf = __builtin_inff();
+  q.o = o, q.d = d, q.r = r;
+  q.rr = r * r;
+  q.dd = dot(d, d);
+  q.inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  return ez_abs(o.x) < inf && ez_abs(o.y) < inf && ez_abs(o.z) < inf && ez_abs(d.x) < inf && ez_abs(d.y) < inf && ez_abs(d.z) < inf &&
+         r >= 0.0f && r < inf && q.dd > 0.0f && q.dd < inf && (d.x == 0.0f || ez_abs(q.inv.x) < inf) &&
+         (d.y == 0.0f || ez_abs(q.inv.y) < inf) && (d.z == 0.0f || ez_abs(q.inv.z) < inf);
+}
+// one axis of the slab test: false when a flat axis (d == 0 or -0) lies outside [lo - r, hi + r]; a NaN bound constrains nothing
+EZD bool sphere_cast_axis(float o, float d, float inv, float r, float lo, float hi, float& tn, float& tf) {
+  const float L = lo - r, H = hi + r;
+  if (d == 0.0f) return !(o < L || o > H);
+  const float x = (L - o) * inv, y = (H - o) * inv;
+  tn = ez_max(tn, d < 0.0f ? y : x);
+  tf = ez_min(tf, d < 0.0f ? x : y);
+  return true;
+}
+// the gate: tnear = max(0, nears), tfar = min(+inf, fars); true when no flat axis fails and tnear <= tfar.  For a box that holds
+// another, tnear is no larger and tfar no smaller ON THE BITS, and it passes whenever the inner one does (ezrt_point_queries.h:
+// sphere_cast_kernel).
+EZD bool sphere_cast_slab(const SphereRay& q, f3 lo, f3 hi, float& tnear) {
+  float tn = 0.0f, tf = __builtin_inff();
+  const bool x = sphere_cast_axis(q.o.x, q.d.x, q.inv.x, q.r, lo.x, hi.x, tn, tf);
+  const bool y = sphere_cast_axis(q.o.y, q.d.y, q.inv.y, q.r, lo.y, hi.y, tn, tf);
+  const bool z = sphere_cast_axis(q.o.z, q.d.z, q.inv.z, q.r, lo.z, hi.z, tn, tf);
+  tnear = tn;
+  return x && y && z && tn <= tf;
+}
+// ... as the lower bound of the t of every pair below a box: tnear, +inf where the gate fails
+EZD float sphere_cast_box(const SphereRay& q, f3 lo, f3 hi) {
+  float tn;
+  return sphere_cast_slab(q, lo, hi, tn) ? tn : __builtin_inff();
+}
+EZD f3 sphere_into_box(f3 x, f3 lo, f3 hi) {
+  return mk(x.x < lo.x ? lo.x : (x.x > hi.x ? hi.x : x.x), x.y < lo.y ? lo.y : (x.y > hi.y ? hi.y : x.y),
+            x.z < lo.z ? lo.z : (x.z > hi.z ? hi.z : x.z));
+}
+EZD f3 sphere_corner(int i, f3 a, f3 b, f3 c) {
+  return mk(i == 0 ? a.x : (i == 1 ? b.x : c.x), i == 0 ? a.y : (i == 1 ? b.y : c.y), i == 0 ? a.z : (i == 1 ? b.z : c.z));
+}
+// the first time A t^2 + 2 B t + C reaches 0 for a centre that approaches (B < 0) from outside (C > 0), in the form without
+// cancellation; 0 where the feature already holds the centre (C <= 0); NaN -- skipped by the caller -- otherwise.  disc is the
+// caller's B^2 - A C in Lagrange's form, A r^2 - |m x d|^2, which does not cancel for a thin sphere far away
+EZD float sphere_root(float B, float C, float disc) {
+  if (C <= 0.0f) return 0.0f;
+  return (B < 0.0f && disc >= 0.0f) ? C / (__builtin_sqrtf(disc) - B) : __builtin_nanf("");
+}
+// The pair rule.  False: the triangle is not live, the gate fails, tnear > limit (such a pair's t exceeds limit: the caller's running
+// best, +inf for none) or no sub-candidate has a finite t.  Else t = max(smallest valid t, tnear), `point` the contact point on the
+// triangle and `sub` the sub-candidate that supplied it (0 face, 1 2 3 edges, 4 5 6 vertices).
+EZD bool sphere_cast_pair(const float4* __restrict__ tg, const SphereRay& q, float limit, float& t, f3& point, int& sub, float& tnear) {
+  const float inf = __builtin_inff();
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  if (!(ez_abs(a.x) < inf && ez_abs(a.y) < inf && ez_abs(a.z) < inf && ez_abs(b.x) < inf && ez_abs(b.y) < inf && ez_abs(b.z) < inf &&
+        ez_abs(c.x) < inf && ez_abs(c.y) < inf && ez_abs(c.z) < inf))
+    return false;
+  const f3 lo = mk(ez_min(ez_min(a.x, b.x), c.x), ez_min(ez_min(a.y, b.y), c.y), ez_min(ez_min(a.z, b.z), c.z));
+  const f3 hi = mk(ez_max(ez_max(a.x, b.x), c.x), ez_max(ez_max(a.y, b.y), c.y), ez_max(ez_max(a.z, b.z), c.z));
+  if (!sphere_cast_slab(q, lo, hi, tnear) || tnear > limit) return false;
+  float best = inf;
+  auto take = [&](float tt, f3 x, int which) {
+    if (tt < best) best = tt, point = x, sub = which; // (false for a NaN or infinite tt; the first wins on equality)
+  };
+  { // the face: the unnormalised normal flipped to o's side; valid when the centre approaches the plane and the foot is in the triangle
+    const f3 ab = b - a, ac = c - a, m = q.o - a;
+    const f3 n0 = cross(ab, ac);
+    const float h0 = dot(n0, m);
+    const bool flip = h0 < 0.0f;
+    const f3 n = flip ? -n0 : n0;
+    const float h = flip ? -h0 : h0;
+    const float nd = dot(n, q.d);
+    if (nd < 0.0f) {
+      const float len = __builtin_sqrtf(dot(n, n));
+      const float g = h - q.r * len;
+      const float tt = g <= 0.0f ? 0.0f : g / (-nd);
+      const f3 x = (q.o + q.d * tt) - n * (q.r / len);
+      const float e0 = dot(cross(ab, x - a), n0), e1 = dot(cross(c - b, x - b), n0), e2 = dot(cross(a - c, x - c), n0);
+      if (e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f) take(tt, sphere_into_box(x, lo, hi), 0);
+    }
+  }
+#pragma unroll 1
+  for (int j = 0; j < 3; j++) { // the edges (a, b) (b, c) (c, a): the cylinder of radius r about the edge, in the plane across it
+    const f3 u = sphere_corner(j, a, b, c), v = sphere_corner(j, b, c, a);
+    const f3 e = v - u, m = q.o - u;
+    const float ee = dot(e, e);
+    const float sd = dot(e, q.d) / ee, sm = dot(e, m) / ee;
+    const f3 dp = q.d - e * sd, mp = m - e * sm;
+    const f3 x = cross(mp, dp);
+    const float tt = sphere_root(dot(mp, dp), dot(mp, mp) - q.rr, dot(dp, dp) * q.rr - dot(x, x));
+    const float s = sm + sd * tt;
+    const f3 elo = mk(ez_min(u.x, v.x), ez_min(u.y, v.y), ez_min(u.z, v.z)), ehi = mk(ez_max(u.x, v.x), ez_max(u.y, v.y), ez_max(u.z, v.z));
+    if (s >= 0.0f && s <= 1.0f) take(tt, sphere_into_box(u + e * s, elo, ehi), 1 + j);
+  }
+#pragma unroll 1
+  for (int j = 0; j < 3; j++) { // the vertices a b c: the sphere of radius r about the vertex
+    const f3 p = sphere_corner(j, a, b, c);
+    const f3 m = q.o - p;
+    const f3 x = cross(m, q.d);
+    take(sphere_root(dot(m, q.d), dot(m, m) - q.rr, q.dd * q.rr - dot(x, x)), p, 4 + j);
+  }
+  if (!(best < inf)) return false;
+  t = ez_max(best, tnear);
+  return t < inf;
+}
+// The running answer of one query.  `t` starts as t_max (tri = -1) and is the radius of the walk from the first step on; the smallest
+// t wins and, among equal t, the smallest index -- whatever the order in which the triangles are met.
+struct SphereBest {
+  float t;
+  int32_t tri;
+  f3 point;
+  bool touching;
+};
+EZD void sphere_cast_candidate(SphereBest& r, const float4* __restrict__ tri_geom, int32_t k, const SphereRay& q) {
+  float t, tnear;
+  f3 x;
+  int sub;
+  if (!sphere_cast_pair(tri_geom + (size_t)k * 3, q, r.t, t, x, sub, tnear)) return;
+  if (t < r.t || (t == r.t && (r.tri < 0 || k < r.tri))) r.t = t, r.tri = k, r.point = x;
+}
+// the pair for a caller who holds it: touching where closest_point_triangle's dist2 <= r * r, else the swept pair; tri stays -1 for a miss
+EZD void sphere_cast_at(SphereBest& r, const float4* __restrict__ tri_geom, int32_t k, const SphereRay& q) {
+  f3 x;
+  float v, w;
+  const float d2 = closest_point_triangle(tri_geom + (size_t)k * 3, q.o, x, v, w);
+  if (d2 < __builtin_inff() && d2 <= q.rr) { // closest_point_candidate's test with B = r * r (false for a NaN d2)
+    r.t = 0.0f, r.tri = k, r.point = x, r.touching = true;
+    return;
+  }
+  sphere_cast_candidate(r, tri_geom, k, q);
+}
+
 // ---- triangle-distance queries (include/ezrt_tri_distance.h, where the definition is the contract): the pair rule of one scene
 // triangle against a LIVE query triangle -- q from tri_query, p1 p2 p3 its vertices as the caller gave them.  The 15 sub-candidates in
 // the header's order (vertices of Q against the triangle, its vertices against Q, the nine edge pairs with Q's edge outer), the first

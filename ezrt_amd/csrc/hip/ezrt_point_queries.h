@@ -1,7 +1,8 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
-// self-overlap and triangle-distance queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h,
-// include/ezrt_tri_distance.h).  One query point, box or triangle per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// self-overlap, triangle-distance and sphere-cast queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
+// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h).  One query point, box, triangle or ray per lane,
+// a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -20,6 +21,9 @@
 //   self_overlap_at_kernel           self_crosses for pairs of ids the caller holds
 //   tri_distance_kernel<WALK>        point_walk with tri_distance_box as the bound and tri_distance_pair as the rule
 //   tri_distance_at_kernel           tri_distance_pair for pairs the caller holds
+//   sphere_cast_kernel<WALK>         closest_point_search with B = r * r, then point_walk with sphere_cast_box as the bound and
+//                                    sphere_cast_pair as the rule
+//   sphere_cast_at_kernel            sphere_cast_at for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -726,6 +730,87 @@ __global__ __launch_bounds__(256) void tri_distance_at_kernel(const float4* tri_
   TriQuery q;
   if ((uint32_t)tri < (uint32_t)n_tri && tri_query(p1, p2, p3, q)) tri_distance_candidate(r, tri_geom, tri, q, p1, p2, p3);
   tri_distance_store(dist, point_query, point_scene, crosses, i, r);
+}
+
+// ---- sphere-cast queries (include/ezrt_sphere_cast.h).
+//
+// sphere_cast_kernel<WALK>: one query per lane, two walks on the lane's stack column of 2 * (stack_need_cp + 1) rows (each leaves
+// nothing pending).  First closest_point_search with d_max = the radius (B = r * r): a winner is the touching answer.  Otherwise
+// point_walk once more, with t in the place of dist2: the radius is t_max (+inf when NULL) until a candidate is found and the best t
+// from then on (RECHECK), and the lower bound of a slot's box [lo, hi] is sphere_cast_box -- tnear of the slab test of the ray against
+// the box inflated by r where tnear <= tfar, else +inf (never descended).
+// Why no margin is needed: for a box [L, H] that holds [l, h], L <= l and H >= h per axis.  Every step of near and far is monotone
+// under rounding: fl(L - r) <= fl(l - r) and fl(H + r) >= fl(h + r); subtracting o keeps the order; multiplying by inv, a constant of
+// fixed sign, keeps it (inv > 0) or turns it (inv < 0, where the two are swapped); max and min keep it.  So tnear(outer) <= tnear(inner)
+// and tfar(outer) >= tfar(inner) ON THE BITS; a flat axis that passes l - r <= o <= h + r passes the wider test; hence an outer box
+// passes whenever an inner one does.  NaN and infinity: o, r and inv are finite and inv != 0, so 0 * inf cannot arise; a difference
+// that overflows (l - r = -inf, (l - r) - o, the product) is an infinity of the right sign and stays ordered; inf - inf cannot arise
+// from a finite o; a NaN bound of a box constrains nothing, which only widens.  The pair's t is max(its smallest sub-candidate,
+// tnear of the triangle's own bounding box), so tnear(any box above T) <= tnear(T) <= t(pair): a subtree skipped at lb > radius holds
+// neither a winner nor a tie, and on equality it is descended.  The pair gate: sphere_cast_pair runs the same slab test on the
+// triangle's own bounding box before its seven sub-candidates and leaves a pair whose tnear exceeds the best t of the moment.
+// Triangles that no leaf holds are swept after each walk.  WALK = false, the sweep route: every triangle, no tree, twice.
+struct SphereCastArgs {
+  ClosestPointArgs cp;      // sc, d_max = the radii, n, tri, point (points, dist and bary unused)
+  const float* rays;        // n x 6
+  const float* t_max;       // n, or null
+  float* t;                 // n, or null
+  uint8_t* touching;        // n, or null
+};
+// row i of the outputs; tri < 0 writes the miss (+inf, zeros, 0: the caller keeps point zero and touching false then)
+EZD void sphere_cast_store(float* t, float* point, uint8_t* touching, uint32_t i, const SphereBest& r) {
+  if (t) t[i] = r.tri >= 0 ? r.t : __builtin_inff();
+  if (point) st3(point + (size_t)i * 3, r.point);
+  if (touching) touching[i] = r.touching ? 1u : 0u;
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void sphere_cast_kernel(SphereCastArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const ClosestPointArgs& a = sa.cp;
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const float* ray = sa.rays + (size_t)i * 6;
+  int* stack = lds_stack + threadIdx.x;
+  SphereBest r;
+  r.tri = -1;
+  r.point = mk(0.0f, 0.0f, 0.0f);
+  r.touching = false;
+  r.t = __builtin_inff();
+  SphereRay q;
+  if (sphere_cast_live(ld3(ray), ld3(ray + 3), a.d_max[i], q)) {
+    const ClosestBest c = closest_point_search<WALK>(a, i, q.o, stack);
+    if (c.tri >= 0) {
+      r.tri = c.tri, r.t = 0.0f, r.point = c.q, r.touching = true;
+    } else {
+      const float tm = sa.t_max ? sa.t_max[i] : __builtin_inff();
+      if (tm >= 0.0f) { // (a negative or NaN t_max gives no candidates)
+        r.t = tm;
+        bound_visit<WALK, true>(
+            a.sc, [&](f3 lo, f3 hi) { return sphere_cast_box(q, lo, hi); }, stack, [&] { return r.t; },
+            [&](int32_t k) { sphere_cast_candidate(r, a.sc.tri_geom, k, q); });
+      }
+    }
+  }
+  a.tri[i] = r.tri;
+  sphere_cast_store(sa.t, a.point, sa.touching, i, r);
+}
+
+// ezrt_sphere_cast_at_device: sphere_cast_at for pairs the caller holds -- query i against triangle tri_id[i].  An id outside the
+// scene, a query or a triangle that is not live or a pair that is no candidate writes (+inf, zeros, 0).
+__global__ __launch_bounds__(256) void sphere_cast_at_kernel(const float4* tri_geom, int32_t n_tri, const float* rays, const float* radius,
+                                                             const int32_t* tri_id, uint32_t n, float* t, float* point, uint8_t* touching) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  const float* ray = rays + (size_t)i * 6;
+  SphereBest r;
+  r.tri = -1;
+  r.point = mk(0.0f, 0.0f, 0.0f);
+  r.touching = false;
+  r.t = __builtin_inff();
+  SphereRay q;
+  if ((uint32_t)tri < (uint32_t)n_tri && sphere_cast_live(ld3(ray), ld3(ray + 3), radius[i], q)) sphere_cast_at(r, tri_geom, tri, q);
+  sphere_cast_store(t, point, touching, i, r);
 }
 
 } // namespace ezd

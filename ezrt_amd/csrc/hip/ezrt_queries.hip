@@ -1,8 +1,8 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap and triangle-distance queries
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance and sphere-cast queries
 // (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h,
-// ezrt_tri_distance.h).  A translation unit of its own: none of its kernels is compiled together
+// ezrt_tri_distance.h, ezrt_sphere_cast.h).  A translation unit of its own: none of its kernels is compiled together
 // with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run
 // the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in
 // ezrt_launch.hip.  DESIGN.md 5.
@@ -17,6 +17,7 @@
 #include "ezrt_tri_overlap.h"
 #include "ezrt_self_overlap.h"
 #include "ezrt_tri_distance.h"
+#include "ezrt_sphere_cast.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -522,6 +523,50 @@ int ezrt_tri_distance_at_device(EzrtScene* s, const float* tris9, const int32_t*
                           {point_query, N * 3 * sizeof(float)}, {point_scene, N * 3 * sizeof(float)}, {crosses, N}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(tri_distance_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tris9, tri_id, (uint32_t)n, dist, point_query,
                          point_scene, crosses);
+    });
+  });
+}
+
+// ---- sphere-cast queries on device memory (include/ezrt_sphere_cast.h): one kernel each on `st`, no scratch; checked, launched and
+// ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_sphere_cast_device(EzrtScene* s, const float* rays6, const float* radius, const float* t_max, int n, int32_t* tri_id, float* t,
+                                  float* point, uint8_t* touching, void* stream) {
+  return ezi::guarded("ezrt_query_sphere_cast_device", [&]() -> int {
+    if (!s || !rays6 || !radius || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{rays6, N * 6 * sizeof(float)}, {radius, N * sizeof(float)}, {t_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)},
+                          {t, N * sizeof(float)}, {point, N * 3 * sizeof(float)}, {touching, N}}, N, st, [&](dim3, dim3) {
+      SphereCastArgs a;
+      const PointRoute r = point_scene(s, a.cp.sc);
+      a.cp.points = nullptr;
+      a.cp.d_max = radius;
+      a.cp.n = (uint32_t)n;
+      a.cp.tri = tri_id;
+      a.cp.point = point;
+      a.cp.dist = nullptr;
+      a.cp.bary = nullptr;
+      a.rays = rays6;
+      a.t_max = t_max;
+      a.t = t;
+      a.touching = touching;
+      launch_routed(sphere_cast_kernel<true>, sphere_cast_kernel<false>, r, r.lds, N, st, a);
+    });
+  });
+}
+int ezrt_sphere_cast_at_device(EzrtScene* s, const float* rays6, const float* radius, const int32_t* tri_id, int n, float* t, float* point,
+                               uint8_t* touching, void* stream) {
+  return ezi::guarded("ezrt_sphere_cast_at_device", [&]() -> int {
+    if (!s || !rays6 || !radius || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!t && !point && !touching) return fail(EZRT_ERR_INVALID, "one of t, point and touching is required");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{rays6, N * 6 * sizeof(float)}, {radius, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {t, N * sizeof(float)},
+                          {point, N * 3 * sizeof(float)}, {touching, N}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(sphere_cast_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, rays6, radius, tri_id, (uint32_t)n, t, point,
+                         touching);
     });
   });
 }

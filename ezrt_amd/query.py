@@ -1,6 +1,6 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
-include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h).
+include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -22,6 +22,8 @@ include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distan
     crosses = query.self_overlap_at(scene, a, b)                 # ... the same test for pairs of triangle ids already held  (bool)
     tri, dist, point_query, point_scene, crosses = query.tri_distance(scene, tris, d_max)   # how close each triangle comes to the mesh
     tri, dist, point_query, point_scene, crosses = query.tri_distance_at(scene, tris, tri)  # ... for pairs already held (include/ezrt_tri_distance.h)
+    tri, t, point, touching = query.sphere_cast(scene, rays, radius, t_max)   # first contact of a sphere moving along each ray
+    tri, t, point, touching = query.sphere_cast_at(scene, rays, radius, tri)  # ... for pairs already held (include/ezrt_sphere_cast.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -33,6 +35,9 @@ return without waiting for it.  `axis` (0..5: +x, -x, +y, -y, +z, -z) is the dir
 on a closed mesh every axis gives the same answer, on an open one (the Bunny has holes) they may differ: vote over several.
 There is no t_min: a triangle is accepted at t >= 0.0005 only, so a ray leaving a surface needs its
 origin offset by the caller.  A miss is (-1, 114514.0): ezrt_query_hits' miss (the reference's INF).
+`sphere_cast` is not the reference's rule: `radius` is a float32 GPU tensor of shape rays.shape[:-1] in world units, the direction
+need not have unit length and t is in units of it (the centre at time t is o + d*t), a contact is accepted from t = 0 on, and a
+miss is the point queries' (-1, +inf, zeros, False).
 """
 import collections
 import ctypes as C
@@ -50,6 +55,7 @@ BoxOverlap = collections.namedtuple("BoxOverlap", "tri n_overlap")
 TriOverlap = collections.namedtuple("TriOverlap", "tri n_overlap")
 SelfOverlap = collections.namedtuple("SelfOverlap", "tri n_overlap")
 TriDistance = collections.namedtuple("TriDistance", "tri dist point_query point_scene crosses")
+SphereCast = collections.namedtuple("SphereCast", "tri t point touching")
 
 
 def _scene_lib(scene, abi):
@@ -633,3 +639,63 @@ def tri_distance_at(scene, tris, tri, stream=None):
                                                  P(point_query.data_ptr()), P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
     _keep((tris, per, tri, dist, point_query, point_scene, crosses), ts, tris)
     return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+
+
+def _check_spheres(rays, radius, t_max):
+    n = _check_rays(rays, t_max)
+    _tensor("radius", radius, torch.float32, rays.shape[:-1], device=rays.device)
+    return n
+
+
+def sphere_cast(scene, rays, radius, t_max=None, stream=None):
+    """SphereCast(tri int32 [...], t float32 [...], point float32 [..., 3], touching bool [...]): for every ray of `rays` (a
+    contiguous float32 GPU tensor [..., 6]: origin o, direction d -- d need not have unit length) the first triangle that a sphere of
+    radius `radius` (float32, of shape rays.shape[:-1], world units) touches while its centre moves along o + d*t, the time t of that
+    contact IN UNITS OF d, and the contact point on the triangle: the contact normal is (o + d*t - point) / radius.  Where the sphere
+    already touches the mesh at t = 0, `touching` is set, t is 0 and (tri, point) are those of `closest_point(scene, o, radius)`.
+    `t_max` (optional, float32, of shape rays.shape[:-1]) admits only contacts at t <= t_max.  A miss is (-1, +inf, zeros, False).
+    Equal t: the lowest triangle index.  A query with a non-finite number, a negative radius or a direction of length 0 misses.  The
+    definition, on the bits: include/ezrt_sphere_cast.h; `sphere_cast_at` evaluates pairs."""
+    n = _check_spheres(rays, radius, t_max)
+    lead = tuple(rays.shape[:-1])
+    lib = _scene_lib(scene, _abi.SPHERE_CAST_ABI)
+    tri = torch.empty(lead, dtype=torch.int32, device=rays.device)
+    t = torch.empty(lead, dtype=torch.float32, device=rays.device)
+    point = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
+    touching = torch.empty(lead, dtype=torch.uint8, device=rays.device)
+    if n == 0:
+        return SphereCast(tri, t, point, touching.view(torch.bool))
+    h, ts = _stream(rays, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_sphere_cast_device(scene._h, P(rays.data_ptr()), P(radius.data_ptr()),
+                                                   P(t_max.data_ptr()) if t_max is not None else None, n, P(tri.data_ptr()),
+                                                   P(t.data_ptr()), P(point.data_ptr()), P(touching.data_ptr()), P(h)))
+    _keep((rays, radius, t_max, tri, t, point, touching), ts, rays)
+    return SphereCast(tri, t, point, touching.view(torch.bool))
+
+
+def sphere_cast_at(scene, rays, radius, tri, stream=None):
+    """SphereCast(tri, t float32 tri.shape, point float32 tri.shape + (3,), touching bool tri.shape): for triangle tri[...] of the
+    scene and its ray and radius, what `sphere_cast` gives for its winner (no t_max).  `tri` (int32) has the shape rays.shape[:-1],
+    or one trailing dimension more -- rows of `nearest` -- and every entry of a row then belongs to the row's ray.  An id that is no
+    triangle of the scene (an unused slot, -1), a query that is not live or a pair without a contact gives (+inf, zeros, False).
+    `tri` is returned as given."""
+    _check_spheres(rays, radius, None)
+    lib = _scene_lib(scene, _abi.SPHERE_CAST_ABI)
+    lead = tuple(rays.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=rays.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    t = torch.empty(shape, dtype=torch.float32, device=rays.device)
+    point = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
+    touching = torch.empty(shape, dtype=torch.uint8, device=rays.device)
+    if n == 0:
+        return SphereCast(tri, t, point, touching.view(torch.bool))
+    h, ts = _stream(rays, stream)
+    per = _per_entry(rays, lead, shape, h, ts)
+    per_r = _per_entry(radius.unsqueeze(-1), lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_sphere_cast_at_device(scene._h, P(per.data_ptr()), P(per_r.data_ptr()), P(tri.data_ptr()), n, P(t.data_ptr()),
+                                                P(point.data_ptr()), P(touching.data_ptr()), P(h)))
+    _keep((rays, radius, per, per_r, tri, t, point, touching), ts, rays)
+    return SphereCast(tri, t, point, touching.view(torch.bool))
