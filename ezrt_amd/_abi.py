@@ -252,6 +252,22 @@ SPHERE_CAST_ABI = {
 }
 
 
+# stream-ordered segment queries on device memory, libezrt_hip.so only (include/ezrt_segment.h); pointers are device addresses.
+# segs6 holds the two END POINTS of every segment, not an origin and a direction.
+SEGMENT_ABI = {
+    # s, segs6, d_max, n, tri_id, dist, point_query, point_scene, crosses, stream
+    "ezrt_query_segment_distance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, segs6, tri_id, n, dist, point_query, point_scene, crosses, stream
+    "ezrt_segment_distance_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    # s, segs6, radius, n, max_k, tri_id, n_overlap, stream
+    "ezrt_query_capsule_overlap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+}
+CAPSULE_OVERLAP_MAX = 64  # EZRT_CAPSULE_OVERLAP_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -319,7 +335,7 @@ def load_hip():
                 "there is no CPU fallback for the trace" % path)
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
-                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI,
+                      INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

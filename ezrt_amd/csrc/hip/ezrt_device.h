@@ -1024,6 +1024,81 @@ EZD void tri_distance_candidate(TriDistanceBest& r, const float4* __restrict__ t
     r.best = d2, r.tri = k, r.x = x, r.y = y, r.crosses = crosses;
 }
 
+// ---- segment queries (include/ezrt_segment.h, where the definition is the contract): the pair rule of one scene triangle against a
+// LIVE query segment [a, b] (six finite numbers; a == b is a point) -- (lo, hi) are a and b in the order of their values, as
+// seg_meets takes them.  The five sub-candidates in the header's order (a, then b, against the triangle by closest_point_abc; the
+// segment as the FIRST argument of segment_segment_closest against the edges (p, q), (q, r), (r, p)), the first smallest finite d2
+// wins and supplies (x, y); then the crossing step: T1 on the two fp32 bounding boxes, and seg_meets as it stands.  False: the pair
+// is no candidate (the triangle is not live, or no d2 is finite).  The two loops are not unrolled and a vertex is picked from the
+// registers by its index, as in tri_distance_pair: one sub-candidate's state is held at a time.
+EZD bool segment_pair(const float4* __restrict__ tg, f3 a, f3 b, f3 lo, f3 hi, float& dist2, f3& x, f3& y, bool& crosses) {
+  const float4 gp = tg[0], gq = tg[1], gr = tg[2];
+  const f3 p = mk(gp.x, gp.y, gp.z), q = mk(gq.x, gq.y, gq.z), r = mk(gr.x, gr.y, gr.z);
+  TriSorted s;
+  if (!tri_live(p, q, r, s)) return false;
+  const float inf = __builtin_inff();
+  float best = inf;
+  bool found = false;
+  auto take = [&](float d2, f3 cx, f3 cy) {
+    if (d2 < inf && (!found || d2 < best)) best = d2, x = cx, y = cy, found = true; // (false for a NaN d2; the first wins on equality)
+  };
+#pragma unroll 1
+  for (int i = 0; i < 2; i++) {
+    const f3 e = tri_pick(i == 0, a, b);
+    f3 qq;
+    float v, w;
+    const float d2 = closest_point_abc(p, q, r, e, qq, v, w);
+    take(d2, e, qq);
+  }
+#pragma unroll 1
+  for (int j = 0; j < 3; j++) {
+    f3 cx, cy;
+    const float d2 = segment_segment_closest(a, b, tri_corner(j, p, q, r), tri_corner(j, q, r, p), cx, cy);
+    take(d2, cx, cy);
+  }
+  if (!found) return false;
+  // T1: the segment's bounding box against the triangle's, closed, on all three axes (every number is finite here)
+  const bool t1 = ez_min(a.x, b.x) <= ez_max(ez_max(p.x, q.x), r.x) && ez_min(ez_min(p.x, q.x), r.x) <= ez_max(a.x, b.x) &&
+                  ez_min(a.y, b.y) <= ez_max(ez_max(p.y, q.y), r.y) && ez_min(ez_min(p.y, q.y), r.y) <= ez_max(a.y, b.y) &&
+                  ez_min(a.z, b.z) <= ez_max(ez_max(p.z, q.z), r.z) && ez_min(ez_min(p.z, q.z), r.z) <= ez_max(a.z, b.z);
+  crosses = t1 && seg_meets(lo, hi, s);
+  dist2 = crosses ? 0.0f : best;
+  return true;
+}
+// a query segment as the kernels hold it; false when it is not live (one of its six numbers is not finite)
+struct SegQuery {
+  f3 a, b;     // the end points as the caller gave them
+  f3 lo, hi;   // ... in the order of their values (seg_meets)
+  f3 qlo, qhi; // the segment's fp32 bounding box: the walk's bound and the pair gate
+};
+EZD bool segment_query(f3 a, f3 b, SegQuery& s) {
+  const float inf = __builtin_inff();
+  if (!(ez_abs(a.x) < inf && ez_abs(a.y) < inf && ez_abs(a.z) < inf && ez_abs(b.x) < inf && ez_abs(b.y) < inf && ez_abs(b.z) < inf)) return false;
+  const bool swap = tri_less(b, a);
+  s.a = a, s.b = b;
+  s.lo = tri_pick(swap, b, a), s.hi = tri_pick(swap, a, b);
+  s.qlo = mk(ez_min(a.x, b.x), ez_min(a.y, b.y), ez_min(a.z, b.z));
+  s.qhi = mk(ez_max(a.x, b.x), ez_max(a.y, b.y), ez_max(a.z, b.z));
+  return true;
+}
+// tri_distance_box of the query's bounding box against triangle k's OWN bounding box: the pair gate of both segment kernels (a NaN
+// vertex gives a NaN lb, which fails every comparison and goes on to segment_pair, where the triangle is found not live)
+EZD float segment_gate(const float4* __restrict__ tg, const SegQuery& s) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const f3 lo = mk(ez_min(ez_min(ga.x, gb.x), gc.x), ez_min(ez_min(ga.y, gb.y), gc.y), ez_min(ez_min(ga.z, gb.z), gc.z));
+  const f3 hi = mk(ez_max(ez_max(ga.x, gb.x), gc.x), ez_max(ez_max(ga.y, gb.y), gc.y), ez_max(ez_max(ga.z, gb.z), gc.z));
+  return tri_distance_box(s.qlo, s.qhi, lo, hi);
+}
+// the running answer is TriDistanceBest, with its order: the smallest dist2, a crossing pair first, then the smallest index
+EZD void segment_candidate(TriDistanceBest& r, const float4* __restrict__ tri_geom, int32_t k, const SegQuery& s) {
+  f3 x, y;
+  float d2;
+  bool crosses;
+  if (!segment_pair(tri_geom + (size_t)k * 3, s.a, s.b, s.lo, s.hi, d2, x, y, crosses)) return;
+  if (d2 < r.best || (d2 == r.best && (r.tri < 0 || (crosses && !r.crosses) || (crosses == r.crosses && k < r.tri))))
+    r.best = d2, r.tri = k, r.x = x, r.y = y, r.crosses = crosses;
+}
+
 // ---------------------------------------------------------------------------
 // Winner reconstruction: the rest of hitTriangle (P5/fsh:172-178, 199-214) and
 // getMaterial (P5/fsh:110-135), evaluated once per ray for the closest hit.

@@ -1,8 +1,8 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
-// self-overlap, triangle-distance and sphere-cast queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
-// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h).  One query point, box, triangle or ray per lane,
-// a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// self-overlap, triangle-distance, sphere-cast and segment queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
+// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h).  One query point, box,
+// triangle, ray or segment per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -12,7 +12,8 @@
 //   slot_walk                        the depth-first walk over the 4-wide records that inside, box overlap and triangle overlap share
 //   inside_kernel<WALK>              inside_count: slot_walk on the rows its axis needs
 //   signed_distance_kernel<WALK>     inside_count + closest_point_search + closest_point_store
-//   overlap_rows                     slot_walk carrying a K-entry list of the lowest ids and a count, and the wave's row finish
+//   collect_rows                     a K-entry list of the lowest ids and a count over the caller's traversal, and the wave's row finish
+//   overlap_rows                     collect_rows over slot_walk on the query's box
 //   box_overlap_kernel<WALK>         overlap_rows with the box as the gate and box_overlaps as the rule
 //   box_overlap_at_kernel            box_overlaps for pairs the caller holds
 //   tri_overlap_kernel<WALK>         overlap_rows with the query triangle's bounding box as the gate and tri_overlaps as the rule
@@ -24,6 +25,9 @@
 //   sphere_cast_kernel<WALK>         closest_point_search with B = r * r, then point_walk with sphere_cast_box as the bound and
 //                                    sphere_cast_pair as the rule
 //   sphere_cast_at_kernel            sphere_cast_at for pairs the caller holds
+//   segment_distance_kernel<WALK>    point_walk with tri_distance_box of the segment's box as the bound and segment_pair as the rule
+//   segment_distance_at_kernel       segment_pair for pairs the caller holds
+//   capsule_overlap_kernel<WALK>     collect_rows over point_walk with the constant radius R2 and segment_pair's dist2 <= R2 as the rule
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -459,8 +463,10 @@ struct BoxOverlapArgs {
 // the wave's row finish.  `a` has sc, n, K, div_k, tri and n_overlap; load(i, q) reads query i into q and says whether it is live;
 // q.lo and q.hi are the gate of the walk (the box itself, or the query triangle's bounding box); overlaps(tri_geom_k, q) is the
 // per-triangle rule, of which the gate is a necessary condition on the triangle's own bounding box (H1, T1).
-template <bool WALK, class Query, class Args, class Load, class Overlaps>
-EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Overlaps overlaps) {
+// (collect_rows is that body with the traversal left to the caller: search(q, visit) calls visit(k) for every triangle that may pass
+// `overlaps` -- overlap_rows' depth-first slot_walk on the query's box, or capsule_overlap_kernel's point_walk on a distance bound.)
+template <class Query, class Args, class Load, class Overlaps, class Search>
+EZD void collect_rows(const Args& a, Load load, Overlaps overlaps, Search search) {
   const uint32_t lane = threadIdx.x;
   const uint32_t i = blockIdx.x * CP_BLOCK + lane;
   const int K = a.K;
@@ -488,30 +494,7 @@ EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Ove
       }
       put(j, k);
     };
-    if (live) {
-      if (WALK) {
-        const f3 &lo = q.lo, &hi = q.hi;
-        slot_walk(
-            a.sc.inner4, lds_stack + lane,
-            [&](const float4* rec, auto take) {
-              const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
-              const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
-              auto pass = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
-                return [=, &lo, &hi] { return lx <= hi.x && hx >= lo.x && ly <= hi.y && hy >= lo.y && lz <= hi.z && hz >= lo.z; };
-              };
-              take(pass(ax.x, ay.x, az.x, bx.x, by.x, bz.x), __float_as_uint(rf.x));
-              take(pass(ax.y, ay.y, az.y, bx.y, by.y, bz.y), __float_as_uint(rf.y));
-              take(pass(ax.z, ay.z, az.z, bx.z, by.z, bz.z), __float_as_uint(rf.z));
-              take(pass(ax.w, ay.w, az.w, bx.w, by.w, bz.w), __float_as_uint(rf.w));
-            },
-            visit);
-#pragma unroll 1
-        for (int u = 0; u < a.sc.n_uncovered; u++) visit(a.sc.uncovered[u]);
-      } else {
-#pragma unroll 1
-        for (int k = 0; k < a.sc.n_tri; k++) visit(k);
-      }
-    }
+    if (live) search(q, visit);
     if (a.n_overlap) a.n_overlap[i] = count;
   }
   // the wave's 64 rows, one flat run of 64 K words from its first row; the rows were written by other lanes of this wave, whose
@@ -524,6 +507,33 @@ EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Ove
     const int used = __shfl(nb, (int)row);
     if (i - lane + row < a.n && slot >= (uint32_t)used) a.tri[base + e] = -1;
   }
+}
+template <bool WALK, class Query, class Args, class Load, class Overlaps>
+EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Overlaps overlaps) {
+  collect_rows<Query>(a, load, overlaps, [&](const Query& q, auto& visit) {
+    if (WALK) {
+      const f3 &lo = q.lo, &hi = q.hi;
+      slot_walk(
+          a.sc.inner4, lds_stack + threadIdx.x,
+          [&](const float4* rec, auto take) {
+            const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
+            const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
+            auto pass = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+              return [=, &lo, &hi] { return lx <= hi.x && hx >= lo.x && ly <= hi.y && hy >= lo.y && lz <= hi.z && hz >= lo.z; };
+            };
+            take(pass(ax.x, ay.x, az.x, bx.x, by.x, bz.x), __float_as_uint(rf.x));
+            take(pass(ax.y, ay.y, az.y, bx.y, by.y, bz.y), __float_as_uint(rf.y));
+            take(pass(ax.z, ay.z, az.z, bx.z, by.z, bz.z), __float_as_uint(rf.z));
+            take(pass(ax.w, ay.w, az.w, bx.w, by.w, bz.w), __float_as_uint(rf.w));
+          },
+          visit);
+#pragma unroll 1
+      for (int u = 0; u < a.sc.n_uncovered; u++) visit(a.sc.uncovered[u]);
+    } else {
+#pragma unroll 1
+      for (int k = 0; k < a.sc.n_tri; k++) visit(k);
+    }
+  });
 }
 struct BoxQuery {
   f3 lo, hi;
@@ -811,6 +821,125 @@ __global__ __launch_bounds__(256) void sphere_cast_at_kernel(const float4* tri_g
   SphereRay q;
   if ((uint32_t)tri < (uint32_t)n_tri && sphere_cast_live(ld3(ray), ld3(ray + 3), radius[i], q)) sphere_cast_at(r, tri_geom, tri, q);
   sphere_cast_store(t, point, touching, i, r);
+}
+
+// ---- segment queries (include/ezrt_segment.h).
+//
+// segment_distance_kernel<WALK>: one query segment per lane, as tri_distance_kernel: point_walk on the lane's stack column of
+// 2 * (stack_need_cp + 1) rows with the running best dist2 as the radius (RECHECK) and tri_distance_box against the segment's own fp32
+// bounding box [qlo, qhi] = [min(a, b), max(a, b)] as the lower bound of a slot's box.
+// Why no margin is needed, for THIS rule: every x of segment_pair is an end point -- a corner of [qlo, qhi] per axis -- or comes
+// out of seg_point(a, b, ..), which clamps it into [min(a, b), max(a, b)] = [qlo, qhi]; every y is closest_point_abc's q, clamped to the
+// triangle's bounding box, or seg_point's of an edge, clamped to the edge's box, which lies in the triangle's; and the triangle's box
+// lies in every box above it (the scene prunes).  Per axis either g = 0 <= |e|, or g = fl(lo - qhi) with y >= lo > qhi >= x: y - x >=
+// lo - qhi in the reals, rounding is monotone and |fl(x - y)| = fl(y - x), so |e| >= g (the same on the other side).  fl(x * x) is
+// monotone in |x| and fl(fl(X + Y) + Z) in each of X, Y, Z >= 0, so lb <= d2 ON THE BITS for each of the five sub-candidates with a
+// finite d2, overflow included, hence lb <= their smallest.  A pair that crosses has dist2 = 0 -- and passes T1, which is why T1 is in
+// the rule: its boxes overlap on every axis, g = 0 on each and lb = 0.  A skipped subtree therefore holds no pair with dist2 <=
+// radius, neither a winner nor a tie.  The pair gate: the same lb of triangle k's OWN bounding box (segment_gate) before the five
+// sub-candidates and the fp64 test; a triangle with lb > best can neither win nor tie.
+// Triangles that no leaf holds are swept after the walk.  WALK = false, the sweep route: every triangle, no tree.
+struct SegmentDistanceArgs {
+  PointScene sc;
+  const float* segs;        // n x 6: a, b
+  const float* d_max;       // n, or null
+  uint32_t n;
+  int32_t* tri;             // n
+  float* dist;              // n, or null
+  float* point_query;       // n x 3, or null
+  float* point_scene;       // n x 3, or null
+  uint8_t* crosses;         // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void segment_distance_kernel(SegmentDistanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const float* t = a.segs + (size_t)i * 6;
+  TriDistanceBest r;
+  r.tri = -1;
+  r.x = r.y = mk(0.0f, 0.0f, 0.0f);
+  r.crosses = false;
+  r.best = __builtin_inff();
+  bool live = true;
+  if (a.d_max) { // B = d_max^2; a negative or NaN d_max gives no candidates
+    const float dm = a.d_max[i];
+    if (dm >= 0.0f) r.best = dm * dm;
+    else live = false;
+  }
+  SegQuery q;
+  if (live && segment_query(ld3(t), ld3(t + 3), q))
+    bound_visit<WALK, true>(
+        a.sc, [&](f3 lo, f3 hi) { return tri_distance_box(q.qlo, q.qhi, lo, hi); }, lds_stack + threadIdx.x, [&] { return r.best; },
+        [&](int32_t k) {
+          if (segment_gate(a.sc.tri_geom + (size_t)k * 3, q) > r.best) return; // the pair gate
+          segment_candidate(r, a.sc.tri_geom, k, q);
+        });
+  a.tri[i] = r.tri;
+  tri_distance_store(a.dist, a.point_query, a.point_scene, a.crosses, i, r);
+}
+
+// ezrt_segment_distance_at_device: segment_pair for pairs the caller holds -- query segment i against triangle tri_id[i], no gate.  An
+// id outside the scene, a segment or a triangle that is not live or a pair without a finite sub-candidate writes (+inf, zeros, zeros, 0).
+__global__ __launch_bounds__(256) void segment_distance_at_kernel(const float4* tri_geom, int32_t n_tri, const float* segs, const int32_t* tri_id,
+                                                                  uint32_t n, float* dist, float* point_query, float* point_scene, uint8_t* crosses) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  const float* t = segs + (size_t)i * 6;
+  TriDistanceBest r;
+  r.tri = -1;
+  r.x = r.y = mk(0.0f, 0.0f, 0.0f);
+  r.crosses = false;
+  r.best = __builtin_inff();
+  SegQuery q;
+  if ((uint32_t)tri < (uint32_t)n_tri && segment_query(ld3(t), ld3(t + 3), q)) segment_candidate(r, tri_geom, tri, q);
+  tri_distance_store(dist, point_query, point_scene, crosses, i, r);
+}
+
+// capsule_overlap_kernel<WALK>: one capsule per lane; the list, the count and the wave's row finish are collect_rows', as for the
+// other overlap kernels.  What differs is the traversal: the rule is a distance (dist2 <= R2, R2 = radius * radius), so the walk is
+// bound_visit's point_walk with the CONSTANT radius R2 (no RECHECK: an entry passed at its push) and, as in segment_distance_kernel,
+// tri_distance_box against the segment's bounding box as the bound: a slot is descended when lb <= R2.  lb <= dist2 on the bits
+// (above) makes that a necessary condition with no slack.  The segment's box is NOT inflated by the radius: fl(qhi + r) can round
+// below qhi + r, and a triangle's box between the two would be cut off although its dist2 <= R2.  An unused slot (an all-NaN box)
+// gets lb = +inf in point_walk, which is never descended, whatever R2 is -- +inf included.  The same lb of the triangle's own box
+// gates the pair.  Launched with point_walk's column of 2 * (stack_need_cp + 1) rows.
+struct CapsuleQuery : SegQuery {
+  float R2;
+};
+struct CapsuleOverlapArgs {
+  PointScene sc;
+  const float* segs;        // n x 6: a, b
+  const float* radius;      // n
+  uint32_t n;
+  int32_t K;                // 0 .. 64
+  FastDiv div_k;            // / max(K, 1) (the finishing pass)
+  int32_t* tri;             // n x K (not read or written when K == 0)
+  int32_t* n_overlap;       // n, or null
+};
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_kernel(CapsuleOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  collect_rows<CapsuleQuery>(
+      a,
+      [&](uint32_t i, CapsuleQuery& q) {
+        const float* t = a.segs + (size_t)i * 6;
+        const float r = a.radius[i];
+        q.R2 = r * r;
+        return r >= 0.0f && r < __builtin_inff() && segment_query(ld3(t), ld3(t + 3), q); // (false for a NaN radius)
+      },
+      [](const float4* tg, const CapsuleQuery& q) {
+        if (segment_gate(tg, q) > q.R2) return false; // the pair gate
+        f3 x, y;
+        float d2;
+        bool crosses;
+        return segment_pair(tg, q.a, q.b, q.lo, q.hi, d2, x, y, crosses) && d2 <= q.R2;
+      },
+      [&](const CapsuleQuery& q, auto& visit) {
+        bound_visit<WALK, false>(
+            a.sc, [&](f3 lo, f3 hi) { return tri_distance_box(q.qlo, q.qhi, lo, hi); }, lds_stack + threadIdx.x, [&] { return q.R2; }, visit);
+      });
 }
 
 } // namespace ezd

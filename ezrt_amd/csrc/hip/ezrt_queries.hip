@@ -1,8 +1,8 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance and sphere-cast queries
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast and segment queries
 // (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h,
-// ezrt_tri_distance.h, ezrt_sphere_cast.h).  A translation unit of its own: none of its kernels is compiled together
+// ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h).  A translation unit of its own: none of its kernels is compiled together
 // with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run
 // the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in
 // ezrt_launch.hip.  DESIGN.md 5.
@@ -18,6 +18,7 @@
 #include "ezrt_self_overlap.h"
 #include "ezrt_tri_distance.h"
 #include "ezrt_sphere_cast.h"
+#include "ezrt_segment.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -567,6 +568,75 @@ int ezrt_sphere_cast_at_device(EzrtScene* s, const float* rays6, const float* ra
                           {point, N * 3 * sizeof(float)}, {touching, N}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(sphere_cast_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, rays6, radius, tri_id, (uint32_t)n, t, point,
                          touching);
+    });
+  });
+}
+
+// ---- segment queries on device memory (include/ezrt_segment.h): one kernel each on `st`, no scratch (a capsule's list is kept in its
+// own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_segment_distance_device(EzrtScene* s, const float* segs6, const float* d_max, int n, int32_t* tri_id, float* dist,
+                                       float* point_query, float* point_scene, uint8_t* crosses, void* stream) {
+  return ezi::guarded("ezrt_query_segment_distance_device", [&]() -> int {
+    if (!s || !segs6 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{segs6, N * 6 * sizeof(float)}, {d_max, N * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {dist, N * sizeof(float)},
+                          {point_query, N * 3 * sizeof(float)}, {point_scene, N * 3 * sizeof(float)}, {crosses, N}}, N, st, [&](dim3, dim3) {
+      SegmentDistanceArgs a;
+      const PointRoute r = ::point_scene(s, a.sc); // (the function: the parameter of that name is the output)
+      a.segs = segs6;
+      a.d_max = d_max;
+      a.n = (uint32_t)n;
+      a.tri = tri_id;
+      a.dist = dist;
+      a.point_query = point_query;
+      a.point_scene = point_scene;
+      a.crosses = crosses;
+      launch_routed(segment_distance_kernel<true>, segment_distance_kernel<false>, r, r.lds, N, st, a);
+    });
+  });
+}
+int ezrt_segment_distance_at_device(EzrtScene* s, const float* segs6, const int32_t* tri_id, int n, float* dist, float* point_query,
+                                    float* point_scene, uint8_t* crosses, void* stream) {
+  return ezi::guarded("ezrt_segment_distance_at_device", [&]() -> int {
+    if (!s || !segs6 || !tri_id || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (!dist && !point_query && !point_scene && !crosses)
+      return fail(EZRT_ERR_INVALID, "one of dist, point_query, point_scene and crosses is required");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{segs6, N * 6 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {dist, N * sizeof(float)},
+                          {point_query, N * 3 * sizeof(float)}, {point_scene, N * 3 * sizeof(float)}, {crosses, N}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(segment_distance_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, segs6, tri_id, (uint32_t)n, dist,
+                         point_query, point_scene, crosses);
+    });
+  });
+}
+int ezrt_query_capsule_overlap_device(EzrtScene* s, const float* segs6, const float* radius, int n, int max_k, int32_t* tri_id,
+                                      int32_t* n_overlap, void* stream) {
+  return ezi::guarded("ezrt_query_capsule_overlap_device", [&]() -> int {
+    if (!s || !segs6 || !radius || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 0 || max_k > EZRT_CAPSULE_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_CAPSULE_OVERLAP_MAX);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{segs6, N * 6 * sizeof(float)}, {radius, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      CapsuleOverlapArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.segs = segs6;
+      a.radius = radius;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      // this walk is point_walk: {lb, ref} entries, the whole column
+      launch_routed(capsule_overlap_kernel<true>, capsule_overlap_kernel<false>, r, r.lds, N, st, a);
     });
   });
 }

@@ -1,6 +1,7 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
-include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h).
+include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
+include/ezrt_segment.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -24,6 +25,9 @@ include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distan
     tri, dist, point_query, point_scene, crosses = query.tri_distance_at(scene, tris, tri)  # ... for pairs already held (include/ezrt_tri_distance.h)
     tri, t, point, touching = query.sphere_cast(scene, rays, radius, t_max)   # first contact of a sphere moving along each ray
     tri, t, point, touching = query.sphere_cast_at(scene, rays, radius, tri)  # ... for pairs already held (include/ezrt_sphere_cast.h)
+    tri, dist, point_query, point_scene, crosses = query.segment_distance(scene, segs, d_max)   # how close each segment comes to the mesh
+    tri, dist, point_query, point_scene, crosses = query.segment_distance_at(scene, segs, tri)  # ... for pairs already held
+    tri, n_overlap = query.capsule_overlap(scene, segs, radius, max_k=8)      # the triangles each capsule touches (include/ezrt_segment.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -38,6 +42,8 @@ origin offset by the caller.  A miss is (-1, 114514.0): ezrt_query_hits' miss (t
 `sphere_cast` is not the reference's rule: `radius` is a float32 GPU tensor of shape rays.shape[:-1] in world units, the direction
 need not have unit length and t is in units of it (the centre at time t is o + d*t), a contact is accepted from t = 0 on, and a
 miss is the point queries' (-1, +inf, zeros, False).
+`segs` is a contiguous float32 GPU tensor of shape [..., 6] that holds THE TWO END POINTS a, b of every segment -- not an origin and a
+direction, as every `rays` above does: the segment of a ray up to t is (o, o + d*t).
 """
 import collections
 import ctypes as C
@@ -56,6 +62,8 @@ TriOverlap = collections.namedtuple("TriOverlap", "tri n_overlap")
 SelfOverlap = collections.namedtuple("SelfOverlap", "tri n_overlap")
 TriDistance = collections.namedtuple("TriDistance", "tri dist point_query point_scene crosses")
 SphereCast = collections.namedtuple("SphereCast", "tri t point touching")
+SegmentDistance = collections.namedtuple("SegmentDistance", "tri dist point_query point_scene crosses")
+CapsuleOverlap = collections.namedtuple("CapsuleOverlap", "tri n_overlap")
 
 
 def _scene_lib(scene, abi):
@@ -699,3 +707,102 @@ def sphere_cast_at(scene, rays, radius, tri, stream=None):
                                                 P(point.data_ptr()), P(touching.data_ptr()), P(h)))
     _keep((rays, radius, per, per_r, tri, t, point, touching), ts, rays)
     return SphereCast(tri, t, point, touching.view(torch.bool))
+
+
+def _check_segs(segs):
+    """The number of segments, after the checks every segment query makes of them."""
+    _tensor("segs", segs, torch.float32, last=6)
+    return _count(segs, 6, "segments")
+
+
+def segment_distance(scene, segs, d_max=None, stream=None):
+    """SegmentDistance(tri int32 [...], dist float32 [...], point_query float32 [..., 3], point_scene float32 [..., 3], crosses bool
+    [...]): for every segment of `segs` (a contiguous float32 GPU tensor [..., 6]: THE TWO END POINTS a, b -- not an origin and a
+    direction) the nearest triangle of the scene, the distance between the two, and the points where they come closest --
+    `point_query` on the segment, `point_scene` on the triangle.  The distance is taken over the two end points against the face and
+    the segment against the three edges; where the segment crosses or touches the triangle it is 0 and `crosses` is set, and the two
+    points are then the nearest features, not a common point.  `d_max` (optional, float32, of shape segs.shape[:-1]) admits only
+    triangles within that distance: the clearance check of a capsule of that radius.  A miss is (-1, +inf, zeros, zeros, False).
+    Equal distances: a triangle that is crossed first, then the lowest triangle index.  a == b is a point.  A segment with a
+    non-finite number misses; a triangle with a non-finite number or with collinear or repeated vertices is never found.  The
+    definition, on the bits: include/ezrt_segment.h; `segment_distance_at` evaluates pairs."""
+    n = _check_segs(segs)
+    if d_max is not None:
+        _tensor("d_max", d_max, torch.float32, segs.shape[:-1], device=segs.device)
+    lead = tuple(segs.shape[:-1])
+    lib = _scene_lib(scene, _abi.SEGMENT_ABI)
+    tri = torch.empty(lead, dtype=torch.int32, device=segs.device)
+    dist = torch.empty(lead, dtype=torch.float32, device=segs.device)
+    point_query = torch.empty(lead + (3,), dtype=torch.float32, device=segs.device)
+    point_scene = torch.empty(lead + (3,), dtype=torch.float32, device=segs.device)
+    crosses = torch.empty(lead, dtype=torch.uint8, device=segs.device)
+    if n == 0:
+        return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+    h, ts = _stream(segs, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_segment_distance_device(scene._h, P(segs.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None,
+                                                        n, P(tri.data_ptr()), P(dist.data_ptr()), P(point_query.data_ptr()),
+                                                        P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
+    _keep((segs, d_max, tri, dist, point_query, point_scene, crosses), ts, segs)
+    return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+
+
+def segment_distance_at(scene, segs, tri, stream=None):
+    """SegmentDistance(tri, dist float32 tri.shape, point_query float32 tri.shape + (3,), point_scene float32 tri.shape + (3,),
+    crosses bool tri.shape): for triangle tri[...] of the scene and its segment (`segs` [..., 6]: the two END POINTS), what
+    `segment_distance` gives for its winner.  `tri` (int32) has the shape segs.shape[:-1], or one trailing dimension more -- rows of
+    `capsule_overlap` or `nearest` -- and every entry of a row then belongs to the row's segment.  An id that is no triangle of the
+    scene (an unused slot, -1), a segment with a non-finite number or a triangle that is not live gives (+inf, zeros, zeros, False).
+    `tri` is returned as given."""
+    _check_segs(segs)
+    lib = _scene_lib(scene, _abi.SEGMENT_ABI)
+    lead = tuple(segs.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=segs.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    dist = torch.empty(shape, dtype=torch.float32, device=segs.device)
+    point_query = torch.empty(shape + (3,), dtype=torch.float32, device=segs.device)
+    point_scene = torch.empty(shape + (3,), dtype=torch.float32, device=segs.device)
+    crosses = torch.empty(shape, dtype=torch.uint8, device=segs.device)
+    if n == 0:
+        return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+    h, ts = _stream(segs, stream)
+    per = _per_entry(segs, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_segment_distance_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(dist.data_ptr()),
+                                                     P(point_query.data_ptr()), P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
+    _keep((segs, per, tri, dist, point_query, point_scene, crosses), ts, segs)
+    return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
+
+
+def capsule_overlap(scene, segs, radius, max_k=8, count=False, stream=None):
+    """CapsuleOverlap(tri int32 [..., max_k], n_overlap int32 [...] or None): for every capsule -- the segment of `segs` (a contiguous
+    float32 GPU tensor [..., 6]: THE TWO END POINTS a, b, not an origin and a direction) and its `radius` (float32, of shape
+    segs.shape[:-1], world units) -- the triangles of the scene within `radius` of the segment by `segment_distance`'s rule:
+    dist2 <= radius*radius in float32.  `tri` holds the lowest triangle indices in ascending order, then -1: a larger max_k (0 .. 64)
+    only appends, and the answer depends on neither the tree nor the order of the visits.  `count=True` also returns the full number
+    of such triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count` must be True).
+    radius == 0 lists the triangles the segment crosses or touches, and any whose nearest point rounds onto it.  A capsule with a
+    non-finite number or a negative radius touches nothing.  `segment_distance(scene, segs, radius)` finds a triangle exactly where
+    the count here is > 0.  The definition, on the bits: include/ezrt_segment.h."""
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.CAPSULE_OVERLAP_MAX:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.CAPSULE_OVERLAP_MAX, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    n = _check_segs(segs)
+    _tensor("radius", radius, torch.float32, segs.shape[:-1], device=segs.device)
+    lib = _scene_lib(scene, _abi.SEGMENT_ABI)
+    lead = tuple(segs.shape[:-1])
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=segs.device)
+    total = torch.empty(lead, dtype=torch.int32, device=segs.device) if count else None
+    if n == 0:
+        return CapsuleOverlap(tri, total)
+    h, ts = _stream(segs, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_capsule_overlap_device(scene._h, P(segs.data_ptr()), P(radius.data_ptr()), n, max_k,
+                                                       P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None,
+                                                       P(h)))
+    _keep((segs, radius, tri, total), ts, segs)
+    return CapsuleOverlap(tri, total)
