@@ -268,6 +268,16 @@ SEGMENT_ABI = {
 CAPSULE_OVERLAP_MAX = 64  # EZRT_CAPSULE_OVERLAP_MAX
 
 
+# stream-ordered oriented-box queries on device memory, libezrt_hip.so only (include/ezrt_obb_overlap.h); pointers are device addresses
+OBB_OVERLAP_ABI = {
+    # s, centre3, axes9, n, max_k, tri_id, n_overlap, stream
+    "ezrt_query_obb_overlap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, centre3, axes9, tri_id, n, overlaps, stream
+    "ezrt_obb_overlap_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+OBB_OVERLAP_MAX = 64  # EZRT_OBB_OVERLAP_MAX
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -336,7 +346,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      REFIT_ABI):
+                      OBB_OVERLAP_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

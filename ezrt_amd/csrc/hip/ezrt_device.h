@@ -538,6 +538,127 @@ EZD bool box_overlaps(const float4* __restrict__ tg, f3 lo, f3 hi) {
   return true;
 }
 
+// ---- oriented-box queries (include/ezrt_obb_overlap.h, where the definition is the contract): the per-box numbers (obb_query: n_j,
+// r_j and the hull, once per box), the two gates of a walk (obb_hull_gate, obb_face_gate) and H0 .. H3 of one triangle against a LIVE
+// box (obb_overlaps), in the header's order.  H0 is asked in fp32 against the hull rounded inward -- the same answer as the fp64
+// comparison for every fp32 coordinate, a NaN or an infinity included.  The axes are kept as the caller's fp32 numbers and converted
+// where they are used (exact, and 9 registers instead of 18); only one edge's fp64 state is live at a time, as in box_overlaps: the
+// three edges are one loop that is not unrolled, with (A, B, C) moved from one edge to the next between its rounds.
+struct d3 {
+  double x, y, z;
+};
+EZD d3 obb_up(f3 u) { return d3{(double)u.x, (double)u.y, (double)u.z}; }
+EZD d3 obb_d(f3 x, f3 y) { return d3{(double)x.x - (double)y.x, (double)x.y - (double)y.y, (double)x.z - (double)y.z}; }
+EZD double obb_dot(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+EZD d3 obb_cross(d3 a, d3 b) { return d3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// x rounded to fp32 toward minus infinity / toward plus infinity (x finite; a result past the largest float is that float's)
+EZD float obb_round_down(double x) {
+  const float f = (float)x;
+  if (!((double)f > x)) return f;
+  const uint32_t b = __builtin_bit_cast(uint32_t, f);
+  return __builtin_bit_cast(float, f > 0.0f ? b - 1u : (f < 0.0f ? b + 1u : 0x80000001u));
+}
+EZD float obb_round_up(double x) { return -obb_round_down(-x); }
+struct ObbQuery {
+  f3 c, u0, u1, u2; // the caller's twelve numbers
+  f3 lo, hi;        // the hull rounded inward to fp32: the first gate of the walk, and H0
+  d3 n0, n1, n2;    // the face directions
+  double r0, r1, r2;
+};
+// the box as the kernels hold it; false when it is not live (q is then not to be used)
+EZD bool obb_query(f3 c, f3 u0, f3 u1, f3 u2, ObbQuery& q) {
+  const float inf = __builtin_inff();
+  if (!(ez_abs(c.x) < inf && ez_abs(c.y) < inf && ez_abs(c.z) < inf && ez_abs(u0.x) < inf && ez_abs(u0.y) < inf && ez_abs(u0.z) < inf &&
+        ez_abs(u1.x) < inf && ez_abs(u1.y) < inf && ez_abs(u1.z) < inf && ez_abs(u2.x) < inf && ez_abs(u2.y) < inf && ez_abs(u2.z) < inf))
+    return false;
+  q.c = c, q.u0 = u0, q.u1 = u1, q.u2 = u2;
+  const d3 U0 = obb_up(u0), U1 = obb_up(u1), U2 = obb_up(u2);
+  q.n0 = obb_cross(U1, U2), q.n1 = obb_cross(U2, U0), q.n2 = obb_cross(U0, U1);
+  q.r0 = __builtin_fabs(obb_dot(q.n0, U0)), q.r1 = __builtin_fabs(obb_dot(q.n1, U1)), q.r2 = __builtin_fabs(obb_dot(q.n2, U2));
+  const double hx = (__builtin_fabs(U0.x) + __builtin_fabs(U1.x)) + __builtin_fabs(U2.x);
+  const double hy = (__builtin_fabs(U0.y) + __builtin_fabs(U1.y)) + __builtin_fabs(U2.y);
+  const double hz = (__builtin_fabs(U0.z) + __builtin_fabs(U1.z)) + __builtin_fabs(U2.z);
+  q.lo = mk(obb_round_up((double)c.x - hx), obb_round_up((double)c.y - hy), obb_round_up((double)c.z - hz));
+  q.hi = mk(obb_round_down((double)c.x + hx), obb_round_down((double)c.y + hy), obb_round_down((double)c.z + hz));
+  return q.r0 > 0.0 && q.r1 > 0.0 && q.r2 > 0.0;
+}
+// the first gate of a slot's box [lo, hi]: H0 on the box.  An unused slot (an all-NaN box) fails it.
+EZD bool obb_hull_gate(const ObbQuery& q, f3 lo, f3 hi) {
+  return lo.x <= q.hi.x && hi.x >= q.lo.x && lo.y <= q.hi.y && hi.y >= q.lo.y && lo.z <= q.hi.z && hi.z >= q.lo.z;
+}
+// one face direction against the box [c + dl, c + dh] (dl = d(lo, c), dh = d(hi, c)): p_j at the corner chosen per component by the
+// sign of n[c], by the rule's own expression.  pmin <= p_j(v) <= pmax on the bits for every fp32 v in the box: no margin.
+EZD bool obb_face_misses(d3 n, double r, d3 dl, d3 dh) {
+  const double lx = n.x * dl.x, hx = n.x * dh.x, ly = n.y * dl.y, hy = n.y * dh.y, lz = n.z * dl.z, hz = n.z * dh.z;
+  const bool ux = n.x >= 0.0, uy = n.y >= 0.0, uz = n.z >= 0.0;
+  const double pmin = ((ux ? lx : hx) + (uy ? ly : hy)) + (uz ? lz : hz);
+  const double pmax = ((ux ? hx : lx) + (uy ? hy : ly)) + (uz ? hz : lz);
+  return pmin > r || pmax < -r; // (false for a NaN: such a box is not skipped)
+}
+// the second gate, asked only behind the first: no face direction has the whole box on one side
+EZD bool obb_face_gate(const ObbQuery& q, f3 lo, f3 hi) {
+  const d3 dl = obb_d(lo, q.c), dh = obb_d(hi, q.c);
+  return !(obb_face_misses(q.n0, q.r0, dl, dh) || obb_face_misses(q.n1, q.r1, dl, dh) || obb_face_misses(q.n2, q.r2, dl, dh));
+}
+// H1 for one j: some vertex has p <= r and some vertex has p >= -r
+EZD bool obb_face_holds(d3 n, double r, d3 da, d3 db, d3 dc) {
+  const double pa = obb_dot(n, da), pb = obb_dot(n, db), pc = obb_dot(n, dc);
+  return (pa <= r || pb <= r || pc <= r) && (pa >= -r || pb >= -r || pc >= -r);
+}
+// does cross(U_j, e) separate?  q = d(C, A), g = d(c, A); (Uv, Uw) = (U_{j+1}, U_{j+2})
+EZD bool obb_edge_axis_separates(f3 uj, f3 uv, f3 uw, d3 e, d3 q, d3 g) {
+  const d3 a = obb_cross(obb_up(uj), e);
+  const double t = obb_dot(a, q), s = obb_dot(a, g);
+  const double R = __builtin_fabs(obb_dot(a, obb_up(uv))) + __builtin_fabs(obb_dot(a, obb_up(uw)));
+  return s - R > (t > 0.0 ? t : 0.0) || s + R < (t < 0.0 ? t : 0.0);
+}
+EZD bool obb_overlaps(const float4* __restrict__ tg, const ObbQuery& q) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  f3 a = mk(ga.x, ga.y, ga.z), b = mk(gb.x, gb.y, gb.z), c = mk(gc.x, gc.y, gc.z);
+  if (!((a.x <= q.hi.x || b.x <= q.hi.x || c.x <= q.hi.x) && (a.x >= q.lo.x || b.x >= q.lo.x || c.x >= q.lo.x))) return false; // H0
+  if (!((a.y <= q.hi.y || b.y <= q.hi.y || c.y <= q.hi.y) && (a.y >= q.lo.y || b.y >= q.lo.y || c.y >= q.lo.y))) return false;
+  if (!((a.z <= q.hi.z || b.z <= q.hi.z || c.z <= q.hi.z) && (a.z >= q.lo.z || b.z >= q.lo.z || c.z >= q.lo.z))) return false;
+  const float inf = __builtin_inff();
+  if (!(ez_abs(a.x) < inf && ez_abs(a.y) < inf && ez_abs(a.z) < inf && ez_abs(b.x) < inf && ez_abs(b.y) < inf && ez_abs(b.z) < inf &&
+        ez_abs(c.x) < inf && ez_abs(c.y) < inf && ez_abs(c.z) < inf))
+    return false; // a non-finite vertex never overlaps
+  {
+    const d3 da = obb_d(a, q.c), db = obb_d(b, q.c), dc = obb_d(c, q.c);
+    if (!obb_face_holds(q.n0, q.r0, da, db, dc)) return false;                                                          // H1
+    if (!obb_face_holds(q.n1, q.r1, da, db, dc)) return false;
+    if (!obb_face_holds(q.n2, q.r2, da, db, dc)) return false;
+  }
+  auto cswap = [](f3& x, f3& y) {
+    if (y.x < x.x || (y.x == x.x && (y.y < x.y || (y.y == x.y && y.z < x.z)))) { // less(y, x)
+      const f3 h = x;
+      x = y, y = h;
+    }
+  };
+  cswap(a, b);
+  cswap(b, c);
+  cswap(a, b);
+  // (v0 v1 v2) = (a b c)
+  {
+    const d3 N = obb_cross(obb_d(b, a), obb_d(c, a));
+    const double s = obb_dot(N, obb_d(q.c, a));
+    const double R = (__builtin_fabs(obb_dot(N, obb_up(q.u0))) + __builtin_fabs(obb_dot(N, obb_up(q.u1)))) + __builtin_fabs(obb_dot(N, obb_up(q.u2)));
+    if (!(__builtin_fabs(s) <= R)) return false;                                                                         // H2
+  }
+  // H3: (A, B; C) = (v0, v1; v2), then (v1, v2; v0), then (v0, v2; v1)
+  f3 A = a, B = b, C = c;
+#pragma unroll 1
+  for (int edge = 0; edge < 3; edge++) {
+    const d3 e = obb_d(B, A), qq = obb_d(C, A), g = obb_d(q.c, A);
+    if (obb_edge_axis_separates(q.u0, q.u1, q.u2, e, qq, g)) return false;
+    if (obb_edge_axis_separates(q.u1, q.u2, q.u0, e, qq, g)) return false;
+    if (obb_edge_axis_separates(q.u2, q.u0, q.u1, e, qq, g)) return false;
+    const f3 h = A; // (v0, v1; v2) -> (v1, v2; v0): rotate;  (v1, v2; v0) -> (v0, v2; v1): exchange A and C
+    if (edge == 0) A = B, B = C, C = h;
+    else A = C, C = h;
+  }
+  return true;
+}
+
 // ---- triangle-overlap queries (include/ezrt_tri_overlap.h, where the definition is the contract): liveness, T1 and T2 of one scene
 // triangle against a LIVE query triangle (the caller has checked it with tri_live), in the header's order.  A direction g x axis_j
 // has x[j] = 0: its term x[j] * D[j] is a zero (D is finite), and adding a zero changes at most the sign of a zero sum, which no

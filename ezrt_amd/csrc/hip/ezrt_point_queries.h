@@ -1,8 +1,9 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
-// self-overlap, triangle-distance, sphere-cast and segment queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
-// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h).  One query point, box,
-// triangle, ray or segment per lane, a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// self-overlap, triangle-distance, sphere-cast, segment and oriented-box queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
+// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h,
+// include/ezrt_obb_overlap.h).  One query point, box, triangle, ray or segment per lane, a workgroup of one wave.  Included by
+// ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -28,6 +29,8 @@
 //   segment_distance_kernel<WALK>    point_walk with tri_distance_box of the segment's box as the bound and segment_pair as the rule
 //   segment_distance_at_kernel       segment_pair for pairs the caller holds
 //   capsule_overlap_kernel<WALK>     collect_rows over point_walk with the constant radius R2 and segment_pair's dist2 <= R2 as the rule
+//   obb_overlap_kernel<WALK>         collect_rows over slot_walk with the hull and the face directions as the gates and obb_overlaps as the rule
+//   obb_overlap_at_kernel            obb_overlaps for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -940,6 +943,83 @@ __global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_kernel(CapsuleOverla
         bound_visit<WALK, false>(
             a.sc, [&](f3 lo, f3 hi) { return tri_distance_box(q.qlo, q.qhi, lo, hi); }, lds_stack + threadIdx.x, [&] { return q.R2; }, visit);
       });
+}
+
+// ---- oriented-box queries (include/ezrt_obb_overlap.h).
+//
+// obb_overlap_kernel<WALK>: one box per lane; the list, the count and the wave's row finish are collect_rows', as for the other
+// overlap kernels, and the traversal is slot_walk directly -- overlap_rows is not widened: its gate is one fp32 box, this one has two.
+// A slot is descended when it passes both, the second asked only behind the first:
+//   1. the hull, by H0: slot.lo[c] <= hull_hi[c] && slot.hi[c] >= hull_lo[c] -- overlap_rows' six fp32 comparisons, against the hull
+//      rounded inward once per box (obb_query), which compares as the fp64 hull does.  An unused slot (an all-NaN box) fails here.
+//   2. the three face directions (obb_face_gate): p_j by the rule's own expression at the slot's corners chosen per component by the
+//      sign of n_j[c]; the slot is left when pmin > r_j || pmax < -r_j.
+// Why no margin is needed: by H0 an overlapping triangle's own bounding box passes 1, hence every box that holds the triangle (the
+// scene prunes).  For 2, rounding to nearest is monotone, and d(x, c), a product with a fixed factor and a sum are each monotone in
+// each operand: pmin <= p_j(v) <= pmax ON THE BITS for every fp32 point v in the slot's box, so with pmin > r_j no vertex below the
+// slot has p_j <= r_j, and with pmax < -r_j none has p_j >= -r_j -- every triangle below it fails H1.  A NaN (0 times an infinite
+// bound) fails both comparisons and the slot is descended.  Triangles that no leaf holds are swept after the walk.  WALK = false,
+// the sweep route: every triangle, no tree.  Both call obb_overlaps (ezrt_device.h: H0 .. H3 of the header) with the numbers of the
+// box -- n_j, r_j, the hull -- computed once, in obb_query.  Launched with slot_walk's column of stack_need_cp + 1 rows.
+struct ObbOverlapArgs {
+  PointScene sc;
+  const float* centre;      // n x 3
+  const float* axes;        // n x 9: u0 u1 u2
+  uint32_t n;
+  int32_t K;                // 0 .. 64
+  FastDiv div_k;            // / max(K, 1) (the finishing pass)
+  int32_t* tri;             // n x K (not read or written when K == 0)
+  int32_t* n_overlap;       // n, or null
+};
+EZD bool obb_load(const float* centre, const float* axes, uint32_t i, ObbQuery& q) {
+  const float* u = axes + (size_t)i * 9;
+  return obb_query(ld3(centre + (size_t)i * 3), ld3(u), ld3(u + 3), ld3(u + 6), q);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void obb_overlap_kernel(ObbOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  collect_rows<ObbQuery>(
+      a, [&](uint32_t i, ObbQuery& q) { return obb_load(a.centre, a.axes, i, q); },
+      [](const float4* tg, const ObbQuery& q) { return obb_overlaps(tg, q); },
+      [&](const ObbQuery& q, auto& visit) {
+        if (WALK) {
+          slot_walk(
+              a.sc.inner4, lds_stack + threadIdx.x,
+              [&](const float4* rec, auto take) {
+                const float4 ax = rec[N4_ROW_AA], ay = rec[N4_ROW_AA + 1], az = rec[N4_ROW_AA + 2], rf = rec[N4_ROW_REF];
+                const float4 bx = rec[N4_ROW_BB], by = rec[N4_ROW_BB + 1], bz = rec[N4_ROW_BB + 2];
+                auto pass = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+                  return [=, &q] {
+                    const f3 lo = mk(lx, ly, lz), hi = mk(hx, hy, hz);
+                    return obb_hull_gate(q, lo, hi) && obb_face_gate(q, lo, hi);
+                  };
+                };
+                take(pass(ax.x, ay.x, az.x, bx.x, by.x, bz.x), __float_as_uint(rf.x));
+                take(pass(ax.y, ay.y, az.y, bx.y, by.y, bz.y), __float_as_uint(rf.y));
+                take(pass(ax.z, ay.z, az.z, bx.z, by.z, bz.z), __float_as_uint(rf.z));
+                take(pass(ax.w, ay.w, az.w, bx.w, by.w, bz.w), __float_as_uint(rf.w));
+              },
+              visit);
+#pragma unroll 1
+          for (int u = 0; u < a.sc.n_uncovered; u++) visit(a.sc.uncovered[u]);
+        } else {
+#pragma unroll 1
+          for (int k = 0; k < a.sc.n_tri; k++) visit(k);
+        }
+      });
+}
+
+// ezrt_obb_overlap_at_device: obb_overlaps for pairs the caller holds -- box i against triangle tri_id[i].  An id outside the scene
+// or a box that is not live writes 0.
+__global__ __launch_bounds__(256) void obb_overlap_at_kernel(const float4* tri_geom, int32_t n_tri, const float* centre, const float* axes,
+                                                             const int32_t* tri_id, uint32_t n, uint8_t* overlaps) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  ObbQuery q;
+  bool o = false;
+  if ((uint32_t)tri < (uint32_t)n_tri && obb_load(centre, axes, i, q)) o = obb_overlaps(tri_geom + (size_t)tri * 3, q);
+  overlaps[i] = o ? 1u : 0u;
 }
 
 } // namespace ezd

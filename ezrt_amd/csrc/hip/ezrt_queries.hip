@@ -1,11 +1,11 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast and segment queries
-// (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h,
-// ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h).  A translation unit of its own: none of its kernels is compiled together
-// with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed kernel.  The ray queries that run
-// the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device, ezrt_query_surface_device) are in
-// ezrt_launch.hip.  DESIGN.md 5.
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment and
+// oriented-box queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h,
+// ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h).  A translation unit of its own: none
+// of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
+// kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
+// ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
 #include "ezrt_internal.h"
 #include "ezrt_shade.h"
 #include "ezrt_path.h"
@@ -19,6 +19,7 @@
 #include "ezrt_tri_distance.h"
 #include "ezrt_sphere_cast.h"
 #include "ezrt_segment.h"
+#include "ezrt_obb_overlap.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -399,6 +400,49 @@ int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* 
     return query_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
                       st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(box_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, box_lo3, box_hi3, tri_id, (uint32_t)n, overlaps);
+    });
+  });
+}
+
+// ---- oriented-box queries on device memory (include/ezrt_obb_overlap.h): one kernel each on `st`, no scratch (a box's list is kept in
+// its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
+int ezrt_query_obb_overlap_device(EzrtScene* s, const float* centre3, const float* axes9, int n, int max_k, int32_t* tri_id,
+                                  int32_t* n_overlap, void* stream) {
+  return ezi::guarded("ezrt_query_obb_overlap_device", [&]() -> int {
+    if (!s || !centre3 || !axes9 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 0 || max_k > EZRT_OBB_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_OBB_OVERLAP_MAX);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{centre3, N * 3 * sizeof(float)}, {axes9, N * 9 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
+                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      ObbOverlapArgs a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.centre = centre3;
+      a.axes = axes9;
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      // slot_walk's entries are bare references, one row each: half of the column that decides the route (stack_need_cp + 1 rows)
+      launch_routed(obb_overlap_kernel<true>, obb_overlap_kernel<false>, r, r.lds / 2, N, st, a);
+    });
+  });
+}
+int ezrt_obb_overlap_at_device(EzrtScene* s, const float* centre3, const float* axes9, const int32_t* tri_id, int n, uint8_t* overlaps,
+                               void* stream) {
+  return ezi::guarded("ezrt_obb_overlap_at_device", [&]() -> int {
+    if (!s || !centre3 || !axes9 || !tri_id || !overlaps || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{centre3, N * 3 * sizeof(float)}, {axes9, N * 9 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
+                      st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(obb_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, centre3, axes9, tri_id, (uint32_t)n, overlaps);
     });
   });
 }

@@ -1,7 +1,7 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
-include/ezrt_segment.h).
+include/ezrt_segment.h, include/ezrt_obb_overlap.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -28,6 +28,8 @@ include/ezrt_segment.h).
     tri, dist, point_query, point_scene, crosses = query.segment_distance(scene, segs, d_max)   # how close each segment comes to the mesh
     tri, dist, point_query, point_scene, crosses = query.segment_distance_at(scene, segs, tri)  # ... for pairs already held
     tri, n_overlap = query.capsule_overlap(scene, segs, radius, max_k=8)      # the triangles each capsule touches (include/ezrt_segment.h)
+    tri, n_overlap = query.obb_overlap(scene, centre, axes, max_k=8)          # the triangles each rotated box touches (include/ezrt_obb_overlap.h)
+    touches = query.obb_overlap_at(scene, centre, axes, tri)                  # ... the same test for pairs already held  (bool)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -44,6 +46,8 @@ need not have unit length and t is in units of it (the centre at time t is o + d
 miss is the point queries' (-1, +inf, zeros, False).
 `segs` is a contiguous float32 GPU tensor of shape [..., 6] that holds THE TWO END POINTS a, b of every segment -- not an origin and a
 direction, as every `rays` above does: the segment of a ray up to t is (o, o + d*t).
+`centre` is a contiguous float32 GPU tensor of shape [..., 3] and `axes` one of shape [..., 3, 3] whose rows are the three HALF-axis
+vectors u0 u1 u2 of the box c + s0 u0 + s1 u1 + s2 u2, |s_j| <= 1; they need not be unit or orthogonal.
 """
 import collections
 import ctypes as C
@@ -64,6 +68,7 @@ TriDistance = collections.namedtuple("TriDistance", "tri dist point_query point_
 SphereCast = collections.namedtuple("SphereCast", "tri t point touching")
 SegmentDistance = collections.namedtuple("SegmentDistance", "tri dist point_query point_scene crosses")
 CapsuleOverlap = collections.namedtuple("CapsuleOverlap", "tri n_overlap")
+ObbOverlap = collections.namedtuple("ObbOverlap", "tri n_overlap")
 
 
 def _scene_lib(scene, abi):
@@ -806,3 +811,71 @@ def capsule_overlap(scene, segs, radius, max_k=8, count=False, stream=None):
                                                        P(h)))
     _keep((segs, radius, tri, total), ts, segs)
     return CapsuleOverlap(tri, total)
+
+
+def _check_obbs(centre, axes):
+    """The number of oriented boxes, after the checks every such query makes of its centres and axes."""
+    _tensor("centre", centre, torch.float32, last=3)
+    _tensor("axes", axes, torch.float32)
+    if axes.device != centre.device:
+        raise ValueError("axes is on %s, not on %s" % (axes.device, centre.device))
+    if tuple(axes.shape) != tuple(centre.shape) + (3,):
+        raise ValueError("axes must have shape %s, not %s" % (tuple(centre.shape) + (3,), tuple(axes.shape)))
+    if not axes.is_contiguous():
+        raise ValueError("axes must be contiguous")
+    return _count(centre, 3, "boxes")
+
+
+def obb_overlap(scene, centre, axes, max_k=8, count=False, stream=None):
+    """ObbOverlap(tri int32 [..., max_k], n_overlap int32 [...] or None): for every oriented box -- `centre` [..., 3] and `axes`
+    [..., 3, 3] with the half-axis vectors u0 u1 u2 as rows, contiguous float32 GPU tensors; the box is c + s0 u0 + s1 u1 + s2 u2 with
+    |s_j| <= 1, and the vectors need not be unit or orthogonal (a sheared box is allowed) -- the triangles of the scene that touch it:
+    the exact separating-axis test of a closed triangle against a closed parallelepiped, so touching counts and a degenerate triangle
+    overlaps as the segment or point it is.  `tri` holds the lowest triangle indices in ascending order, then -1: a larger max_k
+    (0 .. 64) only appends, and the answer depends on neither the tree nor the order of the visits.  `count=True` also returns the
+    full number of overlapping triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count`
+    must be True).  A box with a non-finite number or without volume (a zero axis, parallel or coplanar axes: give a thin box
+    instead) overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
+    include/ezrt_obb_overlap.h; `obb_overlap_at` tests pairs."""
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.OBB_OVERLAP_MAX:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.OBB_OVERLAP_MAX, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    n = _check_obbs(centre, axes)
+    lib = _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
+    lead = tuple(centre.shape[:-1])
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=centre.device)
+    total = torch.empty(lead, dtype=torch.int32, device=centre.device) if count else None
+    if n == 0:
+        return ObbOverlap(tri, total)
+    h, ts = _stream(centre, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_obb_overlap_device(scene._h, P(centre.data_ptr()), P(axes.data_ptr()), n, max_k,
+                                                   P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
+    _keep((centre, axes, tri, total), ts, centre)
+    return ObbOverlap(tri, total)
+
+
+def obb_overlap_at(scene, centre, axes, tri, stream=None):
+    """bool tri.shape: whether triangle tri[...] touches its oriented box, by `obb_overlap`'s test.  `tri` (int32) has the shape
+    centre.shape[:-1], or one trailing dimension more -- the output of `obb_overlap` -- and every entry of a row then belongs to the
+    row's box.  An id that is no triangle of the scene (an unused slot, -1) gives False."""
+    _check_obbs(centre, axes)
+    lib = _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
+    lead = tuple(centre.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=centre.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    out = torch.empty(shape, dtype=torch.uint8, device=centre.device)
+    if n == 0:
+        return out.view(torch.bool)
+    h, ts = _stream(centre, stream)
+    flat = axes.reshape(lead + (9,))
+    per_c, per_u = _per_entry(centre, lead, shape, h, ts), _per_entry(flat, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_obb_overlap_at_device(scene._h, P(per_c.data_ptr()), P(per_u.data_ptr()), P(tri.data_ptr()), n,
+                                                P(out.data_ptr()), P(h)))
+    _keep((centre, axes, per_c, per_u, tri, out), ts, centre)
+    return out.view(torch.bool)
