@@ -278,6 +278,17 @@ OBB_OVERLAP_ABI = {
 OBB_OVERLAP_MAX = 64  # EZRT_OBB_OVERLAP_MAX
 
 
+# stream-ordered winding-number queries on device memory, libezrt_hip.so only (include/ezrt_winding.h); pointers are device addresses
+WINDING_ABI = {
+    # s, points3, n, chunks, fixed, winding, stream
+    "ezrt_query_winding_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, points3, tri_id, n, fixed, winding, stream
+    "ezrt_winding_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # n, n_tri: the slices of a call with chunks == 0
+    "ezrt_winding_chunks": (C.c_int, [C.c_int, C.c_int]),
+}
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -346,7 +357,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

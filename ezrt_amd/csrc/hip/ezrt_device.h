@@ -463,6 +463,72 @@ EZD bool inside_crossed(const float4* __restrict__ tg, const InsideFrame& f) {
   return __builtin_fabs(D) < __builtin_inf() && ((D < 0.0 && A > 0.0) || (D > 0.0 && A < 0.0));                 // G6
 }
 
+// ---- winding-number queries (include/ezrt_winding.h, where the definition is the contract): W1 of one triangle (winding_tri: the
+// vertices in the order of their values, converted to fp64, and sgn -- which depend on the triangle alone, so where the triangle is
+// uniform across a wave this is scalar work) and W2 .. W4 of one point against it (winding_term), in the header's order.
+struct WindingTri {
+  double v[9];  // v0 v1 v2
+  float sgn;    // +-1: the parity of the sort; 0: the triangle has no term (a non-finite coordinate, two vertices equal by value)
+};
+EZD void winding_tri(const float4* __restrict__ tg, WindingTri& w) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  float ax = ga.x, ay = ga.y, az = ga.z, bx = gb.x, by = gb.y, bz = gb.z, cx = gc.x, cy = gc.y, cz = gc.z;
+  const float inf = __builtin_inff();
+  const bool finite = ez_abs(ax) < inf && ez_abs(ay) < inf && ez_abs(az) < inf && ez_abs(bx) < inf && ez_abs(by) < inf &&
+                      ez_abs(bz) < inf && ez_abs(cx) < inf && ez_abs(cy) < inf && ez_abs(cz) < inf;
+  // the three compare-and-swaps as selects, and the parity of the swaps that happened
+  auto cswap = [](float& xx, float& xy, float& xz, float& yx, float& yy, float& yz) {
+    const bool sw = yx < xx || (yx == xx && (yy < xy || (yy == xy && yz < xz))); // less(y, x)
+    const float lx = sw ? yx : xx, ly = sw ? yy : xy, lz = sw ? yz : xz;
+    const float hx = sw ? xx : yx, hy = sw ? xy : yy, hz = sw ? xz : yz;
+    xx = lx, xy = ly, xz = lz, yx = hx, yy = hy, yz = hz;
+    return sw;
+  };
+  const bool s1 = cswap(ax, ay, az, bx, by, bz);
+  const bool s2 = cswap(bx, by, bz, cx, cy, cz);
+  const bool s3 = cswap(ax, ay, az, bx, by, bz);
+  const float sgn = ((s1 != s2) != s3) ? -1.0f : 1.0f;
+  const bool repeated = (ax == bx && ay == by && az == bz) || (bx == cx && by == cy && bz == cz);
+  w.v[0] = (double)ax, w.v[1] = (double)ay, w.v[2] = (double)az;
+  w.v[3] = (double)bx, w.v[4] = (double)by, w.v[5] = (double)bz;
+  w.v[6] = (double)cx, w.v[7] = (double)cy, w.v[8] = (double)cz;
+  w.sgn = (finite && !repeated) ? sgn : 0.0f;
+}
+// q_k of the FINITE point (px, py, pz) and a triangle with w.sgn != 0
+EZD long long winding_term(const WindingTri& w, double px, double py, double pz) {
+  const double ax = w.v[0] - px, ay = w.v[1] - py, az = w.v[2] - pz;
+  const double bx = w.v[3] - px, by = w.v[4] - py, bz = w.v[5] - pz;
+  const double cx = w.v[6] - px, cy = w.v[7] - py, cz = w.v[8] - pz;
+  const double nx = by * cz - bz * cy;
+  const double ny = bz * cx - bx * cz;
+  const double nz = bx * cy - by * cx;
+  const double det = (ax * nx + ay * ny) + az * nz;
+  const double la = __builtin_sqrt((ax * ax + ay * ay) + az * az);
+  const double lb = __builtin_sqrt((bx * bx + by * by) + bz * bz);
+  const double lc = __builtin_sqrt((cx * cx + cy * cy) + cz * cz);
+  const double ab = (ax * bx + ay * by) + az * bz;
+  const double bc = (bx * cx + by * cy) + bz * cz;
+  const double ca = (cx * ax + cy * ay) + cz * az;
+  const double den = (((la * lb) * lc + ab * lc) + bc * la) + ca * lb;
+  const double fdet = __builtin_fabs(det), fden = __builtin_fabs(den), dinf = __builtin_inf();
+  if (!(det != 0.0 && fdet < dinf && fden < dinf)) return 0;                                                      // W3
+  const double m = fdet < fden ? fden : fdet;
+  if (m == 0.0) return 0;
+  const float t = w.sgn * ez_atan2((float)(det / m), (float)(den / m));
+  return (long long)__builtin_rint((double)t * 0x1p36);                                                           // W4
+}
+// W5's conversion of the sum
+EZD float winding_of(long long S) { return (float)(((double)S * 0x1p-36) * 0x1.45f306dc9c883p-3); }
+// the single term of a pair, for ezrt_winding_at_device
+EZD long long winding_pair(const float4* __restrict__ tg, f3 p) {
+  const float inf = __builtin_inff();
+  if (!(ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf)) return 0;
+  WindingTri w;
+  winding_tri(tg, w);
+  if (w.sgn == 0.0f) return 0;
+  return winding_term(w, (double)p.x, (double)p.y, (double)p.z);
+}
+
 // ---- box-overlap queries (include/ezrt_box_overlap.h, where the definition is the contract): H1 .. H3 of one triangle against a
 // LIVE box (the caller has checked the box), in the header's order.  An edge axis has a[j] = 0: its term a[j] * d is a zero (d is
 // finite), and adding a zero changes at most the sign of a zero sum, which no comparison sees -- so those terms are left out and

@@ -1,9 +1,9 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
-// self-overlap, triangle-distance, sphere-cast, segment and oriented-box queries (include/ezrt_box_overlap.h, include/ezrt_tri_overlap.h,
-// include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h,
-// include/ezrt_obb_overlap.h).  One query point, box, triangle, ray or segment per lane, a workgroup of one wave.  Included by
-// ezrt_queries.hip alone.
+// self-overlap, triangle-distance, sphere-cast, segment, oriented-box and winding-number queries (include/ezrt_box_overlap.h,
+// include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h,
+// include/ezrt_obb_overlap.h, include/ezrt_winding.h).  One query point, box, triangle, ray or segment per lane, a workgroup of one wave.
+// Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -31,6 +31,9 @@
 //   capsule_overlap_kernel<WALK>     collect_rows over point_walk with the constant radius R2 and segment_pair's dist2 <= R2 as the rule
 //   obb_overlap_kernel<WALK>         collect_rows over slot_walk with the hull and the face directions as the gates and obb_overlaps as the rule
 //   obb_overlap_at_kernel            obb_overlaps for pairs the caller holds
+//   winding_kernel<ATOMIC, TILE>     no walk: every lane sums winding_term over a slice of the triangles (include/ezrt_winding.h)
+//   winding_finish_kernel            the int64 sums of a sliced call to float
+//   winding_at_kernel                winding_pair for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -1020,6 +1023,94 @@ __global__ __launch_bounds__(256) void obb_overlap_at_kernel(const float4* tri_g
   bool o = false;
   if ((uint32_t)tri < (uint32_t)n_tri && obb_load(centre, axes, i, q)) o = obb_overlaps(tri_geom + (size_t)tri * 3, q);
   overlaps[i] = o ? 1u : 0u;
+}
+
+// ---- winding-number queries (include/ezrt_winding.h).
+//
+// winding_kernel<ATOMIC, TILE>: one point per lane, a workgroup of one wave; the grid is (point blocks) x (slices of the triangle
+// range), and every lane of a workgroup loops over the same slice [blockIdx.y * per_slice, ...) and keeps its sum S in a 64-bit
+// register pair.  An exact sum has nothing to prune: no tree is read, only tri_geom, and there is no stack.  ATOMIC = false, one
+// slice: S is stored to fixed and, where asked for, converted to winding.  ATOMIC = true: the host zeroed fixed on the stream, every
+// workgroup adds its partial sum with a 64-bit integer atomicAdd (an integer sum: the order costs no bit), and
+// winding_finish_kernel converts afterwards.
+// Reading the triangles.  TILE = true (the default): each lane sorts ONE triangle of a tile of WN_BLOCK (W1: winding_tri) and writes
+// its WindingTri to LDS; the wave then reads the tile entry by entry at one address for all lanes, a broadcast without bank
+// conflicts -- W1 costs each pair 1/64 of a lane's evaluation.  TILE = false, the alternative kept for measuring
+// (EZRT_WINDING_SCALAR=1, read once per process): the triangle index is the loop counter, bounded by kernel arguments -- uniform
+// across the wave, so the 48-byte record is read with scalar loads (s_load_dwordx8 + x4) into SGPRs; but gfx950 has no scalar
+// floating-point compare or convert, so W1 is then evaluated by every wave for every triangle in the vector unit on uniform values,
+// which costs about a quarter of the pair's time (profiles/r23/winding_rates.txt).  Both evaluate winding_tri and winding_term
+// (ezrt_device.h) and give the same bits.
+constexpr int WN_BLOCK = 64;
+struct WindingArgs {
+  const float4* tri_geom;
+  int32_t n_tri;
+  int32_t per_slice;        // triangles per slice: ceil(n_tri / slices)
+  const float* points;      // n x 3
+  uint32_t n;
+  long long* fixed;         // n
+  float* winding;           // n, or null (ATOMIC: written by winding_finish_kernel)
+};
+template <bool ATOMIC, bool TILE>
+__global__ __launch_bounds__(WN_BLOCK) void winding_kernel(WindingArgs a) {
+  const uint32_t i = blockIdx.x * WN_BLOCK + threadIdx.x;
+  const int32_t k0 = (int32_t)blockIdx.y * a.per_slice;
+  const int32_t k1 = a.n_tri - k0 < a.per_slice ? a.n_tri : k0 + a.per_slice;
+  const float inf = __builtin_inff();
+  f3 p = mk(0.0f, 0.0f, 0.0f);
+  if (i < a.n) p = ld3(a.points + (size_t)i * 3);
+  const bool live = i < a.n && ez_abs(p.x) < inf && ez_abs(p.y) < inf && ez_abs(p.z) < inf; // a non-finite p: S = 0
+  const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+  long long S = 0;
+  if (TILE) {
+    __shared__ WindingTri tile[WN_BLOCK];
+#pragma unroll 1
+    for (int32_t base = k0; base < k1; base += WN_BLOCK) {
+      const int32_t k = base + (int32_t)threadIdx.x;
+      if (k < k1) winding_tri(a.tri_geom + (size_t)k * 3, tile[threadIdx.x]);
+      __syncthreads();
+      const int32_t m = k1 - base < WN_BLOCK ? k1 - base : WN_BLOCK;
+      if (live) {
+#pragma unroll 1
+        for (int32_t j = 0; j < m; j++) {
+          const WindingTri w = tile[j];
+          if (w.sgn != 0.0f) S += winding_term(w, px, py, pz);
+        }
+      }
+      __syncthreads();
+    }
+  } else if (live) {
+#pragma unroll 1
+    for (int32_t k = k0; k < k1; k++) {
+      WindingTri w;
+      winding_tri(a.tri_geom + (size_t)k * 3, w);
+      if (w.sgn != 0.0f) S += winding_term(w, px, py, pz);
+    }
+  }
+  if (i >= a.n) return;
+  if (ATOMIC) {
+    if (S != 0) atomicAdd((unsigned long long*)(a.fixed + i), (unsigned long long)S); // two's complement: the signed sum
+  } else {
+    a.fixed[i] = S;
+    if (a.winding) a.winding[i] = winding_of(S);
+  }
+}
+__global__ __launch_bounds__(256) void winding_finish_kernel(const long long* fixed, uint32_t n, float* winding) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) winding[i] = winding_of(fixed[i]);
+}
+
+// ezrt_winding_at_device: winding_pair for pairs the caller holds -- point i against triangle tri_id[i].  An id outside the scene
+// writes 0.
+__global__ __launch_bounds__(256) void winding_at_kernel(const float4* tri_geom, int32_t n_tri, const float* points, const int32_t* tri_id,
+                                                         uint32_t n, long long* fixed, float* winding) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  long long q = 0;
+  if ((uint32_t)tri < (uint32_t)n_tri) q = winding_pair(tri_geom + (size_t)tri * 3, ld3(points + (size_t)i * 3));
+  fixed[i] = q;
+  if (winding) winding[i] = winding_of(q);
 }
 
 } // namespace ezd

@@ -1,8 +1,9 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
-// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment and
-// oriented-box queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h, ezrt_tri_overlap.h,
-// ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h).  A translation unit of its own: none
+// nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
+// oriented-box and winding-number queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
+// ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h;
+// the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
 // ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
@@ -20,6 +21,7 @@
 #include "ezrt_sphere_cast.h"
 #include "ezrt_segment.h"
 #include "ezrt_obb_overlap.h"
+#include "ezrt_winding.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -443,6 +445,81 @@ int ezrt_obb_overlap_at_device(EzrtScene* s, const float* centre3, const float* 
     return query_call(s, {{centre3, N * 3 * sizeof(float)}, {axes9, N * 9 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {overlaps, N}}, N,
                       st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(obb_overlap_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, centre3, axes9, tri_id, (uint32_t)n, overlaps);
+    });
+  });
+}
+
+// ---- winding-number queries on device memory (include/ezrt_winding.h): no scratch (`fixed` is the caller's accumulator); checked,
+// launched and ordered against a refit by query_call.  No tree is read, so there is no route.
+//
+// The slices of a call with chunks == 0 -- a pure function of n and n_tri.  A workgroup is one wave of WN_BLOCK points; an MI355X
+// has 256 CUs of 4 SIMDs, and WN_FILL = 8192 waves is eight per SIMD, what the kernel's registers allow: the pair function is a long
+// dependent chain of fp64 operations (three square roots, two divisions), and the measured rate still rises from 2 to 8 waves per SIMD
+// (DESIGN.md has the figures).  Where the points alone give that many, one slice (no zeroing, no atomics, no finishing kernel);
+// otherwise enough slices to reach it, but none shorter than WN_MIN_SLICE triangles, below which the per-workgroup cost (the point,
+// the atomic) is no longer small beside the slice.
+constexpr int WN_FILL = 8192, WN_MIN_SLICE = 256, WN_MAX_SLICES = 65535; // (65535: the y extent of a grid)
+int ezrt_winding_chunks(int n, int n_tri) {
+  if (n <= 0 || n_tri <= 0) return 1;
+  const long long blocks = ((long long)n + WN_BLOCK - 1) / WN_BLOCK;
+  if (blocks >= WN_FILL) return 1;
+  const long long want = (WN_FILL + blocks - 1) / blocks, most = n_tri / WN_MIN_SLICE;
+  const long long c = want < most ? want : most;
+  return (int)(c < 1 ? 1 : c);
+}
+int ezrt_query_winding_device(EzrtScene* s, const float* points3, int n, int chunks, int64_t* fixed, float* winding, void* stream) {
+  return ezi::guarded("ezrt_query_winding_device", [&]() -> int {
+    if (!s || !points3 || !fixed || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (chunks < 0) return fail(EZRT_ERR_INVALID, "chunks < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    static const bool tile = [] { // the triangles through an LDS tile (the default: the faster) or by scalar loads (kept for measuring)
+      const char* e = getenv("EZRT_WINDING_SCALAR");
+      return !(e && e[0] == '1');
+    }();
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {fixed, N * sizeof(int64_t)}, {winding, N * sizeof(float)}}, N, st,
+                      [&](dim3, dim3) -> int {
+      const int n_tri = (int)s->n_tri;
+      int c = chunks == 0 ? ezrt_winding_chunks(n, n_tri) : chunks;
+      if (c > n_tri) c = n_tri;
+      if (c > WN_MAX_SLICES) c = WN_MAX_SLICES;
+      if (c < 1) c = 1;
+      WindingArgs a;
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = n_tri;
+      a.per_slice = (n_tri + c - 1) / c;
+      if (a.per_slice > 0) c = (n_tri + a.per_slice - 1) / a.per_slice; // no empty slice
+      a.points = points3;
+      a.n = (uint32_t)n;
+      a.fixed = (long long*)fixed;
+      a.winding = winding;
+      const dim3 g((unsigned)((N + WN_BLOCK - 1) / WN_BLOCK), (unsigned)c), b(WN_BLOCK);
+      if (c == 1) {
+        if (tile) hipLaunchKernelGGL((winding_kernel<false, true>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((winding_kernel<false, false>), g, b, 0, st, a);
+        return 0;
+      }
+      HIP_TRY(hipMemsetAsync(fixed, 0, N * sizeof(int64_t), st));
+      if (tile) hipLaunchKernelGGL((winding_kernel<true, true>), g, b, 0, st, a);
+      else hipLaunchKernelGGL((winding_kernel<true, false>), g, b, 0, st, a);
+      if (winding)
+        hipLaunchKernelGGL(winding_finish_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const long long*)fixed, (uint32_t)n,
+                           winding);
+      return 0;
+    });
+  });
+}
+int ezrt_winding_at_device(EzrtScene* s, const float* points3, const int32_t* tri_id, int n, int64_t* fixed, float* winding, void* stream) {
+  return ezi::guarded("ezrt_winding_at_device", [&]() -> int {
+    if (!s || !points3 || !tri_id || !fixed || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{points3, N * 3 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {fixed, N * sizeof(int64_t)},
+                          {winding, N * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(winding_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, (long long*)fixed,
+                         winding);
     });
   });
 }

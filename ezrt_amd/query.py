@@ -1,7 +1,7 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
-include/ezrt_segment.h, include/ezrt_obb_overlap.h).
+include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -30,6 +30,9 @@ include/ezrt_segment.h, include/ezrt_obb_overlap.h).
     tri, n_overlap = query.capsule_overlap(scene, segs, radius, max_k=8)      # the triangles each capsule touches (include/ezrt_segment.h)
     tri, n_overlap = query.obb_overlap(scene, centre, axes, max_k=8)          # the triangles each rotated box touches (include/ezrt_obb_overlap.h)
     touches = query.obb_overlap_at(scene, centre, axes, tri)                  # ... the same test for pairs already held  (bool)
+    w = query.winding_number(scene, points)                                   # how often the mesh wraps each point: 1 inside, 0 outside
+    w, fixed = query.winding_number(scene, points, fixed=True)                # ... and the exact int64 sum behind it (include/ezrt_winding.h)
+    w, fixed = query.winding_number_at(scene, points, tri)                    # ... the term of single triangles, for pairs already held
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -375,8 +378,8 @@ def inside(scene, points, axis=0, crossings=False, stream=None):
     number of triangles crossed by the ray that leaves the point along `axis` (0..5: +x, -x, +y, -y, +z, -z), by a rule that is
     consistent on shared edges and vertices and independent of the tree, of the order of the triangles and of their windings.
     `crossings=True` returns (inside, crossings int32 [...]).  A point with a non-finite coordinate crosses nothing.  On an open mesh
-    the answer is still that parity and may differ between axes: vote over several.  The definition, on the bits:
-    include/ezrt_inside.h."""
+    the answer is still that parity and may differ between axes: vote over several -- or use `winding_number(...) > 0.5` (`abs(...)`
+    for a mesh that faces inwards), the robust test on open meshes.  The definition, on the bits: include/ezrt_inside.h."""
     _check_axis(axis)
     n = _check_points(points, None)
     lib = _scene_lib(scene, _abi.INSIDE_ABI)
@@ -879,3 +882,60 @@ def obb_overlap_at(scene, centre, axes, tri, stream=None):
                                                 P(out.data_ptr()), P(h)))
     _keep((centre, axes, per_c, per_u, tri, out), ts, centre)
     return out.view(torch.bool)
+
+
+def _check_chunks(chunks):
+    if chunks is None:
+        return 0
+    if not isinstance(chunks, int) or isinstance(chunks, bool) or chunks < 1:
+        raise ValueError("chunks must be None or an int >= 1, not %r" % (chunks,))
+    return min(chunks, 2**31 - 1)
+
+
+def winding_number(scene, points, fixed=False, chunks=None, stream=None):
+    """float32 [...]: the generalised winding number of the mesh at each point of `points` (a contiguous float32 GPU tensor [..., 3])
+    -- the solid angles of all triangles summed and divided by 4 pi: 1 inside and 0 outside a closed mesh that faces outwards (-1
+    inside one that faces inwards), and a smooth value across a hole, a doubled sheet or a self-crossing, where `inside`'s parity
+    differs between axes: `winding_number(...) > 0.5` (`abs(...)` for inward-facing meshes) is the robust inside test on open
+    meshes.  `fixed=True` returns (winding, fixed int64 [...]): the sum in units of 2^-36 rad of half solid angle, an INTEGER sum and
+    so independent of the order of the triangles, the tree and the split of the work, on the bits; `fixed` of mesh parts (or of one
+    mesh split over devices) may be added, and a flipped triangle negates its term exactly.  A point in the plane of a triangle gets
+    nothing from it; a point with a non-finite coordinate has 0.  Every triangle is summed for every point (no tree is read):
+    `chunks=None` lets the library split the triangle range over workgroups where the points alone do not fill the device,
+    `chunks=k` forces k slices -- the answer is the same.  The definition, on the bits: include/ezrt_winding.h."""
+    c = _check_chunks(chunks)
+    n = _check_points(points, None)
+    lib = _scene_lib(scene, _abi.WINDING_ABI)
+    lead = tuple(points.shape[:-1])
+    acc = torch.empty(lead, dtype=torch.int64, device=points.device)    # the call's accumulator, allocated whether returned or not
+    out = torch.empty(lead, dtype=torch.float32, device=points.device)
+    if n > 0:
+        h, ts = _stream(points, stream)
+        P = C.c_void_p
+        _call(scene, lib.ezrt_query_winding_device(scene._h, P(points.data_ptr()), n, c, P(acc.data_ptr()), P(out.data_ptr()), P(h)))
+        _keep((points, acc, out), ts, points)
+    return (out, acc) if fixed else out
+
+
+def winding_number_at(scene, points, tri, stream=None):
+    """(winding float32 tri.shape, fixed int64 tri.shape): the term of triangle tri[...] alone in `winding_number` of its point.  `tri`
+    (int32) has the shape points.shape[:-1], or one trailing dimension more, and every entry of a row then belongs to the row's
+    point.  An id that is no triangle of the scene (an unused slot, -1) gives 0.  The sum of `fixed` over all triangles of the scene
+    is `winding_number`'s."""
+    _check_points(points, None)
+    lib = _scene_lib(scene, _abi.WINDING_ABI)
+    lead = tuple(points.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=points.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    acc = torch.empty(shape, dtype=torch.int64, device=points.device)
+    out = torch.empty(shape, dtype=torch.float32, device=points.device)
+    if n == 0:
+        return out, acc
+    h, ts = _stream(points, stream)
+    per_entry = _per_entry(points, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_winding_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(acc.data_ptr()), P(out.data_ptr()),
+                                            P(h)))
+    _keep((points, per_entry, tri, acc, out), ts, points)
+    return out, acc
