@@ -223,9 +223,13 @@ struct Tuning {
   int prune_mis = 2;       // ... of the MIS integrators' bounce stages (two rays per path, one an env shadow ray) when prune == 2:
                            // slot order there (1) was a wash on C4 (14.36 vs 14.28 Grays/s) and lost 6 % on C5 (2.46 vs 2.61)
   int prune_min_records = 0; // scenes with fewer 4-wide records than this are traced unpruned (small trees gain nothing)
-  int stack_cap = 0;       // prune 2: LDS stack rows of the nearest-first traversal before a ray is handed to the redo list (0: the exact
-                           // worst case of the slot-order traversal).  Fewer rows = more top-of-tree records staged in LDS
-  int debug_stack_cap = 0; // test hook (prune 2): > 0 = stack rows beyond which a ray goes to the redo list, instead of the scene's bound
+  int stack_cap = 0;       // prune 2: rows of the LDS RING that holds the newest entries of the nearest-first traversal's stack (stack_cap4): 0 =
+                           // 16 rows; another value is rounded down to a power of two, at least 4 and at most 32.  Older entries move to the
+                           // lane's spill area in global memory (16 entries, OVF_CAP); a ray that fills both goes to the redo list.  Fewer
+                           // rows = more top-of-tree records staged in LDS.  (prune 0 / 1 run on the exact bound of the slot order instead)
+  int debug_stack_cap = 0; // test hook (prune 2), 0..8: n > 0 = a ring of 4 rows and a spill area of 4 (n - 1) entries per lane (ovf_cap4),
+                           // whatever stack_cap says: 1 sends every ray that needs a fifth row to the redo list, 5 has the production spill
+                           // area of 16 entries, 8 -- 4 + 28 -- the production depth of 32 with almost all of it spilled
   int bounce_scatter = 1;  // the bounce stages' trace launches draw their queue in a scattered order, in granules of 8 rays
                            // (TraceQ4Args::gscat_shift; 0: consecutive slots, the order the shading stage wrote; 1: queues with one
                            // ray per path.  The MIS integrators' two-ray queues lost 1.3-2.8 % with it: never scattered)
@@ -285,7 +289,7 @@ const TuningName kTuning[] = {{"megakernel", &Tuning::megakernel, 0, 1},
                               {"prune_mis", &Tuning::prune_mis, 0, 2},
                               {"prune_min_records", &Tuning::prune_min_records, 0, 1 << 24},
                               {"stack_cap", &Tuning::stack_cap, 0, 64},
-                              {"debug_stack_cap", &Tuning::debug_stack_cap, 0, 64},
+                              {"debug_stack_cap", &Tuning::debug_stack_cap, 0, 8},
                               {"bounce_scatter", &Tuning::bounce_scatter, 0, 1},
                               {"pipeline_calls", &Tuning::pipeline_calls, 0, 2},
                               {"static_pct_pipelined", &Tuning::static_pct_pipelined, 0, 95},
@@ -321,7 +325,7 @@ struct Pipe {
   DevBuf<uint32_t> qcounts; // [0..63] path counts per stage, [64..99] trace queue heads, [100..115] debug,
                             // [120] redo count, [121] redo queue head
   DevBuf<uint32_t> redo_slots;
-  DevBuf<uint32_t> ovf;         // traceq4_kernel's spill area of the LDS traversal stacks: [launch lanes][OVF_CAP] (TraceQ4Args::stack_cap)
+  DevBuf<uint32_t> ovf;         // traceq4_kernel's spill area of the LDS traversal stacks: [launch lanes][max(OVF_CAP, ovf_cap4)] (TraceQ4Args::stack_cap)
   DevBuf<uint32_t> qheads;      // traceq reservation counters: [launch slot][TRACE_HEADS][TRACE_HEAD_STRIDE] (QHEADS_WORDS in all; zeroed per chunk)
   DevBuf<float4> inner_rel;     // inner records translated by -eye (primary rays)
   DevBuf<float4> inner4_rel;    // 4-wide records translated by -eye

@@ -254,7 +254,7 @@ constexpr size_t QHEADS_WORDS = 81 * QHEAD_SLOT_WORDS; // launch slots of reserv
 // t: the stage's queue arguments as for the binary kernel (knobs already filled); rel: 4-wide records translated by
 // t.origin (or NULL)
 // gen (or NULL): the chunk's stage-0 arguments when the launch generates its primary rays itself (needs rel)
-// ovf: the scratch set's spill area of the traversal stacks (Pipe::ovf: [grid lanes][OVF_CAP])
+// ovf: the scratch set's spill area of the traversal stacks (Pipe::ovf: [grid lanes][max(OVF_CAP, ovf_cap4(s))], indexed with a stride of ovf_cap4(s))
 void fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, const WfArgs* gen, uint32_t* ovf, TraceQ4Args& A) {
   memset(&A.gen_p, 0, sizeof A.gen_p);
   A.gen_blocks = nullptr;
@@ -441,7 +441,8 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
     int rc_cu = ensure_num_cus(s);
     if (rc_cu) return rc_cu;
   }
-  HIP_TRY(pp.ovf.ensure((size_t)s->num_cus * 8 * BLOCK * OVF_CAP)); // (spill area of the traversal stacks: at most 8 workgroups per CU)
+  // (spill area of the traversal stacks: at most 8 workgroups per CU, and per lane the larger of the production cap and the test hook's)
+  HIP_TRY(pp.ovf.ensure((size_t)s->num_cus * 8 * BLOCK * (size_t)std::max(OVF_CAP, ovf_cap4(s))));
   auto queue = [&](int k) {
     RayQueue q;
     q.o = pp.rq_o[k].p;
@@ -1043,7 +1044,7 @@ static int ezrt_query_hits_body(EzrtScene* s, const float* rays, int n_rays, int
     t.wave_log = nullptr;
     HIP_TRY(hipEventRecord(s->ev_trace[0][0], nullptr));
     if (wide) {
-      HIP_TRY(pp.ovf.ensure((size_t)s->num_cus * 8 * BLOCK * OVF_CAP));
+      HIP_TRY(pp.ovf.ensure((size_t)s->num_cus * 8 * BLOCK * (size_t)std::max(OVF_CAP, ovf_cap4(s))));
       launch_traceq4_cfg(s, trace_cfg4(s, rel4 != nullptr), t, rel4, nullptr, nullptr, pp.ovf.p);
     }
     else launch_traceq_cfg(s, cfg, t, false, nullptr);

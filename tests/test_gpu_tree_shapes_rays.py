@@ -34,10 +34,8 @@ PRUNE_CASES = [(n, r) for n, r in CASES if n in WALKS or n == "leaf_misses"]
 STACK_CAP_CASES = [(n, r) for n, r in CASES if n in ("chain", "median1")]
 RADIANCE_CASES = [(n, r) for n, r in CASES if n in ("chain", "median1", "leaf128", "root_leaf_8", "two_leaves") and (n == "chain" or r != 0)]
 REFIT_CASES = [("median1", 0), ("median1", 1), ("chain", 0)]
-# (eye, target) of the camera that looks at the shape: at least a fifth of the 40 x 24 paths hit it and some reach the last bounce
-CAMERAS = dict(chain=((3.5, 5.67, 6.67), (6.5, 3.67, 3.67)), median1=((10.67, 6.67, 9.67), (6.67, 3.67, 3.67)),
-               leaf128=((10.67, 6.67, 9.67), (6.67, 3.67, 3.67)), root_leaf_8=((1.78, 4.67, 2.38), (1.67, 5.0, 2.33)),
-               two_leaves=((1.78, 4.67, 2.38), (1.67, 5.0, 2.33)))
+# (tree_shapes.CAMERAS: the camera that looks at the shape -- at least a fifth of the 40 x 24 paths hit it and some reach the last bounce)
+CAMERAS, _look_at = T.CAMERAS, T._look_at
 W, H, BOUNCES, FRAMES = 40, 24, 3, (0, 7)
 STEP = np.float32([0.25, -0.5, 0.25])
 
@@ -211,17 +209,6 @@ def test_a_tiny_stack_hands_the_rays_to_the_redo_launch(hip, oracle, dev, name, 
         sg.set_option("debug_stack_cap", cap)
         assert sg.prune_info()["mode"] == 2
         _check(closest_answers(sg, r, X, dev), _closest_names(X), "%s debug_stack_cap=%d" % (name, cap))
-
-
-def _look_at(eye, target):
-    """(eye, cameraRotate) of a camera at `eye` that looks at `target`: the columns of the rotation are right, up and back"""
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    f = (target - eye) / np.linalg.norm(target - eye)
-    right = np.cross(f, [0.0, 1.0, 0.0])
-    right /= np.linalg.norm(right)
-    m = np.eye(4)
-    m[:3, 0], m[:3, 1], m[:3, 2] = right, np.cross(right, f), -f
-    return eye.astype(np.float32), m.T.ravel().astype(np.float32)
 
 
 _audits = {}

@@ -295,3 +295,129 @@ def test_the_chain_rays_leave_entries_pending_on_the_callers_nodes(oracle):
     print("chain: deepest pending count %d from the deep end, %d from the shallow end; %d rays at 40 or more"
           % (depth["deep"].max(), depth["shallow"].max(), (both >= 40).sum()))
     assert (both >= 40).sum() >= 16 and both.max() <= expect["depth"] - 1
+
+
+# ---- the frames of tests/test_gpu_tree_shapes_frames.py: conditions on the inputs, on the CPU oracle alone -- the small frame (64 x 48,
+# 4 spp, 3 bounces, synthetic_hdr(64, 32) with its cache, integrators 50 and 51) hits the shape and reaches the last bounce, holds no NaN,
+# shows which of two byte-identical triangles won, shows that the uncovered triangles are never seen, and does not depend on the tree
+# where the leaves hold the same triangles.  These are conditions, not measurements of the code under test.
+
+FRAME_INTEGRATORS = (50, 51)
+TINY = ("root_leaf_1", "root_leaf_8", "two_leaves")
+WITH_COPIES = [n for n in T.HOST_SHAPES if n not in TINY]
+_frames = {}
+
+
+def _oracle_scene(oracle, arrays):
+    so = oracle.scene_create(*arrays)
+    so.set_env(*T.frame_env())
+    return so
+
+
+def _frame(oracle, key, arrays, name, integ):
+    """the oracle's small frame of `arrays` with the camera of `name`, rendered once"""
+    if (key, name, integ) not in _frames:
+        _frames[(key, name, integ)] = _oracle_scene(oracle, arrays).render(T.frame_params(name, integ))
+    return _frames[(key, name, integ)]
+
+
+def test_a_copy_never_carries_its_originals_material():
+    for name in T.HOST_SHAPES:
+        tri, nodes = T.coloured(name)
+        plain = T.shape(name)[0]
+        assert np.array_equal(tri[:, :18], plain[:, :18]) and nodes is T.shape(name)[1] and not tri.flags.writeable
+        pairs = T.copy_pairs(tri)
+        assert pairs.shape[0] == (0 if name in TINY else 24 if name == "chain" else T.N_DUPLICATES), name
+        assert (tri[pairs[:, 0], 18:36] != tri[pairs[:, 1], 18:36]).any(1).all(), name      # the point of the function
+        sw = T.swapped(name)[0]
+        assert np.array_equal(sw[pairs[:, 0], 18:36], tri[pairs[:, 1], 18:36]) and np.array_equal(sw[pairs[:, 1], 18:36], tri[pairs[:, 0], 18:36])
+        rest = np.setdiff1d(np.arange(tri.shape[0]), pairs)
+        assert np.array_equal(sw[rest], tri[rest]) and np.array_equal(sw[:, :18], tri[:, :18])
+        if tri.shape[0] > 8:
+            base_colour = np.unique(tri[:, 21:24], axis=0).shape[0]
+            varied = (tri[:, 24:36] != plain[:, 24:36]).any(1).mean()                          # roughness, metallic, specular, clearcoat, anisotropy
+            lights = (tri[:, 18:21] > 0).any(1).mean()
+            print("%s: %d base colours of %d triangles, %.3f with varied lobes, %.3f emissive" % (name, base_colour, tri.shape[0], varied, lights))
+            assert base_colour == tri.shape[0] and 0.15 <= varied <= 0.35 and 1 / 32 <= lights <= 1 / 8
+    assert set(T.CAMERAS) == set(T.HOST_SHAPES + T.LBVH_SHAPES)
+
+
+@pytest.mark.parametrize("name", T.HOST_SHAPES)
+def test_the_frames_hit_the_shape_reach_the_last_bounce_and_hold_no_nan(oracle, name):
+    so = _oracle_scene(oracle, T.coloured(name))
+    for integ in FRAME_INTEGRATORS:
+        hit, last = [], []
+        for frame in range(T.FRAME_SPP):                               # the samples of the small frame, one audit each
+            ids = so.render_paths(T.frame_params(name, integ, spp=1, frame0=frame), want_colour=False)[0]
+            ids = ids.reshape(T.FRAME_W * T.FRAME_H, -1)
+            hit.append((ids[:, 0] >= 0).mean())
+            last.append(int((ids[:, -1] >= -1).sum()))                 # (-2: the slot was never traced)
+        print("%s, integrator %d: primary rays that hit %.2f .. %.2f, paths at the last bounce %d .. %d of %d"
+              % (name, integ, min(hit), max(hit), min(last), max(last), T.FRAME_W * T.FRAME_H))
+        if name == "root_leaf_1":
+            assert min(hit) > 0.05
+        else:
+            assert min(hit) >= 0.7 and min(last) >= (20 if name in TINY else 100)
+        f = _frame(oracle, "coloured", T.coloured(name), name, integ)
+        assert not np.isnan(f).any() and float(f[..., :3].max()) > 0.1
+
+
+@pytest.mark.parametrize("name", WITH_COPIES)
+def test_the_tie_winner_shows_in_the_frame(oracle, name):
+    """coloured against swapped: the two frames differ only where a path met an original or its copy -- a renderer that lets the
+    wrong one of the two win draws the swapped frame."""
+    for integ in FRAME_INTEGRATORS:
+        a = _frame(oracle, "coloured", T.coloured(name), name, integ)
+        b = _frame(oracle, "swapped", T.swapped(name), name, integ)
+        differ = int((~T.same_pixels(a, b)).sum())
+        print("%s, integrator %d: %d of %d pixels (%.1f %%) depend on the winner of a tie" % (name, integ, differ, a.shape[0] * a.shape[1],
+                                                                                          100.0 * differ / (a.shape[0] * a.shape[1])))
+        assert differ >= 0.02 * a.shape[0] * a.shape[1]
+
+
+def test_the_uncovered_triangles_show_in_the_frame(oracle):
+    """Uniform materials (the two arrays order the triangles differently): the frame of `uncovered` against the same triangles under
+    a tree that covers all of them."""
+    tri, nodes = T.covered_again()
+    assert T.check_valid(tri, nodes)["uncovered"].size == 0
+    key = lambda a: sorted(a[k].tobytes() for k in range(a.shape[0]))  # noqa: E731
+    assert key(tri) == key(T.shape("uncovered")[0])
+    for integ in FRAME_INTEGRATORS:
+        a = _frame(oracle, "plain", T.shape("uncovered")[:2], "uncovered", integ)
+        b = _frame(oracle, "covered_again", (tri, nodes), "uncovered", integ)
+        differ = int((~T.same_pixels(a, b)).sum())
+        print("uncovered, integrator %d: %d of %d pixels (%.1f %%) differ from the frame of a tree that covers every triangle"
+              % (integ, differ, a.shape[0] * a.shape[1], 100.0 * differ / (a.shape[0] * a.shape[1])))
+        assert differ >= 0.03 * a.shape[0] * a.shape[1]
+
+
+def test_the_tree_alone_changes_no_pixel(oracle):
+    """Uniform materials: loose boxes, a leaf box that misses a vertex and leaves of one triangle hold the triangles that sah8's
+    leaves hold -- the frames are sah8's on the bits (a tie's two partners carry one material here)."""
+    for integ in FRAME_INTEGRATORS:
+        want = _frame(oracle, "plain", T.shape("sah8")[:2], "sah8", integ)
+        for name in ("loose", "leaf_misses", "median1"):
+            assert T.CAMERAS[name] == T.CAMERAS["sah8"]
+            differ = int((~T.same_pixels(_frame(oracle, "plain", T.shape(name)[:2], name, integ), want)).sum())
+            print("%s, integrator %d: %d pixels differ from sah8's frame" % (name, integ, differ))
+            assert differ == 0
+
+
+@pytest.mark.parametrize("name", ["median1", "leaf128", "chain"])
+def test_the_frames_meet_ties_whose_partners_lie_in_different_leaves(oracle, name):
+    """Where a leaf parts an original from its copy, "the lower index wins" is no rule: the audited frames (integrators 50 and 51, frames
+    0 and 7) have ray slots that go to the copy -- the higher index -- of such a pair, and slots that go to the original."""
+    tri, nodes = T.coloured(name)
+    leaf = _leaf_of(nodes, tri.shape[0])
+    pairs = T.copy_pairs(tri)
+    across = pairs[leaf[pairs[:, 0]] != leaf[pairs[:, 1]]]
+    so = _oracle_scene(oracle, (tri, nodes))
+    to_copy = to_original = 0
+    for integ in FRAME_INTEGRATORS:
+        for frame in (0, 7):
+            ids = so.render_paths(T.frame_params(name, integ, spp=1, frame0=frame), want_colour=False)[0]
+            to_copy += int(np.isin(ids, across[:, 1]).sum())
+            to_original += int(np.isin(ids, across[:, 0]).sum())
+    print("%s: %d of %d pairs lie across leaves; %d ray slots of the audited frames go to their copies, %d to their originals"
+          % (name, across.shape[0], pairs.shape[0], to_copy, to_original))
+    assert across.shape[0] >= 3 and to_copy >= 20 and to_original >= 20

@@ -697,3 +697,114 @@ def ray_expected(oracle, name):
         X["surface%d.point" % form], X["surface%d.normal" % form], X["surface%d.inside" % form] = RS.restate(tri, rays, to, do, form >= 50)
     _cache[("X", name)] = X
     return X
+
+
+# ---- the frames (tests/test_tree_shapes.py on the CPU, tests/test_gpu_tree_shapes_frames.py on the device)
+#
+# What a rendered frame of a shape needs.  Every triangle of the base set carries one material, so a frame of shape(name) could not
+# show which of two byte-identical triangles won a tie.  coloured(name) gives every triangle a material of its own -- a copy never
+# its original's --, swapped(name) exchanges the materials of every original and its copy (only for the CPU condition that the
+# winner shows in the frame), CAMERAS has a camera per shape.
+import zlib  # noqa: E402
+
+# (eye, target) of the camera that looks at the shape.  The shapes over the base set share median1's but leaf128, which looks at the
+# far pair of solids: its leaves of 128 part 3 of the 48 originals from their copies, and only there does a path meet such a pair (32
+# ray slots of the audited frames go to the copy, 285 to the original).  The tiny shapes look at their handful of triangles from close by
+_BASE_CAMERA = ((10.67, 6.67, 9.67), (6.67, 3.67, 3.67))
+_TINY_CAMERA = ((1.78, 4.67, 2.38), (1.67, 5.0, 2.33))
+CAMERAS = dict(chain=((3.5, 5.67, 6.67), (6.5, 3.67, 3.67)), median1=_BASE_CAMERA, leaf128=((14.67, 6.67, 7.67), (11.67, 4.17, 4.17)), root_leaf_8=_TINY_CAMERA,
+               two_leaves=_TINY_CAMERA, sah8=_BASE_CAMERA, uncovered=_BASE_CAMERA, loose=_BASE_CAMERA, leaf_misses=_BASE_CAMERA,
+               lbvh1=_BASE_CAMERA, lbvh3=_BASE_CAMERA, root_leaf_1=((2.28, 2.87, 2.57), (1.0, 2.67, 2.67)))
+FRAME_W, FRAME_H, FRAME_SPP, FRAME_BOUNCES = 64, 48, 4, 3
+EMISSIVE_ONE_IN, VARIED_ONE_IN = 16, 4
+
+
+def _look_at(eye, target):
+    """(eye, cameraRotate) of a camera at `eye` that looks at `target`: the columns of the rotation are right, up and back"""
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    f = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(f, [0.0, 1.0, 0.0])
+    right /= np.linalg.norm(right)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2] = right, np.cross(right, f), -f
+    return eye.astype(np.float32), m.T.ravel().astype(np.float32)
+
+
+def material_of(vertex_bytes, index):
+    """float32 [18]: the material of triangle `index`, from a generator seeded with the triangle's bytes and its index -- so a
+    byte-identical copy, which has another index, draws another material.  The base colour always varies; one triangle in 4 also
+    draws roughness, metallic, specular, clearcoat and anisotropy (what integrator 52 samples), one in 16 is a light."""
+    rng = np.random.default_rng([zlib.crc32(vertex_bytes), index])
+    kind = rng.integers(0, 1 << 30)
+    kw = dict(baseColor=tuple(float(x) for x in rng.uniform(0.1, 0.95, 3)))
+    if kind % VARIED_ONE_IN == 0:
+        kw.update(roughness=float(rng.uniform(0.2, 0.9)), metallic=float(rng.uniform(0.0, 0.9)), specular=float(rng.uniform(0.1, 0.9)),
+                  clearcoat=float(rng.uniform(0.0, 1.0)), anisotropic=float(rng.uniform(0.0, 0.9)))
+    if (kind // VARIED_ONE_IN) % EMISSIVE_ONE_IN == 0:
+        kw.update(emissive=tuple(float(x) for x in rng.uniform(0.5, 4.0, 3)))
+    return S.Material.disney(**kw).to18()
+
+
+def copy_pairs(tri):
+    """int [k, 2]: (original, copy) of every triangle that has a byte-identical copy at a higher index"""
+    V, first, pairs = vertices(tri), {}, []
+    for t in range(V.shape[0]):
+        o = first.setdefault(V[t].tobytes(), t)
+        if o != t:
+            pairs.append((o, t))
+    pairs = np.array(pairs, int).reshape(-1, 2)
+    assert np.unique(pairs).size == pairs.size                                      # pairs, no triples: an exchange is well defined
+    return pairs
+
+
+def coloured(name):
+    """(tri [n, 36], nodes): the shape's arrays with a material per triangle in columns 18:36; positions, normals and nodes are the
+    shape's own.  The LBVH shapes colour the arrays the device builder returned."""
+    if ("C", name) not in _cache:
+        tri, nodes, _ = shape(name)
+        V = vertices(tri)
+        out = np.array(tri)
+        for t in range(out.shape[0]):
+            out[t, 18:36] = material_of(V[t].tobytes(), t)
+        out.setflags(write=False)
+        _cache[("C", name)] = (out, nodes)
+    return _cache[("C", name)]
+
+
+def swapped(name):
+    """(tri, nodes): coloured(name) with the materials of every original and its copy exchanged"""
+    if ("S", name) not in _cache:
+        tri, nodes = coloured(name)
+        out = np.array(tri)
+        pairs = copy_pairs(tri)
+        out[pairs[:, 0], 18:36], out[pairs[:, 1], 18:36] = tri[pairs[:, 1], 18:36], tri[pairs[:, 0], 18:36]
+        out.setflags(write=False)
+        _cache[("S", name)] = (out, nodes)
+    return _cache[("S", name)]
+
+
+def covered_again():
+    """(tri, nodes): the triangle set of `uncovered` under a tree that covers all of it (buildBVHwithSAH(8) over the whole array)"""
+    if "covered_again" not in _cache:
+        _cache["covered_again"] = _host(shape("uncovered")[0], True, 8)
+    return _cache["covered_again"]
+
+
+def frame_env():
+    """(hdr, cache) of the frames: synthetic_hdr(64, 32) and its importance cache"""
+    if "env" not in _cache:
+        from ezrt_amd import scenes
+        hdr = scenes.synthetic_hdr(64, 32)
+        _cache["env"] = (hdr, S.calculateHdrCache(hdr))
+    return _cache["env"]
+
+
+def frame_params(name, integ, w=FRAME_W, h=FRAME_H, spp=FRAME_SPP, bounces=FRAME_BOUNCES, frame0=0, camera=None, **kw):
+    from ezrt_amd import trace
+    return trace.make_params(w, h, *_look_at(*CAMERAS[camera or name]), integ, bounces, spp=spp, frame0=frame0,
+                             env_clamp=10.0 if integ == 3 else 0.0, **kw)
+
+
+def same_pixels(a, b):
+    """bool [h, w]: the pixels of two frames that are equal on the bits in every channel"""
+    return (np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)).all(-1)
