@@ -289,6 +289,21 @@ WINDING_ABI = {
 }
 
 
+# stream-ordered plane queries on device memory, libezrt_hip.so only (include/ezrt_plane.h); pointers are device addresses
+PLANE_ABI = {
+    # n, n_tri, slices: the effective number of slices
+    "ezrt_plane_slices": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    # s, planes4, n, slices, part, n_cross, offsets, stream
+    "ezrt_query_plane_count_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # s, planes4, n, slices, part, offsets, capacity, tri_id, seg, stream
+    "ezrt_query_plane_section_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    # s, planes4, tri_id, n, crosses, side, seg, stream
+    "ezrt_plane_section_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+PLANE_TILE = 64  # planes per workgroup (ezrt_point_queries.h: PL_TILE)
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -357,7 +372,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

@@ -529,6 +529,63 @@ EZD long long winding_pair(const float4* __restrict__ tg, f3 p) {
   return winding_term(w, (double)p.x, (double)p.y, (double)p.z);
 }
 
+// ---- plane queries (include/ezrt_plane.h, where the definition is the contract): P1 (plane_load), P2 (plane_side), P3
+// (plane_crossed), P4 (plane_point) and P5 (plane_segment), in the header's order.  A triangle is held as nine doubles, the exact
+// conversions of its fp32 coordinates (a conversion back is exact too), so a kernel converts it once for all planes.
+struct PlaneEq {
+  double a, b, c, d;
+  int live; // P1
+};
+EZD void plane_load(const float* __restrict__ p4, PlaneEq& pl) {
+  const float a = p4[0], b = p4[1], c = p4[2], d = p4[3], inf = __builtin_inff();
+  pl.a = (double)a, pl.b = (double)b, pl.c = (double)c, pl.d = (double)d;
+  pl.live = ez_abs(a) < inf && ez_abs(b) < inf && ez_abs(c) < inf && ez_abs(d) < inf && !(a == 0.0f && b == 0.0f && c == 0.0f);
+}
+EZD double plane_side(const PlaneEq& pl, double x, double y, double z) { return ((pl.a * x + pl.b * y) + pl.c * z) - pl.d; }
+// the nine coordinates of tri_geom's rows as doubles; false where one of them is not finite
+EZD bool plane_tri(const float4* __restrict__ tg, double v[9]) {
+  const float4 ga = tg[0], gb = tg[1], gc = tg[2];
+  const float inf = __builtin_inff();
+  v[0] = (double)ga.x, v[1] = (double)ga.y, v[2] = (double)ga.z;
+  v[3] = (double)gb.x, v[4] = (double)gb.y, v[5] = (double)gb.z;
+  v[6] = (double)gc.x, v[7] = (double)gc.y, v[8] = (double)gc.z;
+  return ez_abs(ga.x) < inf && ez_abs(ga.y) < inf && ez_abs(ga.z) < inf && ez_abs(gb.x) < inf && ez_abs(gb.y) < inf &&
+         ez_abs(gb.z) < inf && ez_abs(gc.x) < inf && ez_abs(gc.y) < inf && ez_abs(gc.z) < inf;
+}
+// P3 of a triangle with finite coordinates and a live plane, from the three sides
+EZD bool plane_crossed(double s0, double s1, double s2) {
+  const bool u0 = s0 >= 0.0, u1 = s1 >= 0.0, u2 = s2 >= 0.0;
+  return !(u0 && u1 && u2) && (u0 || u1 || u2);
+}
+// P4: one coordinate of the point of the edge with the ends A < B (the order of their values), sides sa and sb, t = sa / (sa - sb)
+EZD float plane_coord(double A, double B, double sa, double sb, double t) {
+  const float a = (float)A, b = (float)B; // exact
+  float p = (float)(A + t * (B - A));
+  const float lo = b < a ? b : a, hi = b < a ? a : b;
+  p = p < lo ? lo : (p > hi ? hi : p);
+  return sa == 0.0 ? a : (sb == 0.0 ? b : p);
+}
+// P4: the point of the edge with the ends X and Y (sides sx and sy, one UP and one DOWN), whichever way round they are given
+EZD f3 plane_point(double Xx, double Xy, double Xz, double sx, double Yx, double Yy, double Yz, double sy) {
+  const bool sw = Yx < Xx || (Yx == Xx && (Yy < Xy || (Yy == Xy && Yz < Xz))); // less(Y, X)
+  const double sa = sw ? sy : sx, sb = sw ? sx : sy;
+  const double t = sa / (sa - sb);
+  return mk(plane_coord(sw ? Yx : Xx, sw ? Xx : Yx, sa, sb, t), plane_coord(sw ? Yy : Xy, sw ? Xy : Yy, sa, sb, t),
+            plane_coord(sw ? Yz : Xz, sw ? Xz : Yz, sa, sb, t));
+}
+// P5: (q0, q1) of a CROSSED triangle: the point of the directed edge that goes UP -> DOWN (p1 p2, p2 p3 or p3 p1), and of the one
+// that goes DOWN -> UP.  (Written on the three edges' points under selects of scalars: nothing is indexed.)
+EZD void plane_segment(const double v[9], double s0, double s1, double s2, f3& q0, f3& q1) {
+  const double x0 = v[0], y0 = v[1], z0 = v[2], x1 = v[3], y1 = v[4], z1 = v[5], x2 = v[6], y2 = v[7], z2 = v[8];
+  const bool u0 = s0 >= 0.0, u1 = s1 >= 0.0, u2 = s2 >= 0.0;
+  const bool a0 = u0 && !u1, a1 = !a0 && u1 && !u2;   // q0's edge is p1 p2, p2 p3, else p3 p1
+  const bool b0 = !u0 && u1, b1 = !b0 && !u1 && u2;   // q1's edge likewise
+  q0 = plane_point(a0 ? x0 : (a1 ? x1 : x2), a0 ? y0 : (a1 ? y1 : y2), a0 ? z0 : (a1 ? z1 : z2), a0 ? s0 : (a1 ? s1 : s2),
+                   a0 ? x1 : (a1 ? x2 : x0), a0 ? y1 : (a1 ? y2 : y0), a0 ? z1 : (a1 ? z2 : z0), a0 ? s1 : (a1 ? s2 : s0));
+  q1 = plane_point(b0 ? x0 : (b1 ? x1 : x2), b0 ? y0 : (b1 ? y1 : y2), b0 ? z0 : (b1 ? z1 : z2), b0 ? s0 : (b1 ? s1 : s2),
+                   b0 ? x1 : (b1 ? x2 : x0), b0 ? y1 : (b1 ? y2 : y0), b0 ? z1 : (b1 ? z2 : z0), b0 ? s1 : (b1 ? s2 : s0));
+}
+
 // ---- box-overlap queries (include/ezrt_box_overlap.h, where the definition is the contract): H1 .. H3 of one triangle against a
 // LIVE box (the caller has checked the box), in the header's order.  An edge axis has a[j] = 0: its term a[j] * d is a zero (d is
 // finite), and adding a zero changes at most the sign of a zero sum, which no comparison sees -- so those terms are left out and

@@ -1,9 +1,9 @@
 // ezrt_point_queries.h -- the gfx950 kernels of the point queries: closest point (include/ezrt_closest_point.h), nearest K
 // (include/ezrt_nearest.h), inside and signed distance (include/ezrt_inside.h), and of the box-overlap, triangle-overlap,
-// self-overlap, triangle-distance, sphere-cast, segment, oriented-box and winding-number queries (include/ezrt_box_overlap.h,
+// self-overlap, triangle-distance, sphere-cast, segment, oriented-box, winding-number and plane queries (include/ezrt_box_overlap.h,
 // include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h,
-// include/ezrt_obb_overlap.h, include/ezrt_winding.h).  One query point, box, triangle, ray or segment per lane, a workgroup of one wave.
-// Included by ezrt_queries.hip alone.
+// include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h).  One query point, box, triangle, ray or segment per lane
+// (the plane queries: one TRIANGLE per lane, the plane uniform), a workgroup of one wave.  Included by ezrt_queries.hip alone.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -34,6 +34,10 @@
 //   winding_kernel<ATOMIC, TILE>     no walk: every lane sums winding_term over a slice of the triangles (include/ezrt_winding.h)
 //   winding_finish_kernel            the int64 sums of a sliced call to float
 //   winding_at_kernel                winding_pair for pairs the caller holds
+//   plane_kernel<FILL>               no walk: one triangle per lane against a tile of planes, a ballot per plane (include/ezrt_plane.h)
+//   plane_total_kernel               part's rows summed to n_cross
+//   plane_offsets_kernel             the exclusive prefix sum of n_cross
+//   plane_at_kernel                  the plane rule for pairs the caller holds
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -1111,6 +1115,168 @@ __global__ __launch_bounds__(256) void winding_at_kernel(const float4* tri_geom,
   if ((uint32_t)tri < (uint32_t)n_tri) q = winding_pair(tri_geom + (size_t)tri * 3, ld3(points + (size_t)i * 3));
   fixed[i] = q;
   if (winding) winding[i] = winding_of(q);
+}
+
+// ---- plane queries (include/ezrt_plane.h).
+//
+// plane_kernel<FILL>: a workgroup of one wave per (tile of PL_TILE planes, slice of the triangle range): the grid is (tiles) x
+// (slices).  The tile's planes are converted once (plane_load) into LDS, one per lane, and read from there at one address for all
+// lanes -- a broadcast without bank conflicts.  The wave then goes through its slice in rounds of 64 triangles: each lane converts ONE
+// triangle to nine doubles, and for every plane of the tile evaluates the three sides (18 fp64 operations) and P3; the ballot of the
+// crossed lanes is uniform.
+// FILL = false: its population count is added to the plane's counter, which lane p keeps for plane p of the tile, and is stored to
+// part[i * slices + j] at the end: every (plane, slice) is written by exactly one lane of one workgroup, so nothing is zeroed first.
+// FILL = true: lane p first fetches the first row of (its plane, this slice): offsets[i] + part[i][0 .. j) (the wave sums a row of
+// part together, plane by plane).  A crossed lane's row is that base plus the number of set ballot bits below it -- the lanes hold
+// ascending ids and the rounds ascend, so the rows are in ascending id without a sort, and no other workgroup writes them -- and
+// only crossed lanes run P4's sort and division (plane_segment), behind a uniform branch on the ballot.  Rows >= capacity are not
+// written.  Nothing is read of the tree; no atomics; the index of every load and store is checked against its array's extent
+// (k < k1 <= n_tri, i < n, l < j <= slices, row < capacity).
+constexpr int PL_BLOCK = 64, PL_TILE = 64;
+struct PlaneArgs {
+  const float4* tri_geom;
+  int32_t n_tri;
+  int32_t per_slice;        // L: triangles per slice, a multiple of 64
+  int32_t slices;           // S
+  const float* planes;      // n x 4
+  uint32_t n;
+  int32_t* part;            // n x S: written (FILL = false) or read (FILL = true)
+  const long long* offsets; // FILL: n + 1
+  long long capacity;       // FILL
+  int32_t* tri_id;          // FILL: capacity
+  float* seg;               // FILL: capacity x 6, or null
+};
+template <bool FILL>
+__global__ __launch_bounds__(PL_BLOCK) void plane_kernel(PlaneArgs a) {
+  __shared__ PlaneEq tile[PL_TILE];
+  const int lane = (int)threadIdx.x;
+  const uint32_t i = blockIdx.x * PL_TILE + threadIdx.x; // lane p's plane
+  const int32_t j = (int32_t)blockIdx.y;
+  const long long k0l = (long long)j * a.per_slice;
+  const int32_t k0 = k0l < a.n_tri ? (int32_t)k0l : a.n_tri;
+  const int32_t k1 = a.n_tri - k0 < a.per_slice ? a.n_tri : k0 + a.per_slice;
+  const int m = a.n - blockIdx.x * PL_TILE < (uint32_t)PL_TILE ? (int)(a.n - blockIdx.x * PL_TILE) : PL_TILE; // planes of this tile
+  PlaneEq mine;
+  mine.a = mine.b = mine.c = mine.d = 0.0, mine.live = 0;
+  if (i < a.n) plane_load(a.planes + (size_t)i * 4, mine);
+  tile[lane] = mine;
+  int32_t cnt = 0;   // FILL = false: the crossed triangles of lane p's plane in this slice
+  long long row = 0; // FILL = true: the next row of lane p's plane
+  if (FILL) {
+#pragma unroll 1
+    for (int p = 0; p < m; p++) {
+      const size_t r = (size_t)(blockIdx.x * PL_TILE + (uint32_t)p) * (size_t)a.slices;
+      int32_t sum = 0;
+      for (int32_t l = lane; l < j; l += PL_BLOCK) sum += a.part[r + (size_t)l];
+      if (j > 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+      }
+      if (lane == p) row = a.offsets[i] + (long long)sum;
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int32_t base = k0; base < k1; base += PL_BLOCK) {
+    const int32_t k = base + lane;
+    double v[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool fin = false;
+    if (k < k1) fin = plane_tri(a.tri_geom + (size_t)k * 3, v);
+#pragma unroll 1
+    for (int p = 0; p < m; p++) {
+      const PlaneEq pl = tile[p];
+      const double s0 = plane_side(pl, v[0], v[1], v[2]), s1 = plane_side(pl, v[3], v[4], v[5]), s2 = plane_side(pl, v[6], v[7], v[8]);
+      const bool crossed = fin && pl.live != 0 && plane_crossed(s0, s1, s2);
+      const unsigned long long mask = __ballot(crossed);
+      if (!FILL) {
+        cnt += lane == p ? (int32_t)__popcll(mask) : 0;
+      } else if (mask != 0ull) {
+        const long long r0 = ((long long)__builtin_amdgcn_readlane((int)(row >> 32), p) << 32) |
+                             (long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)row, p);
+        if (crossed) {
+          const long long r = r0 + (long long)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+          if ((unsigned long long)r < (unsigned long long)a.capacity) { // (a negative row -- offsets that no count call left -- is no row)
+            a.tri_id[r] = k;
+            if (a.seg) {
+              f3 q0, q1;
+              plane_segment(v, s0, s1, s2, q0, q1);
+              float2* out = (float2*)(a.seg + (size_t)r * 6); // 24-byte rows: 8-byte aligned
+              out[0] = make_float2(q0.x, q0.y), out[1] = make_float2(q0.z, q1.x), out[2] = make_float2(q1.y, q1.z);
+            }
+          }
+        }
+        if (lane == p) row += (long long)__popcll(mask);
+      }
+    }
+  }
+  if (!FILL && i < a.n) a.part[(size_t)i * (size_t)a.slices + (size_t)j] = cnt;
+}
+// n_cross[i] = the sum of part's row i: one WAVE per plane (four to a workgroup), the lanes stride over the row -- coalesced, and a
+// call of few planes and thousands of slices is not one lane's chain of loads
+__global__ __launch_bounds__(256) void plane_total_kernel(const int32_t* part, int32_t slices, uint32_t n, int32_t* n_cross) {
+  const uint32_t i = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; // uniform across the wave
+  const int lane = (int)(threadIdx.x & 63);
+  if (i >= n) return;
+  int32_t sum = 0;
+  for (int32_t j = lane; j < slices; j += 64) sum += part[(size_t)i * (size_t)slices + (size_t)j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if (lane == 0) n_cross[i] = sum;
+}
+// offsets = the exclusive prefix sum of n_cross, the total in offsets[n]: ONE workgroup -- every thread sums a contiguous chunk, the
+// 1024 chunk sums are scanned in LDS, every thread writes its chunk.  Plain on purpose: n is the number of planes, and the sweep
+// before it costs n * n_tri pair evaluations (profiles/r24/plane_rates.txt has its time).
+constexpr int PL_SCAN = 1024;
+__global__ __launch_bounds__(PL_SCAN) void plane_offsets_kernel(const int32_t* n_cross, uint32_t n, long long* offsets) {
+  __shared__ long long sums[PL_SCAN];
+  const uint32_t t = threadIdx.x;
+  const unsigned long long chunk = ((unsigned long long)n + PL_SCAN - 1) / PL_SCAN;
+  const unsigned long long lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+  long long s = 0;
+  for (unsigned long long i = lo; i < hi; i++) s += n_cross[i];
+  sums[t] = s;
+  __syncthreads();
+  for (uint32_t o = 1; o < PL_SCAN; o <<= 1) {
+    const long long add = t >= o ? sums[t - o] : 0;
+    __syncthreads();
+    sums[t] += add;
+    __syncthreads();
+  }
+  long long run = sums[t] - s;
+  for (unsigned long long i = lo; i < hi; i++) {
+    offsets[i] = run;
+    run += n_cross[i];
+  }
+  if (t == PL_SCAN - 1) offsets[n] = sums[t];
+}
+
+// ezrt_plane_section_at_device: the rule for pairs the caller holds -- plane i against triangle tri_id[i].  An id outside the scene, a
+// plane that is not live and a triangle with a non-finite coordinate write zeros.
+__global__ __launch_bounds__(256) void plane_at_kernel(const float4* tri_geom, int32_t n_tri, const float* planes, const int32_t* tri_id,
+                                                       uint32_t n, uint8_t* crosses, int8_t* side, float* seg) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t tri = tri_id[i];
+  PlaneEq pl;
+  plane_load(planes + (size_t)i * 4, pl);
+  f3 q0 = mk(0.0f, 0.0f, 0.0f), q1 = q0;
+  int8_t sd[3] = {0, 0, 0};
+  bool crossed = false;
+  if ((uint32_t)tri < (uint32_t)n_tri && pl.live) {
+    double v[9];
+    if (plane_tri(tri_geom + (size_t)tri * 3, v)) {
+      const double s0 = plane_side(pl, v[0], v[1], v[2]), s1 = plane_side(pl, v[3], v[4], v[5]), s2 = plane_side(pl, v[6], v[7], v[8]);
+      sd[0] = (int8_t)((s0 > 0.0) - (s0 < 0.0)), sd[1] = (int8_t)((s1 > 0.0) - (s1 < 0.0)), sd[2] = (int8_t)((s2 > 0.0) - (s2 < 0.0));
+      crossed = plane_crossed(s0, s1, s2);
+      if (crossed) plane_segment(v, s0, s1, s2, q0, q1);
+    }
+  }
+  crosses[i] = crossed ? 1u : 0u;
+  if (side) side[(size_t)i * 3] = sd[0], side[(size_t)i * 3 + 1] = sd[1], side[(size_t)i * 3 + 2] = sd[2];
+  if (seg) {
+    float* out = seg + (size_t)i * 6;
+    out[0] = q0.x, out[1] = q0.y, out[2] = q0.z, out[3] = q1.x, out[4] = q1.y, out[5] = q1.z;
+  }
 }
 
 } // namespace ezd

@@ -1,9 +1,10 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
 // nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
-// oriented-box and winding-number queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
-// ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h;
-// the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream).  A translation unit of its own: none
+// oriented-box, winding-number and plane queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
+// ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
+// ezrt_plane.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// and two small kernels).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
 // ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
@@ -22,6 +23,7 @@
 #include "ezrt_segment.h"
 #include "ezrt_obb_overlap.h"
 #include "ezrt_winding.h"
+#include "ezrt_plane.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -520,6 +522,108 @@ int ezrt_winding_at_device(EzrtScene* s, const float* points3, const int32_t* tr
                           {winding, N * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(winding_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, points3, tri_id, (uint32_t)n, (long long*)fixed,
                          winding);
+    });
+  });
+}
+
+// ---- plane queries on device memory (include/ezrt_plane.h): no scratch (`part` and `offsets` are the caller's); checked, launched and
+// ordered against a refit by query_call.  No tree is read, so there is no route.
+//
+// The slices.  A workgroup is one wave for a slice of the triangle range and a tile of PL_TILE planes.  slices == 0: where the tiles
+// alone give PL_FILL = 16384 waves one slice; otherwise enough slices to reach that, but none below PL_MIN_SLICE = 256 triangles,
+// where the tile's conversion and the counters' store are no longer small beside the slice.  16384 is two waves for each of the
+// 8 x 1024 wave slots of an MI355X that the sweep's 40 VGPRs allow.  Measured (profiles/r24/plane_rates.txt): the COUNT
+// pass of 10 000 planes gets faster with more waves well past the slots (4 239 waves 690 to 730 Gpairs/s, 10 048 840 to 930, 16 485
+// 920 to 1 020, 40 192 1 050 to 1 100: the sides of one plane are three short dependent chains of fp64 operations, and short
+// workgroups leave a shorter tail), but the FILL pass pays for every slice before its own -- the sum of part[i][0 .. j) per plane of
+// the tile -- and 40960 waves, tried, lost 15 % on the fill of 10 000 random planes against 64 slices.  16384 is within the
+// run-to-run spread of the best of 1, 8 and 64 forced slices in both passes wherever a call takes longer than a launch.
+constexpr int PL_FILL = 16384, PL_MIN_SLICE = 256, PL_MAX_SLICES = 4096;
+int ezrt_plane_slices(int n, int n_tri, int slices) {
+  const long long rounds = n_tri > 0 ? ((long long)n_tri + PL_BLOCK - 1) / PL_BLOCK : 1;
+  long long c = 1;
+  if (slices >= 1) {
+    c = slices;
+  } else if (n > 0 && n_tri > 0) {
+    const long long tiles = ((long long)n + PL_TILE - 1) / PL_TILE;
+    const long long want = tiles >= PL_FILL ? 1 : (PL_FILL + tiles - 1) / tiles, most = n_tri / PL_MIN_SLICE;
+    c = want < most ? want : most;
+  }
+  if (c > rounds) c = rounds;
+  if (c > PL_MAX_SLICES) c = PL_MAX_SLICES;
+  return (int)(c < 1 ? 1 : c);
+}
+// L of the header: the triangles of a slice, a multiple of 64
+static int32_t plane_per_slice(int n_tri, int S) {
+  const long long per = ((long long)(n_tri > 0 ? n_tri : 0) + S - 1) / S;
+  const long long L = (per + PL_BLOCK - 1) / PL_BLOCK * PL_BLOCK;
+  return (int32_t)(L < PL_BLOCK ? PL_BLOCK : L);
+}
+int ezrt_query_plane_count_device(EzrtScene* s, const float* planes4, int n, int slices, int32_t* part, int32_t* n_cross, int64_t* offsets,
+                                  void* stream) {
+  return ezi::guarded("ezrt_query_plane_count_device", [&]() -> int {
+    if (!s || !planes4 || !part || !n_cross || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (slices < 0) return fail(EZRT_ERR_INVALID, "slices < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tri = (int)s->n_tri, S = ezrt_plane_slices(n, n_tri, slices);
+    return query_call(s, {{planes4, N * 4 * sizeof(float)}, {part, N * (size_t)S * sizeof(int32_t)}, {n_cross, N * sizeof(int32_t)},
+                          {offsets, (N + 1) * sizeof(int64_t)}}, N, st, [&](dim3, dim3) {
+      PlaneArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = n_tri;
+      a.per_slice = plane_per_slice(n_tri, S);
+      a.slices = S;
+      a.planes = planes4;
+      a.n = (uint32_t)n;
+      a.part = part;
+      hipLaunchKernelGGL((plane_kernel<false>), dim3((unsigned)((N + PL_TILE - 1) / PL_TILE), (unsigned)S), dim3(PL_BLOCK), 0, st, a);
+      hipLaunchKernelGGL(plane_total_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const int32_t*)part, (int32_t)S, (uint32_t)n, n_cross);
+      if (offsets) hipLaunchKernelGGL(plane_offsets_kernel, dim3(1), dim3(PL_SCAN), 0, st, (const int32_t*)n_cross, (uint32_t)n, (long long*)offsets);
+    });
+  });
+}
+int ezrt_query_plane_section_device(EzrtScene* s, const float* planes4, int n, int slices, const int32_t* part, const int64_t* offsets,
+                                    int64_t capacity, int32_t* tri_id, float* seg, void* stream) {
+  return ezi::guarded("ezrt_query_plane_section_device", [&]() -> int {
+    if (!s || !planes4 || !part || !offsets || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (slices < 0) return fail(EZRT_ERR_INVALID, "slices < 0");
+    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
+    if (!tri_id && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL tri_id with capacity > 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, cap = (size_t)capacity;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tri = (int)s->n_tri, S = ezrt_plane_slices(n, n_tri, slices);
+    return query_call(s, {{planes4, N * 4 * sizeof(float)}, {part, N * (size_t)S * sizeof(int32_t)}, {offsets, (N + 1) * sizeof(int64_t)},
+                          {tri_id, cap * sizeof(int32_t)}, {seg, cap * 6 * sizeof(float)}}, N, st, [&](dim3, dim3) {
+      if (capacity == 0) return; // no row can be written
+      PlaneArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = n_tri;
+      a.per_slice = plane_per_slice(n_tri, S);
+      a.slices = S;
+      a.planes = planes4;
+      a.n = (uint32_t)n;
+      a.part = const_cast<int32_t*>(part);
+      a.offsets = (const long long*)offsets;
+      a.capacity = (long long)capacity;
+      a.tri_id = tri_id;
+      a.seg = seg;
+      hipLaunchKernelGGL((plane_kernel<true>), dim3((unsigned)((N + PL_TILE - 1) / PL_TILE), (unsigned)S), dim3(PL_BLOCK), 0, st, a);
+    });
+  });
+}
+int ezrt_plane_section_at_device(EzrtScene* s, const float* planes4, const int32_t* tri_id, int n, uint8_t* crosses, int8_t* side, float* seg,
+                                 void* stream) {
+  return ezi::guarded("ezrt_plane_section_at_device", [&]() -> int {
+    if (!s || !planes4 || !tri_id || !crosses || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{planes4, N * 4 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {crosses, N}, {side, N * 3},
+                          {seg, N * 6 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(plane_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, planes4, tri_id, (uint32_t)n, crosses, side, seg);
     });
   });
 }

@@ -1,7 +1,7 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
-include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h).
+include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -33,6 +33,9 @@ include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h).
     w = query.winding_number(scene, points)                                   # how often the mesh wraps each point: 1 inside, 0 outside
     w, fixed = query.winding_number(scene, points, fixed=True)                # ... and the exact int64 sum behind it (include/ezrt_winding.h)
     w, fixed = query.winding_number_at(scene, points, tri)                    # ... the term of single triangles, for pairs already held
+    n_cross = query.plane_count(scene, planes)                                # how many triangles each plane a x + b y + c z = d crosses
+    offsets, tri, seg = query.plane_section(scene, planes)                    # ... and all of them with their segments, CSR (include/ezrt_plane.h)
+    crosses, side, seg = query.plane_section_at(scene, planes, tri)           # ... the same rule for pairs already held
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -939,3 +942,113 @@ def winding_number_at(scene, points, tri, stream=None):
                                             P(h)))
     _keep((points, per_entry, tri, acc, out), ts, points)
     return out, acc
+
+
+def _check_slices(slices):
+    if slices is None:
+        return 0
+    if not isinstance(slices, int) or isinstance(slices, bool) or slices < 1:
+        raise ValueError("slices must be None or an int >= 1, not %r" % (slices,))
+    return min(slices, 2**31 - 1)
+
+
+def _check_planes(planes):
+    _tensor("planes", planes, torch.float32, last=4)
+    return _count(planes, 4, "planes")
+
+
+def _plane_counts(scene, lib, planes, n, c, h, ts, want_offsets):
+    """(S, part int32 [n, S], n_cross int32 [n], offsets int64 [n + 1] or None), enqueued on the query's stream"""
+    S = int(lib.ezrt_plane_slices(n, scene.stats()["n_tri"], c))
+    dev = planes.device
+    part = torch.empty((n, S), dtype=torch.int32, device=dev)
+    n_cross = torch.empty((n,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev) if want_offsets else None
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_plane_count_device(scene._h, P(planes.data_ptr()), n, c, P(part.data_ptr()), P(n_cross.data_ptr()),
+                                                   P(offsets.data_ptr()) if want_offsets else None, P(h)))
+    return S, part, n_cross, offsets
+
+
+def plane_count(scene, planes, slices=None, stream=None):
+    """int32 planes.shape[:-1]: the number of triangles each plane of `planes` (a contiguous float32 GPU tensor [..., 4]: a, b, c, d of
+    a x + b y + c z = d, the normal need not be unit) CROSSES: the triangles with a vertex on the plane or on the side its normal
+    points to, and a vertex strictly on the other side.  A plane with a non-finite entry or a zero normal crosses nothing.  Every
+    plane is tested against every triangle (no tree is read); `slices=None` lets the library split the triangle range over
+    workgroups where the planes alone do not fill the device, `slices=k` forces k slices -- the answer is the same.  The
+    definition, on the bits: include/ezrt_plane.h."""
+    c = _check_slices(slices)
+    n = _check_planes(planes)
+    lib = _scene_lib(scene, _abi.PLANE_ABI)
+    lead = tuple(planes.shape[:-1])
+    if n == 0:
+        return torch.empty(lead, dtype=torch.int32, device=planes.device)
+    h, ts = _stream(planes, stream)
+    _, part, n_cross, _ = _plane_counts(scene, lib, planes, n, c, h, ts, False)
+    _keep((planes, part, n_cross), ts, planes)
+    return n_cross.view(lead)
+
+
+def plane_section(scene, planes, capacity=None, slices=None, stream=None):
+    """(offsets int64 [n + 1], tri int32 [rows], seg float32 [rows, 2, 3]): the cross-sections of the mesh with the n planes of `planes`
+    ([..., 4], flattened row-major), complete, in CSR form: rows offsets[i] .. offsets[i + 1] hold the triangles plane i crosses in
+    ascending id, and for each the segment q0 -> q1 in which the plane cuts it, oriented so that the material of an outward-wound
+    mesh lies on its left seen from the side the plane's normal points to.  Two triangles that share an edge by value get the same
+    end point on the bits, so the segments chain into loops with a dictionary on the end points' bytes.  `capacity=None`
+    synchronises the stream once to read the total, offsets[n], and returns exactly that many rows.  A given `capacity` never
+    synchronises and returns `capacity` rows: rows past offsets[n] keep tri == -1, and rows that did not fit are simply missing --
+    compare offsets[n] with the capacity.  `slices` as for plane_count.  The definition, on the bits: include/ezrt_plane.h."""
+    c = _check_slices(slices)
+    n = _check_planes(planes)
+    if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0):
+        raise ValueError("capacity must be None or an int >= 0, not %r" % (capacity,))
+    lib = _scene_lib(scene, _abi.PLANE_ABI)
+    dev = planes.device
+    h, ts = _stream(planes, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    if n == 0:
+        rows = 0 if capacity is None else capacity
+        with torch.cuda.stream(own):
+            return (torch.zeros((1,), dtype=torch.int64, device=dev), torch.full((rows,), -1, dtype=torch.int32, device=dev),
+                    torch.zeros((rows, 2, 3), dtype=torch.float32, device=dev))
+    _, part, n_cross, offsets = _plane_counts(scene, lib, planes, n, c, h, ts, True)
+    if capacity is None:
+        with torch.cuda.stream(own):
+            rows = int(offsets[n].item())                          # the one synchronisation: of the query's stream
+    else:
+        rows = capacity
+    with torch.cuda.stream(own):
+        tri = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+        seg = torch.zeros((rows, 2, 3), dtype=torch.float32, device=dev)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_query_plane_section_device(scene._h, P(planes.data_ptr()), n, c, P(part.data_ptr()), P(offsets.data_ptr()), rows,
+                                                     P(tri.data_ptr()) if rows else None, P(seg.data_ptr()) if rows else None, P(h)))
+    _keep((planes, part, n_cross, offsets, tri, seg), ts, planes)
+    return offsets, tri, seg
+
+
+def plane_section_at(scene, planes, tri, stream=None):
+    """(crosses bool tri.shape, side int8 tri.shape + (3,), seg float32 tri.shape + (2, 3)): the plane rule for pairs already held --
+    plane i against triangle tri[i].  `tri` (int32) has the shape planes.shape[:-1], or one trailing dimension more, and every entry
+    of a row then belongs to the row's plane.  `side` is the sign of p1, p2 and p3 against the plane (-1 / 0 / +1; 0 is ON the plane,
+    which the rule counts to the normal's side): with it a caller applies a touching rule of their own.  An id that is no triangle
+    of the scene (an unused slot, -1), a plane that is not live and a triangle with a non-finite coordinate give zeros; a pair that
+    is not crossed has a zero seg.  `crosses` summed over all triangles of the scene is plane_count's."""
+    _check_planes(planes)
+    lib = _scene_lib(scene, _abi.PLANE_ABI)
+    lead = tuple(planes.shape[:-1])
+    _tensor("tri", tri, torch.int32, device=planes.device)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    crosses = torch.empty(shape, dtype=torch.uint8, device=planes.device)
+    side = torch.empty(shape + (3,), dtype=torch.int8, device=planes.device)
+    seg = torch.empty(shape + (2, 3), dtype=torch.float32, device=planes.device)
+    if n == 0:
+        return crosses.view(torch.bool), side, seg
+    h, ts = _stream(planes, stream)
+    per_entry = _per_entry(planes, lead, shape, h, ts)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_plane_section_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(crosses.data_ptr()),
+                                                  P(side.data_ptr()), P(seg.data_ptr()), P(h)))
+    _keep((planes, per_entry, tri, crosses, side, seg), ts, planes)
+    return crosses.view(torch.bool), side, seg
