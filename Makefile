@@ -60,10 +60,27 @@ clean:
 	rm -f $(LIBDIR)/*.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all host hip oracle examples clean negctl
+.PHONY: all host hip oracle examples clean negctl olvariants
 
 # negative control of tests/test_gpu_prune.py (tools/gpu_negctl.sh): the HIP library with a pruning margin that is
 # negative on purpose; never loaded by the product (EZRT_HIP_LIB selects it for that one run)
 negctl:
 	@mkdir -p build_ab
 	$(HIPCC) $(HIP_FLAGS) -DEZRT_PRUNE_NEGATIVE_CONTROL=1 -shared -o build_ab/libezrt_hip_negctl.so $(HIP_SRC) -ldl -pthread
+
+# measurement variants of the overlap lists (include/ezrt_overlap_list.h; tools/gpu_overlap_list_variants.sh runs them): the HIP
+# library with other limits compiled in, and one without the sort launch (its long rows are unsorted: for timing the fill kernel
+# alone).  Only ezrt_queries.hip is compiled again; never loaded by the product (EZRT_HIP_LIB selects one for a run).  The i16
+# library is also what runs fill_rows' insertion path in tests/test_gpu_overlap_list.py, which the compiled insert_max = 0 never takes.
+OL_OTHER_OBJ = $(filter-out build/hip/ezrt_queries.o,$(HIP_OBJ))
+OL_VARIANTS = i16_t4096 i64_t4096 i0_t2048 i0_t8192 nosort
+OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
+OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
+OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048
+OL_FLAGS_i0_t8192 = -DEZRT_OL_TILE_MAX=8192
+OL_FLAGS_nosort = -DEZRT_OL_SKIP_SORT=1
+olvariants: $(addprefix build_ab/libezrt_hip_,$(addsuffix .so,$(OL_VARIANTS)))
+build_ab/libezrt_hip_%.so: ezrt_amd/csrc/hip/ezrt_queries.hip $(OL_OTHER_OBJ) $(wildcard ezrt_amd/csrc/hip/*.h) $(wildcard include/*)
+	@mkdir -p build_ab
+	$(HIPCC) $(HIP_FLAGS) $(OL_FLAGS_$*) -c -o build_ab/ezrt_queries_$*.o ezrt_amd/csrc/hip/ezrt_queries.hip
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OL_OTHER_OBJ) build_ab/ezrt_queries_$*.o -ldl -pthread

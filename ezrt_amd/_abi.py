@@ -304,6 +304,35 @@ PLANE_ABI = {
 PLANE_TILE = 64  # planes per workgroup (ezrt_point_queries.h: PL_TILE)
 
 
+# stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
+_LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
+OVERLAP_LIST_ABI = {
+    # insert_max, tile_max: the limits as compiled (host pointers; no device work)
+    "ezrt_overlap_list_limits": (None, [C.c_void_p, C.c_void_p]),
+    # s, n_overlap, n, offsets, stream
+    "ezrt_overlap_offsets_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # s, box_lo3, box_hi3, n, offsets, capacity, tri_id, n_found, stream
+    "ezrt_query_box_overlap_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + _LIST),
+    # s, centre3, axes9, n, offsets, capacity, tri_id, n_found, stream
+    "ezrt_query_obb_overlap_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + _LIST),
+    # s, tris9, n, offsets, capacity, tri_id, n_found, stream
+    "ezrt_query_tri_overlap_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + _LIST),
+    # s, ids, n, offsets, capacity, tri_id, n_found, stream
+    "ezrt_query_self_overlap_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + _LIST),
+    # s, segs6, radius, n, offsets, capacity, tri_id, n_found, stream
+    "ezrt_query_capsule_overlap_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + _LIST),
+}
+
+
+def overlap_list_limits():
+    """(insert_max, tile_max) of the loaded HIP library: rows up to insert_max ids are kept sorted while they are filled, rows up to
+    tile_max ids are sorted in LDS, longer ones in global memory (include/ezrt_overlap_list.h).  No device work."""
+    lib = _declare(load_hip(), OVERLAP_LIST_ABI)
+    a, b = C.c_int(-1), C.c_int(-1)
+    lib.ezrt_overlap_list_limits(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 # device-side refit of a scene's geometry, libezrt_hip.so only (include/ezrt_refit.h); tri36 is a device address
 REFIT_ABI = {
     "ezrt_scene_refit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -372,7 +401,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

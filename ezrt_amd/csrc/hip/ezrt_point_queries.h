@@ -14,7 +14,10 @@
 //   inside_kernel<WALK>              inside_count: slot_walk on the rows its axis needs
 //   signed_distance_kernel<WALK>     inside_count + closest_point_search + closest_point_store
 //   collect_rows                     a K-entry list of the lowest ids and a count over the caller's traversal, and the wave's row finish
-//   overlap_rows                     collect_rows over slot_walk on the query's box
+//   fill_rows<WALK>                  collect_rows for a row of the caller's length (include/ezrt_overlap_list.h): every id, not the lowest K
+//   overlap_rows                     collect_rows or fill_rows over slot_walk on the query's box
+//   *_overlap_list_kernel<WALK>      the five overlap kernels' bodies with a list's arguments: fill_rows instead of collect_rows
+//   overlap_sort_kernel              sorts the rows that fill_rows appended on the walk route, in LDS or in place in global memory
 //   box_overlap_kernel<WALK>         overlap_rows with the box as the gate and box_overlaps as the rule
 //   box_overlap_at_kernel            box_overlaps for pairs the caller holds
 //   tri_overlap_kernel<WALK>         overlap_rows with the query triangle's bounding box as the gate and tri_overlaps as the rule
@@ -518,9 +521,97 @@ EZD void collect_rows(const Args& a, Load load, Overlaps overlaps, Search search
     if (i - lane + row < a.n && slot >= (uint32_t)used) a.tri[base + e] = -1;
   }
 }
+// ---- overlap lists (include/ezrt_overlap_list.h): the fill side of count / offsets / fill.
+//
+// fill_rows is collect_rows for a row of the caller's length: lane i's row is tri[offsets[i] .. offsets[i + 1]), and it holds EVERY
+// triangle that passes `overlaps`, not the lowest K.  load, overlaps and search are collect_rows' own, so a list kernel is its
+// max_k sibling with other arguments (the *_body functions below serve both).  A row that is no row -- offsets[i] < 0, offsets[i + 1] <
+// offsets[i] or offsets[i + 1] > capacity -- has length 0 here: the traversal still runs and counts (n_found reports the truth), and
+// nothing is stored.  Every store is ri[j] with 0 <= j < len, so whatever the offsets say nothing outside a row that is valid and
+// fits is written.
+//   len <= OL_INSERT_MAX on the walk: collect_rows' insertion with K = len, the row sorted at every moment.  When the offsets are
+//     the count's, the row is never full before the last overlap, so no id is dropped; when they are not (n_found != len) the row
+//     keeps the lowest len ids met, inside itself.
+//   longer rows on the walk: appended in the order of the visits while count < len, and sorted afterwards by overlap_sort_kernel.
+//   the sweep visits ascending ids: every row is appended and none needs a sort.
+// There is no wave-level row finish: a row has no unused slots when the offsets are the count's, and where they are not its contents
+// are unspecified.  OL_INSERT_MAX and OL_TILE_MAX are what ezrt_overlap_list_limits reports (the macros exist for the measured
+// comparison of DESIGN.md "Overlap lists": `make olvariants` builds those libraries under build_ab/, the product's build sets none
+// of them, and tools/gpu_overlap_list_variants.sh runs the tests on the insert_max = 16 one -- EZRT_OL_SKIP_SORT leaves pass 2 out, so that
+// tools/overlap_list_rates.py can time the fill kernel alone: such a library's long rows are unsorted, and it is never the product).
+#ifndef EZRT_OL_SKIP_SORT
+#define EZRT_OL_SKIP_SORT 0
+#endif
+#ifndef EZRT_OL_INSERT_MAX
+#define EZRT_OL_INSERT_MAX 0 // measured (profiles/r25/overlap_list_rates.txt): appending and sorting beats the insertion at every row length
+#endif
+#ifndef EZRT_OL_TILE_MAX
+#define EZRT_OL_TILE_MAX 4096
+#endif
+constexpr int OL_INSERT_MAX = EZRT_OL_INSERT_MAX; // rows up to this length are kept sorted while they are filled (0 .. 64)
+constexpr int OL_TILE_MAX = EZRT_OL_TILE_MAX;     // rows up to this length are sorted in LDS (a power of two; 4 B each)
+constexpr bool OL_SKIP_SORT = EZRT_OL_SKIP_SORT != 0;
+static_assert(OL_INSERT_MAX >= 0 && OL_INSERT_MAX <= 64, "the insertion is collect_rows': K <= 64");
+static_assert(OL_TILE_MAX > 64 && (OL_TILE_MAX & (OL_TILE_MAX - 1)) == 0 && OL_TILE_MAX * 4 < 64 * 1024, "a power of two inside 64 KiB");
+struct OverlapList {
+  const long long* offsets; // n + 1
+  long long capacity;
+  int32_t* tri;             // capacity
+  int32_t* n_found;         // n, or null
+};
+// the row [base, base + len) that offsets[i], offsets[i + 1] and the capacity describe; (0, 0) when they describe none
+EZD void list_row(long long o0, long long o1, long long capacity, long long& base, long long& len) {
+  const bool ok = o0 >= 0 && o1 >= o0 && o1 <= capacity;
+  base = ok ? o0 : 0;
+  len = ok ? o1 - o0 : 0;
+}
+template <bool WALK, class Query, class Args, class Load, class Overlaps, class Search>
+EZD void fill_rows(const Args& a, Load load, Overlaps overlaps, Search search) {
+  const uint32_t i = blockIdx.x * CP_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  Query q;
+  const bool live = load(i, q);
+  long long base, len;
+  list_row(a.offsets[i], a.offsets[(size_t)i + 1], a.capacity, base, len);
+  int32_t* ri = a.tri + base; // (not dereferenced when len == 0: tri may be null with capacity == 0)
+  const bool sorted = WALK && len <= (long long)OL_INSERT_MAX;
+  const int K = sorted ? (int)len : 0;
+  int32_t count = 0;
+  int nb = 0;
+  int32_t last_id = -1; // collect_rows': entry K - 1 once the row is full
+  auto put = [&](int j, int32_t id) {
+    ri[j] = id;
+    if (j == K - 1) last_id = id; // (a put to slot K - 1 happens only when the row is full)
+  };
+  auto visit = [&](int32_t k) {
+    if (!overlaps(a.sc.tri_geom + (size_t)k * 3, q)) return;
+    const int32_t c = count++;
+    if (!sorted) {
+      if ((long long)c < len) ri[c] = k;
+      return;
+    }
+    if (nb == K && k > last_id) return; // behind a full row (offsets that are not the count's): counted only
+    int j = nb < K ? nb++ : K - 1;
+    while (j > 0) {
+      const int32_t ip = ri[j - 1];
+      if (ip < k) break;
+      put(j, ip);
+      j--;
+    }
+    put(j, k);
+  };
+  if (live) search(q, visit);
+  if (a.n_found) a.n_found[i] = count;
+}
+// collect_rows for the max_k calls' arguments, fill_rows for a list's
+template <bool WALK, class Query, class Args, class Load, class Overlaps, class Search>
+EZD void rows(const Args& a, Load load, Overlaps overlaps, Search search) {
+  if constexpr (__is_base_of(OverlapList, Args)) fill_rows<WALK, Query>(a, load, overlaps, search);
+  else collect_rows<Query>(a, load, overlaps, search);
+}
 template <bool WALK, class Query, class Args, class Load, class Overlaps>
 EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Overlaps overlaps) {
-  collect_rows<Query>(a, load, overlaps, [&](const Query& q, auto& visit) {
+  rows<WALK, Query>(a, load, overlaps, [&](const Query& q, auto& visit) {
     if (WALK) {
       const f3 &lo = q.lo, &hi = q.hi;
       slot_walk(
@@ -548,9 +639,14 @@ EZD void overlap_rows(const Args& a, int* __restrict__ lds_stack, Load load, Ove
 struct BoxQuery {
   f3 lo, hi;
 };
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+struct BoxOverlapListArgs : OverlapList {
+  PointScene sc;
+  const float* lo;          // n x 3
+  const float* hi;          // n x 3
+  uint32_t n;
+};
+template <bool WALK, class Args>
+EZD void box_overlap_body(const Args& a, int* __restrict__ lds_stack) {
   overlap_rows<WALK, BoxQuery>(
       a, lds_stack,
       [&](uint32_t i, BoxQuery& q) {
@@ -558,6 +654,16 @@ __global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a)
         return box_live(q.lo, q.hi);
       },
       [](const float4* tg, const BoxQuery& q) { return box_overlaps(tg, q.lo, q.hi); });
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void box_overlap_kernel(BoxOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  box_overlap_body<WALK>(a, lds_stack);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void box_overlap_list_kernel(BoxOverlapListArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  box_overlap_body<WALK>(a, lds_stack);
 }
 
 // ezrt_box_overlap_at_device: box_overlaps for pairs the caller holds -- box i against triangle tri_id[i].  An id outside the scene
@@ -588,9 +694,13 @@ struct TriOverlapArgs {
   int32_t* tri;             // n x K (not read or written when K == 0)
   int32_t* n_overlap;       // n, or null
 };
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void tri_overlap_kernel(TriOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+struct TriOverlapListArgs : OverlapList {
+  PointScene sc;
+  const float* tris;        // n x 9
+  uint32_t n;
+};
+template <bool WALK, class Args>
+EZD void tri_overlap_body(const Args& a, int* __restrict__ lds_stack) {
   overlap_rows<WALK, TriQuery>(
       a, lds_stack,
       [&](uint32_t i, TriQuery& q) {
@@ -598,6 +708,16 @@ __global__ __launch_bounds__(CP_BLOCK) void tri_overlap_kernel(TriOverlapArgs a)
         return tri_query(ld3(t), ld3(t + 3), ld3(t + 6), q);
       },
       [](const float4* tg, const TriQuery& q) { return tri_overlaps(tg, q); });
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void tri_overlap_kernel(TriOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  tri_overlap_body<WALK>(a, lds_stack);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void tri_overlap_list_kernel(TriOverlapListArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  tri_overlap_body<WALK>(a, lds_stack);
 }
 
 // ezrt_tri_overlap_at_device: tri_overlaps for pairs the caller holds -- query triangle i against triangle tri_id[i].  An id outside
@@ -640,9 +760,13 @@ EZD bool self_query(const PointScene& sc, int32_t id, TriQuery& q) {
   const float4 ga = g[0], gb = g[1], gc = g[2];
   return tri_query(mk(ga.x, ga.y, ga.z), mk(gb.x, gb.y, gb.z), mk(gc.x, gc.y, gc.z), q);
 }
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void self_overlap_kernel(SelfOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+struct SelfOverlapListArgs : OverlapList {
+  PointScene sc;
+  const int32_t* ids;       // n, or null: query i is triangle i
+  uint32_t n;
+};
+template <bool WALK, class Args>
+EZD void self_overlap_body(const Args& a, int* __restrict__ lds_stack) {
   overlap_rows<WALK, SelfQuery>(
       a, lds_stack,
       [&](uint32_t i, SelfQuery& q) {
@@ -650,6 +774,16 @@ __global__ __launch_bounds__(CP_BLOCK) void self_overlap_kernel(SelfOverlapArgs 
         return self_query(a.sc, q.id, q);
       },
       [&](const float4* tg, const SelfQuery& q) { return tg != a.sc.tri_geom + (size_t)q.id * 3 && self_crosses(tg, q); });
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void self_overlap_kernel(SelfOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  self_overlap_body<WALK>(a, lds_stack);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void self_overlap_list_kernel(SelfOverlapListArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  self_overlap_body<WALK>(a, lds_stack);
 }
 
 // ezrt_self_overlap_at_device: self_crosses for pairs the caller holds -- triangle tri_a[i] against triangle tri_b[i].  An id outside
@@ -928,10 +1062,15 @@ struct CapsuleOverlapArgs {
   int32_t* tri;             // n x K (not read or written when K == 0)
   int32_t* n_overlap;       // n, or null
 };
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_kernel(CapsuleOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  collect_rows<CapsuleQuery>(
+struct CapsuleOverlapListArgs : OverlapList {
+  PointScene sc;
+  const float* segs;        // n x 6: a, b
+  const float* radius;      // n
+  uint32_t n;
+};
+template <bool WALK, class Args>
+EZD void capsule_overlap_body(const Args& a, int* __restrict__ lds_stack) {
+  rows<WALK, CapsuleQuery>(
       a,
       [&](uint32_t i, CapsuleQuery& q) {
         const float* t = a.segs + (size_t)i * 6;
@@ -950,6 +1089,16 @@ __global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_kernel(CapsuleOverla
         bound_visit<WALK, false>(
             a.sc, [&](f3 lo, f3 hi) { return tri_distance_box(q.qlo, q.qhi, lo, hi); }, lds_stack + threadIdx.x, [&] { return q.R2; }, visit);
       });
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_kernel(CapsuleOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  capsule_overlap_body<WALK>(a, lds_stack);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void capsule_overlap_list_kernel(CapsuleOverlapListArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  capsule_overlap_body<WALK>(a, lds_stack);
 }
 
 // ---- oriented-box queries (include/ezrt_obb_overlap.h).
@@ -982,10 +1131,15 @@ EZD bool obb_load(const float* centre, const float* axes, uint32_t i, ObbQuery& 
   const float* u = axes + (size_t)i * 9;
   return obb_query(ld3(centre + (size_t)i * 3), ld3(u), ld3(u + 3), ld3(u + 6), q);
 }
-template <bool WALK>
-__global__ __launch_bounds__(CP_BLOCK) void obb_overlap_kernel(ObbOverlapArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
-  collect_rows<ObbQuery>(
+struct ObbOverlapListArgs : OverlapList {
+  PointScene sc;
+  const float* centre;      // n x 3
+  const float* axes;        // n x 9: u0 u1 u2
+  uint32_t n;
+};
+template <bool WALK, class Args>
+EZD void obb_overlap_body(const Args& a, int* __restrict__ lds_stack) {
+  rows<WALK, ObbQuery>(
       a, [&](uint32_t i, ObbQuery& q) { return obb_load(a.centre, a.axes, i, q); },
       [](const float4* tg, const ObbQuery& q) { return obb_overlaps(tg, q); },
       [&](const ObbQuery& q, auto& visit) {
@@ -1014,6 +1168,114 @@ __global__ __launch_bounds__(CP_BLOCK) void obb_overlap_kernel(ObbOverlapArgs a)
           for (int k = 0; k < a.sc.n_tri; k++) visit(k);
         }
       });
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void obb_overlap_kernel(ObbOverlapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  obb_overlap_body<WALK>(a, lds_stack);
+}
+template <bool WALK>
+__global__ __launch_bounds__(CP_BLOCK) void obb_overlap_list_kernel(ObbOverlapListArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int lds_stack[];
+  obb_overlap_body<WALK>(a, lds_stack);
+}
+
+// overlap_sort_kernel: pass 2 of a list call on the walk route -- in place, ascending, every row that is longer than OL_INSERT_MAX,
+// valid and inside the capacity (fill_rows appended it in the order of the visits).  A workgroup of OL_SORT_BLOCK threads has
+// OL_SORT_ROWS consecutive rows: its first OL_SORT_ROWS + 1 threads load one offset each into LDS, and a workgroup whose rows need
+// nothing ends there.  The rows that need it are sorted one after the other by the whole workgroup, by the bitonic network in its
+// one-direction form: stage h = 1, 2, 4, .. < len first compares i with its mirror in its block of 2 h (i ^ (2 h - 1)), then i with
+// i + g for g = h / 2 .. 1, always the lower id to the lower index.  Every comparison points the same way, so a length that is no
+// power of two is padded with +inf that never moves: a pair whose upper index is >= len is skipped, and nothing is stored.
+//   len <= OL_TILE_MAX: the row is copied to LDS, sorted there and copied back.
+//   longer rows stay in global memory, no second buffer: the steps of distance < OL_TILE_MAX act inside aligned chunks of
+//     OL_TILE_MAX entries and are run chunk by chunk in LDS; only the steps of distance >= OL_TILE_MAX go through global memory,
+//     with a barrier after each (the row belongs to this workgroup alone, and __syncthreads orders its global accesses).
+// A row longer than the scene has triangles is no count's row; it is left as it is (its contents are unspecified) instead of
+// being sorted for the time its length would take.  Indices: i < l < len <= n_tri < 2^31 in 32 bits, the row's base in 64.
+constexpr int OL_SORT_BLOCK = 256, OL_SORT_ROWS = 16;
+struct OverlapSortArgs {
+  const long long* offsets; // n + 1
+  long long capacity;
+  int32_t* tri;             // capacity
+  uint32_t n;
+  int32_t n_tri;
+};
+// one step on p[0 .. m): thread t of the workgroup takes the pairs t, t + OL_SORT_BLOCK, ..; pair u of half-block h is
+// i = 2 h (u / h) + u % h and l = i ^ (2 h - 1) (flip) or i + h
+EZD void ol_step(int32_t* p, uint32_t m, uint32_t h, bool flip, uint32_t t) {
+  for (uint32_t u = t; u < m; u += OL_SORT_BLOCK) { // (i >= u: no pair is lost, and 2 u does not wrap)
+    const uint32_t i = ((u & ~(h - 1u)) << 1) | (u & (h - 1u));
+    if (i >= m) break;
+    const uint32_t l = flip ? i ^ (2u * h - 1u) : i | h;
+    if (l < m) {
+      const int32_t x = p[i], y = p[l];
+      if (y < x) p[i] = y, p[l] = x;
+    }
+  }
+}
+// every stage of the network on p[0 .. m), m <= OL_TILE_MAX (LDS)
+EZD void ol_sort_tile(int32_t* p, uint32_t m, uint32_t t) {
+  for (uint32_t h = 1; h < m; h <<= 1) {
+    ol_step(p, m, h, true, t);
+    __syncthreads();
+    for (uint32_t g = h >> 1; g > 0; g >>= 1) {
+      ol_step(p, m, g, false, t);
+      __syncthreads();
+    }
+  }
+}
+__global__ __launch_bounds__(OL_SORT_BLOCK) void overlap_sort_kernel(OverlapSortArgs a) {
+  __shared__ int32_t tile[OL_TILE_MAX];
+  __shared__ long long off[OL_SORT_ROWS + 1];
+  const uint32_t t = threadIdx.x;
+  const size_t i0 = (size_t)blockIdx.x * OL_SORT_ROWS;
+  if (t <= (uint32_t)OL_SORT_ROWS) off[t] = i0 + t <= (size_t)a.n ? a.offsets[i0 + t] : -1;
+  __syncthreads();
+  for (int r = 0; r < OL_SORT_ROWS; r++) { // (every condition below is uniform across the workgroup)
+    if (i0 + (size_t)r >= (size_t)a.n) break;
+    long long base, len;
+    list_row(off[r], off[r + 1], a.capacity, base, len);
+    if (len <= (long long)(OL_INSERT_MAX > 1 ? OL_INSERT_MAX : 1) || len > (long long)a.n_tri) continue;
+    int32_t* row = a.tri + base;
+    const uint32_t m = (uint32_t)len;
+    if (m <= (uint32_t)OL_TILE_MAX) {
+      for (uint32_t e = t; e < m; e += OL_SORT_BLOCK) tile[e] = row[e];
+      __syncthreads();
+      ol_sort_tile(tile, m, t);
+      for (uint32_t e = t; e < m; e += OL_SORT_BLOCK) row[e] = tile[e];
+      __syncthreads(); // the tile is the next row's
+      continue;
+    }
+    // chunk by chunk: all stages below OL_TILE_MAX (first) or the steps of distance < OL_TILE_MAX of a later stage
+    auto chunks = [&](bool first) {
+      for (uint32_t c = 0; c < m; c += (uint32_t)OL_TILE_MAX) {
+        const uint32_t cm = m - c < (uint32_t)OL_TILE_MAX ? m - c : (uint32_t)OL_TILE_MAX;
+        for (uint32_t e = t; e < cm; e += OL_SORT_BLOCK) tile[e] = row[c + e];
+        __syncthreads();
+        if (first) {
+          ol_sort_tile(tile, cm, t);
+        } else {
+          for (uint32_t g = (uint32_t)OL_TILE_MAX >> 1; g > 0; g >>= 1) {
+            ol_step(tile, cm, g, false, t);
+            __syncthreads();
+          }
+        }
+        for (uint32_t e = t; e < cm; e += OL_SORT_BLOCK) row[c + e] = tile[e];
+        __syncthreads();
+      }
+    };
+    chunks(true);
+    for (uint32_t h = (uint32_t)OL_TILE_MAX; h < m; h <<= 1) {
+      ol_step(row, m, h, true, t);
+      __syncthreads();
+      for (uint32_t g = h >> 1; g >= (uint32_t)OL_TILE_MAX; g >>= 1) {
+        ol_step(row, m, g, false, t);
+        __syncthreads();
+      }
+      chunks(false);
+    }
+  }
 }
 
 // ezrt_obb_overlap_at_device: obb_overlaps for pairs the caller holds -- box i against triangle tri_id[i].  An id outside the scene

@@ -1,10 +1,10 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
 // nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
-// oriented-box, winding-number and plane queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
+// oriented-box, winding-number, plane and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
-// ezrt_plane.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
-// and two small kernels).  A translation unit of its own: none
+// ezrt_plane.h, ezrt_overlap_list.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
 // ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
@@ -24,6 +24,7 @@
 #include "ezrt_obb_overlap.h"
 #include "ezrt_winding.h"
 #include "ezrt_plane.h"
+#include "ezrt_overlap_list.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 
@@ -72,6 +73,49 @@ static void launch_routed(void (*walk)(Args), void (*sweep)(Args), const PointRo
   const dim3 g((unsigned)((n + CP_BLOCK - 1) / CP_BLOCK)), b(CP_BLOCK);
   if (r.walk) hipLaunchKernelGGL(walk, g, b, lds, st, a);
   else hipLaunchKernelGGL(sweep, g, b, 0, st, a);
+}
+
+// ---- overlap lists on device memory (include/ezrt_overlap_list.h): the fill call that the five entry points at the end of this file
+// share.  in0 and in1 are the query's inputs (a null one is skipped), set(a) fills the query's own members of Args, walk and sweep are
+// its list kernel, and lds_div is 2 for slot_walk's column of bare references and 1 for point_walk's, as in the max_k sibling.  One
+// routed kernel on `st`, and on the walk route overlap_sort_kernel behind it; no scratch; checked, launched and ordered against a
+// refit by query_call.
+template <class Args, class Set>
+static int overlap_list_call(const char* name, EzrtScene* s, bool inputs, ezi::DeviceBuf in0, ezi::DeviceBuf in1, int n, const int64_t* offsets,
+                             int64_t capacity, int32_t* tri_id, int32_t* n_found, void* stream, void (*walk)(Args), void (*sweep)(Args),
+                             size_t lds_div, Set set) {
+  return ezi::guarded(name, [&]() -> int {
+    if (!s || !inputs || !offsets || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
+    // (the byte count below must not wrap: a wrapped one would pass the buffer check and leave list_row a capacity that is none)
+    if (capacity > (int64_t)(PTRDIFF_MAX / sizeof(int32_t))) return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
+    if (!tri_id && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL tri_id with capacity > 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, cap = (size_t)capacity;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {in0, in1, {offsets, (N + 1) * sizeof(int64_t)}, {tri_id, cap * sizeof(int32_t)}, {n_found, N * sizeof(int32_t)}}, N, st,
+                      [&](dim3, dim3) {
+      Args a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.offsets = (const long long*)offsets;
+      a.capacity = (long long)capacity;
+      a.tri = tri_id;
+      a.n_found = n_found;
+      a.n = (uint32_t)n;
+      set(a);
+      launch_routed(walk, sweep, r, r.lds / lds_div, N, st, a);
+      // pass 2: the sweep fills in ascending id, and no row longer than OL_INSERT_MAX fits a smaller capacity
+      if (!OL_SKIP_SORT && r.walk && capacity > (OL_INSERT_MAX > 1 ? OL_INSERT_MAX : 1)) {
+        OverlapSortArgs o;
+        o.offsets = a.offsets;
+        o.capacity = a.capacity;
+        o.tri = tri_id;
+        o.n = a.n;
+        o.n_tri = a.sc.n_tri;
+        hipLaunchKernelGGL(overlap_sort_kernel, dim3((unsigned)((N + OL_SORT_ROWS - 1) / OL_SORT_ROWS)), dim3(OL_SORT_BLOCK), 0, st, o);
+      }
+    });
+  });
 }
 
 extern "C" {
@@ -864,6 +908,59 @@ int ezrt_query_capsule_overlap_device(EzrtScene* s, const float* segs6, const fl
       launch_routed(capsule_overlap_kernel<true>, capsule_overlap_kernel<false>, r, r.lds, N, st, a);
     });
   });
+}
+
+// ---- overlap lists on device memory (include/ezrt_overlap_list.h): count (the max_k == 0 calls above), offsets, fill.
+void ezrt_overlap_list_limits(int* insert_max, int* tile_max) {
+  if (insert_max) *insert_max = OL_INSERT_MAX;
+  if (tile_max) *tile_max = OL_TILE_MAX;
+}
+int ezrt_overlap_offsets_device(EzrtScene* s, const int32_t* n_overlap, int n, int64_t* offsets, void* stream) {
+  return ezi::guarded("ezrt_overlap_offsets_device", [&]() -> int {
+    if (!s || !n_overlap || !offsets || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{n_overlap, N * sizeof(int32_t)}, {offsets, (N + 1) * sizeof(int64_t)}}, N, st, [&](dim3, dim3) {
+      hipLaunchKernelGGL(plane_offsets_kernel, dim3(1), dim3(PL_SCAN), 0, st, n_overlap, (uint32_t)n, (long long*)offsets);
+    });
+  });
+}
+int ezrt_query_box_overlap_list_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, int n, const int64_t* offsets, int64_t capacity,
+                                       int32_t* tri_id, int32_t* n_found, void* stream) {
+  const size_t b3 = (size_t)n * 3 * sizeof(float);
+  return overlap_list_call<BoxOverlapListArgs>("ezrt_query_box_overlap_list_device", s, box_lo3 && box_hi3, {box_lo3, b3}, {box_hi3, b3}, n, offsets,
+                                               capacity, tri_id, n_found, stream, box_overlap_list_kernel<true>, box_overlap_list_kernel<false>, 2,
+                                               [&](BoxOverlapListArgs& a) { a.lo = box_lo3, a.hi = box_hi3; });
+}
+int ezrt_query_obb_overlap_list_device(EzrtScene* s, const float* centre3, const float* axes9, int n, const int64_t* offsets, int64_t capacity,
+                                       int32_t* tri_id, int32_t* n_found, void* stream) {
+  const size_t b3 = (size_t)n * 3 * sizeof(float);
+  return overlap_list_call<ObbOverlapListArgs>("ezrt_query_obb_overlap_list_device", s, centre3 && axes9, {centre3, b3}, {axes9, 3 * b3}, n, offsets,
+                                               capacity, tri_id, n_found, stream, obb_overlap_list_kernel<true>, obb_overlap_list_kernel<false>, 2,
+                                               [&](ObbOverlapListArgs& a) { a.centre = centre3, a.axes = axes9; });
+}
+int ezrt_query_tri_overlap_list_device(EzrtScene* s, const float* tris9, int n, const int64_t* offsets, int64_t capacity, int32_t* tri_id,
+                                       int32_t* n_found, void* stream) {
+  return overlap_list_call<TriOverlapListArgs>("ezrt_query_tri_overlap_list_device", s, tris9 != nullptr, {tris9, (size_t)n * 9 * sizeof(float)},
+                                               {nullptr, 0}, n, offsets, capacity, tri_id, n_found, stream, tri_overlap_list_kernel<true>,
+                                               tri_overlap_list_kernel<false>, 2, [&](TriOverlapListArgs& a) { a.tris = tris9; });
+}
+int ezrt_query_self_overlap_list_device(EzrtScene* s, const int32_t* ids, int n, const int64_t* offsets, int64_t capacity, int32_t* tri_id,
+                                        int32_t* n_found, void* stream) {
+  if (s && !ids && n > 0 && (size_t)n > (size_t)s->n_tri)
+    return fail(EZRT_ERR_INVALID, "n exceeds the scene's %d triangles (ids is NULL)", (int)s->n_tri);
+  return overlap_list_call<SelfOverlapListArgs>("ezrt_query_self_overlap_list_device", s, true, {ids, (size_t)n * sizeof(int32_t)}, {nullptr, 0}, n,
+                                                offsets, capacity, tri_id, n_found, stream, self_overlap_list_kernel<true>,
+                                                self_overlap_list_kernel<false>, 2, [&](SelfOverlapListArgs& a) { a.ids = ids; });
+}
+int ezrt_query_capsule_overlap_list_device(EzrtScene* s, const float* segs6, const float* radius, int n, const int64_t* offsets, int64_t capacity,
+                                           int32_t* tri_id, int32_t* n_found, void* stream) {
+  // this walk is point_walk: {lb, ref} entries, the whole column
+  return overlap_list_call<CapsuleOverlapListArgs>("ezrt_query_capsule_overlap_list_device", s, segs6 && radius,
+                                                   {segs6, (size_t)n * 6 * sizeof(float)}, {radius, (size_t)n * sizeof(float)}, n, offsets, capacity,
+                                                   tri_id, n_found, stream, capsule_overlap_list_kernel<true>, capsule_overlap_list_kernel<false>, 1,
+                                                   [&](CapsuleOverlapListArgs& a) { a.segs = segs6, a.radius = radius; });
 }
 
 } // extern "C"

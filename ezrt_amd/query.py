@@ -1,7 +1,7 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
-include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h).
+include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_overlap_list.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -36,6 +36,8 @@ include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, incl
     n_cross = query.plane_count(scene, planes)                                # how many triangles each plane a x + b y + c z = d crosses
     offsets, tri, seg = query.plane_section(scene, planes)                    # ... and all of them with their segments, CSR (include/ezrt_plane.h)
     crosses, side, seg = query.plane_section_at(scene, planes, tri)           # ... the same rule for pairs already held
+    offsets, tri, n_found = query.box_overlap_list(scene, lo, hi)             # EVERY triangle each box touches, CSR (include/ezrt_overlap_list.h)
+    ... and obb_overlap_list, tri_overlap_list, self_overlap_list, capsule_overlap_list: the inputs of the max_k call, all ids
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -75,6 +77,7 @@ SphereCast = collections.namedtuple("SphereCast", "tri t point touching")
 SegmentDistance = collections.namedtuple("SegmentDistance", "tri dist point_query point_scene crosses")
 CapsuleOverlap = collections.namedtuple("CapsuleOverlap", "tri n_overlap")
 ObbOverlap = collections.namedtuple("ObbOverlap", "tri n_overlap")
+OverlapList = collections.namedtuple("OverlapList", "offsets tri n_found")
 
 
 def _scene_lib(scene, abi):
@@ -442,7 +445,8 @@ def box_overlap(scene, lo, hi, max_k=8, count=False, stream=None):
     tree nor the order of the visits.  `count=True` also returns the full number of overlapping triangles, which may exceed max_k;
     with max_k == 0 the call only counts (`tri` is empty and `count` must be True).  A box with a non-finite number or lo > hi on
     some axis overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
-    include/ezrt_box_overlap.h; `box_overlap_at` tests pairs."""
+    include/ezrt_box_overlap.h; `box_overlap_at` tests pairs.  `box_overlap_list` returns every such triangle, not the
+    lowest max_k."""
     if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.BOX_OVERLAP_MAX:
         raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.BOX_OVERLAP_MAX, max_k))
     if max_k == 0 and not count:
@@ -501,7 +505,8 @@ def tri_overlap(scene, tris, max_k=8, count=False, stream=None):
     tree nor the order of the visits.  `count=True` also returns the full number of overlapping triangles, which may exceed max_k;
     with max_k == 0 the call only counts (`tri` is empty and `count` must be True).  A triangle with a non-finite number or with
     collinear or repeated vertices overlaps nothing, on either side -- unlike `box_overlap`, where a degenerate triangle overlaps as
-    the segment or point it is.  The definition, on the bits: include/ezrt_tri_overlap.h; `tri_overlap_at` tests pairs."""
+    the segment or point it is.  The definition, on the bits: include/ezrt_tri_overlap.h; `tri_overlap_at` tests pairs.  `tri_overlap_list` returns every such triangle, not the
+    lowest max_k."""
     if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.TRI_OVERLAP_MAX:
         raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.TRI_OVERLAP_MAX, max_k))
     if max_k == 0 and not count:
@@ -555,7 +560,8 @@ def self_overlap(scene, ids=None, max_k=8, count=False, stream=None):
     rows, and the answer depends on neither the tree nor the order or winding of any triangle.  `count=True` also returns the full
     number of crossing triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count` must be
     True).  An id that is no triangle of the scene, or a triangle that is not live, has an empty row.  The definition, on the bits:
-    include/ezrt_self_overlap.h; `self_overlap_at` tests pairs."""
+    include/ezrt_self_overlap.h; `self_overlap_at` tests pairs.  `self_overlap_list` returns every such triangle, not the
+    lowest max_k."""
     if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.SELF_OVERLAP_MAX:
         raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.SELF_OVERLAP_MAX, max_k))
     if max_k == 0 and not count:
@@ -795,7 +801,8 @@ def capsule_overlap(scene, segs, radius, max_k=8, count=False, stream=None):
     of such triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count` must be True).
     radius == 0 lists the triangles the segment crosses or touches, and any whose nearest point rounds onto it.  A capsule with a
     non-finite number or a negative radius touches nothing.  `segment_distance(scene, segs, radius)` finds a triangle exactly where
-    the count here is > 0.  The definition, on the bits: include/ezrt_segment.h."""
+    the count here is > 0.  The definition, on the bits: include/ezrt_segment.h.  `capsule_overlap_list` returns every such triangle, not the
+    lowest max_k."""
     if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.CAPSULE_OVERLAP_MAX:
         raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.CAPSULE_OVERLAP_MAX, max_k))
     if max_k == 0 and not count:
@@ -842,7 +849,8 @@ def obb_overlap(scene, centre, axes, max_k=8, count=False, stream=None):
     full number of overlapping triangles, which may exceed max_k; with max_k == 0 the call only counts (`tri` is empty and `count`
     must be True).  A box with a non-finite number or without volume (a zero axis, parallel or coplanar axes: give a thin box
     instead) overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
-    include/ezrt_obb_overlap.h; `obb_overlap_at` tests pairs."""
+    include/ezrt_obb_overlap.h; `obb_overlap_at` tests pairs.  `obb_overlap_list` returns every such triangle, not the
+    lowest max_k."""
     if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.OBB_OVERLAP_MAX:
         raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.OBB_OVERLAP_MAX, max_k))
     if max_k == 0 and not count:
@@ -1052,3 +1060,102 @@ def plane_section_at(scene, planes, tri, stream=None):
                                                   P(side.data_ptr()), P(seg.data_ptr()), P(h)))
     _keep((planes, per_entry, tri, crosses, side, seg), ts, planes)
     return crosses.view(torch.bool), side, seg
+
+
+def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
+    """The three steps of include/ezrt_overlap_list.h on the query's stream: count(lib, n_overlap, h) is the sibling's max_k == 0 call,
+    then the offsets, then fill(lib, offsets, capacity, tri, n_found, h).  `inputs` are the caller's tensors, kept alive for the stream."""
+    if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0):
+        raise ValueError("capacity must be None or an int >= 0, not %r" % (capacity,))
+    lib = _scene_lib(scene, _abi.OVERLAP_LIST_ABI)
+    n_overlap = torch.empty((n,), dtype=torch.int32, device=dev)
+    h, ts = _stream(n_overlap, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    n_found = torch.empty((n,), dtype=torch.int32, device=dev) if check else None
+    if n == 0:
+        rows = 0 if capacity is None else capacity
+        with torch.cuda.stream(own):
+            return OverlapList(torch.zeros((1,), dtype=torch.int64, device=dev), torch.full((rows,), -1, dtype=torch.int32, device=dev), n_found)
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    _call(scene, count(lib, P(n_overlap.data_ptr()), P(h)))
+    _call(scene, lib.ezrt_overlap_offsets_device(scene._h, P(n_overlap.data_ptr()), n, P(offsets.data_ptr()), P(h)))
+    with torch.cuda.stream(own):
+        rows = int(offsets[n].item()) if capacity is None else capacity    # None: the one synchronisation, of the query's stream
+        tri = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    _call(scene, fill(lib, P(offsets.data_ptr()), rows, P(tri.data_ptr()) if rows else None, P(n_found.data_ptr()) if check else None, P(h)))
+    _keep(tuple(inputs) + (n_overlap, offsets, tri, n_found), ts, n_overlap)
+    return OverlapList(offsets, tri, n_found)
+
+
+def box_overlap_list(scene, lo, hi, capacity=None, check=False, stream=None):
+    """OverlapList(offsets int64 [n + 1], tri int32 [rows], n_found int32 [n] or None): for the n boxes of `lo`, `hi` (as for
+    `box_overlap`, flattened row-major) EVERY triangle of the scene that touches the box, complete, in CSR form: tri[offsets[i] ..
+    offsets[i + 1]) holds the triangles of box i in ascending id.  The test is `box_overlap`'s: a row's length is its n_overlap, its
+    first 64 entries are its max_k = 64 row, and a box that is not live has an empty row.  `capacity=None` synchronises the stream
+    once to read the total, offsets[n], and returns exactly that many entries.  A given `capacity` never synchronises and returns
+    `capacity` entries: a row is written whole or not at all, rows that end past the capacity are missing (compare offsets[n] with
+    the capacity), and every entry that belongs to no written row keeps tri == -1.  `check=True` also returns the number of
+    triangles the fill pass itself met per box; it equals the row's length unless the scene was refitted between the passes.  The
+    contract: include/ezrt_overlap_list.h."""
+    n = _check_boxes(lo, hi)
+    _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
+    P = C.c_void_p
+    a = (scene._h, P(lo.data_ptr()), P(hi.data_ptr()), n)
+    return _overlap_list(scene, n, lo.device, (lo, hi), capacity, check, stream,
+                         lambda lib, n_overlap, h: lib.ezrt_query_box_overlap_device(*a, 0, None, n_overlap, h),
+                         lambda lib, *out: lib.ezrt_query_box_overlap_list_device(*a, *out))
+
+
+def obb_overlap_list(scene, centre, axes, capacity=None, check=False, stream=None):
+    """OverlapList(offsets, tri, n_found or None): `box_overlap_list` for the oriented boxes of `obb_overlap` -- every triangle that
+    touches each box, in ascending id, CSR.  The contract: include/ezrt_overlap_list.h."""
+    n = _check_obbs(centre, axes)
+    _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
+    P = C.c_void_p
+    a = (scene._h, P(centre.data_ptr()), P(axes.data_ptr()), n)
+    return _overlap_list(scene, n, centre.device, (centre, axes), capacity, check, stream,
+                         lambda lib, n_overlap, h: lib.ezrt_query_obb_overlap_device(*a, 0, None, n_overlap, h),
+                         lambda lib, *out: lib.ezrt_query_obb_overlap_list_device(*a, *out))
+
+
+def tri_overlap_list(scene, tris, capacity=None, check=False, stream=None):
+    """OverlapList(offsets, tri, n_found or None): `box_overlap_list` for the query triangles of `tri_overlap` -- every triangle of
+    the scene that each one crosses or touches, in ascending id, CSR.  The contract: include/ezrt_overlap_list.h."""
+    n = _check_tris(tris)
+    _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
+    a = (scene._h, C.c_void_p(tris.data_ptr()), n)
+    return _overlap_list(scene, n, tris.device, (tris,), capacity, check, stream,
+                         lambda lib, n_overlap, h: lib.ezrt_query_tri_overlap_device(*a, 0, None, n_overlap, h),
+                         lambda lib, *out: lib.ezrt_query_tri_overlap_list_device(*a, *out))
+
+
+def self_overlap_list(scene, ids=None, capacity=None, check=False, stream=None):
+    """OverlapList(offsets, tri, n_found or None): `box_overlap_list` for the triangle ids of `self_overlap` (None: every triangle of
+    the scene, in order, on the current device) -- every OTHER triangle that crosses each one, in ascending id, CSR: every place
+    where the mesh crosses itself.  The lists are symmetric: b is in a's row exactly when a is in b's, so with ids=None a pair
+    appears twice; keep the entries above the row's own id for each pair once.  The contract: include/ezrt_overlap_list.h."""
+    if ids is not None:
+        _tensor("ids", ids, torch.int32)
+    _scene_lib(scene, _abi.SELF_OVERLAP_ABI)
+    if ids is None:
+        n, device = scene.stats()["n_tri"], torch.device("cuda", torch.cuda.current_device())
+    else:
+        n, device = _count(ids, 1, "triangle ids"), ids.device
+    a = (scene._h, C.c_void_p(ids.data_ptr()) if ids is not None else None, n)
+    return _overlap_list(scene, n, device, (ids,), capacity, check, stream,
+                         lambda lib, n_overlap, h: lib.ezrt_query_self_overlap_device(*a, 0, None, n_overlap, h),
+                         lambda lib, *out: lib.ezrt_query_self_overlap_list_device(*a, *out))
+
+
+def capsule_overlap_list(scene, segs, radius, capacity=None, check=False, stream=None):
+    """OverlapList(offsets, tri, n_found or None): `box_overlap_list` for the capsules of `capsule_overlap` -- every triangle within
+    `radius` of each segment, in ascending id, CSR.  The contract: include/ezrt_overlap_list.h."""
+    n = _check_segs(segs)
+    _tensor("radius", radius, torch.float32, segs.shape[:-1], device=segs.device)
+    _scene_lib(scene, _abi.SEGMENT_ABI)
+    P = C.c_void_p
+    a = (scene._h, P(segs.data_ptr()), P(radius.data_ptr()), n)
+    return _overlap_list(scene, n, segs.device, (segs, radius), capacity, check, stream,
+                         lambda lib, n_overlap, h: lib.ezrt_query_capsule_overlap_device(*a, 0, None, n_overlap, h),
+                         lambda lib, *out: lib.ezrt_query_capsule_overlap_list_device(*a, *out))
