@@ -209,6 +209,8 @@ struct Tuning {
                             // (24 until round 4; C2 and C4 -- 16 stack rows, 6 records left at 7 workgroups per CU -- gain 0.6-1.1 % at 7)
   int gen_primary = 1;     // primary rays are generated inside the primary stage's trace and shading kernels (primary_dir) instead of
                            // written to a queue by raygen_kernel (timed pipeline with the 4-wide, eye-relative records only)
+  int gen_whole = 1;       // ... by the whole-frame generator where the call renders a whole frame (one shard, the full rectangle, width and
+                           // height multiples of 16: traceq4_kernel WHOLE, gen_whole_mode); 0: always the general generator
   int anyhit = 1;          // env shadow rays (the even slots of the MIS integrators' bounce stages) stop at their first accepted hit:
                            // the shading stage only asks whether they hit anything (never in the audit routes)
   int semi = 1;            // rays with an exactly-zero direction component: 1 (default) traversed by the 4-wide kernel in the launches that
@@ -279,6 +281,7 @@ const TuningName kTuning[] = {{"megakernel", &Tuning::megakernel, 0, 1},
                               {"debug_force_pending", &Tuning::debug_force_pending, 0, 1 << 20},
                               {"debug_oom_above", &Tuning::debug_oom_above, 0, 1 << 30},
                               {"gen_primary", &Tuning::gen_primary, 0, 1},
+                              {"gen_whole", &Tuning::gen_whole, 0, 1},
                               {"rel_min_records", &Tuning::rel_min_records, 0, 4096},
                               {"min_staged", &Tuning::min_staged, 0, 4096},
                               {"anyhit", &Tuning::anyhit, 0, 1},

@@ -98,6 +98,59 @@ EZD float4 primary_dir(const EzrtRenderParams& p, const int2* blocks, const Fast
   return make_float4(dir.x, dir.y, dir.z, 1.0f);
 }
 
+// ---- The same for a WHOLE FRAME: one shard, the full rectangle, width and height multiples of 16 (gen_whole_mode on the host), which
+// is what every benchmark configuration renders.  Then every pixel is owned (no pixel_owned: nine launch-uniform values), and
+// build_blocks emits the 16x16 blocks in raster order, so the origin of block k is ((k % bw) * 16, (k / bw) * 16), bw = width / 16,
+// instead of a dependent load of blocks[k] in the middle of the trace kernel's refill block.  The frame of a queue position comes out
+// of the scatter's own division: a frame is n_sub whole granules (256 is a multiple of the granule), so slot_to_pixel's division by
+// n_blocks finds the same fk again.  POW2: width and height are powers of two as well -- then so are bw, n_blocks and n_sub, the
+// divisions are shifts (sh_*), and camera_dir multiplies by the exact reciprocals (camera_dir_scaled).
+struct GenWhole {
+  float rot[12];          // EzrtRenderParams::camera_rotate[0..11] (camera_dir reads 0-2, 4-6, 8-10)
+  float sw, sh;           // POW2: 1 / width, 1 / height; else width, height
+  FastDiv div_sub, div_bw; // !POW2: granules per frame, blocks per row
+  uint32_t sh_sub, sh_bw;  // POW2: their base-2 logarithms
+  uint32_t scatter, scatter_shift, frame_first;
+};
+template <bool POW2>
+EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, uint32_t& frame) {
+  const uint32_t sh = g.scatter_shift;
+  const uint32_t q = qslot >> sh;
+  uint32_t fk, r2; // frame of the chunk; granule within the frame after the scatter (queue_to_sample)
+  if (POW2) {
+    fk = q >> g.sh_sub;
+    const uint32_t mask = (1u << g.sh_sub) - 1u;
+    r2 = ((q & mask) * g.scatter) & mask;
+  } else {
+    const uint32_t n_sub = g.div_sub.d;
+    fk = fastdiv(q, g.div_sub);
+    const uint32_t p = (q - fk * n_sub) * g.scatter;
+    r2 = p - fastdiv(p, g.div_sub) * n_sub;
+  }
+  const uint32_t s = (r2 << sh) | (qslot & ((1u << sh) - 1u)); // sample slot within its frame: [block][8x8 sub-block][lane]
+  const uint32_t blk = s >> 8, tid = s & 255u;
+  uint32_t bx, by;
+  if (POW2) {
+    by = blk >> g.sh_bw;
+    bx = blk & ((1u << g.sh_bw) - 1u);
+  } else {
+    by = fastdiv(blk, g.div_bw);
+    bx = blk - by * g.div_bw.d;
+  }
+  const uint32_t wave = tid >> 6, lane = tid & 63u;
+  x = (int)(bx * 16u + (wave & 1u) * 8u + (lane & 7u));
+  y = (int)(by * 16u + (wave >> 1) * 8u + (lane >> 3));
+  frame = g.frame_first + fk;
+}
+template <bool POW2>
+EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot) {
+  int x, y;
+  uint32_t frame, seed;
+  slot_to_pixel_whole<POW2>(g, qslot, x, y, frame);
+  const f3 dir = camera_dir_scaled<POW2>(g.sw, g.sh, g.rot, (uint32_t)x, (uint32_t)y, frame, seed);
+  return make_float4(dir.x, dir.y, dir.z, 1.0f);
+}
+
 template <int INTEG, bool FULLCTR, bool PATHLOG>
 __global__ __launch_bounds__(BLOCK) void trace_kernel(TraceArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_stack[];

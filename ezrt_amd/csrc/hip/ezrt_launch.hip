@@ -11,6 +11,7 @@
 #include "ezrt_wavefront.h"
 #include "ezrt_traceq4.h"
 
+#include <cassert>
 #include <climits>
 
 namespace {
@@ -195,18 +196,54 @@ bool use_wide4(const EzrtScene* s) {
   return s->tune.wide4 && s->n_inner4 > 0 && s->instr == 0 &&
          ((size_t)s->stack_need4 + 4) * BLOCK * sizeof(int) <= 60 * 1024; // stack rows (+ 3 of slack: prune 2) + lane table
 }
+// Which generator the primary stage's launch runs for a call with parameters p (traceq4_kernel WHOLE): 0 the general one; 1 the frame
+// is whole -- one shard, the full rectangle, width and height multiples of 16, so every queue position is an owned pixel-sample and
+// build_blocks' list is the raster of all blocks --; 2 width and height are powers of two besides.  The whole-frame instances exist
+// for the default schedule only (prune 2, no wave log); knob gen_whole = 0 keeps the general instance (A/B, tests).
+int gen_whole_mode(const EzrtScene* s, const EzrtRenderParams& p) {
+  if (!s->tune.gen_whole || prune_mode(s) != 2) return 0;
+  if (p.shard_count > 1 || p.x0 != 0 || p.y0 != 0 || p.x1 != p.width || p.y1 != p.height || p.width % 16 != 0 || p.height % 16 != 0) return 0;
+  if (p.width < 16 || p.height < 16) return 0;
+  const bool pow2 = (p.width & (p.width - 1)) == 0 && (p.height & (p.height - 1)) == 0;
+  return pow2 ? 2 : 1;
+}
+// (asserted where the whole-frame arguments are filled; compiled out with NDEBUG) the block list of a whole frame is the raster
+// slot_to_pixel_whole assumes
+[[maybe_unused]] bool blocks_are_raster(const EzrtScene* s, const EzrtRenderParams& p) {
+  const int bw = p.width / 16, bh = p.height / 16;
+  if (!s->blocks_valid || (int)s->blocks_host.size() != bw * bh) return false;
+  for (int k = 0; k < bw * bh; k++)
+    if (s->blocks_host[k].x != (k % bw) * 16 || s->blocks_host[k].y != (k / bw) * 16) return false;
+  return true;
+}
+int debug_stages_gen_mode(const EzrtScene* s, const EzrtRenderParams& p) { // (debug_stages = 2 runs the LOG instances: general)
+  return s->tune.debug_stages >= 2 ? 0 : gen_whole_mode(s, p);
+}
 // The instances of traceq4_kernel the library ships (round 6: 19, down from 72 -- the register budgets nobody ran, the cross-wave
 // stealing variants and the scattered draw of two-ray queues are gone):
 //   primary stage, rays generated in the launch (REL + GEN): 7 waves per SIMD with the default schedule (prune 2), 6 otherwise
 //   a common origin without generation (gen_primary = 0, audit_via_queue = 2), bounce stages plain / SEMI: 6 waves, prune 0 / 1 / 2
 //   bounce stages drawn in the scattered order (GS): the default schedule only
 //   LOG (debug_stages = 2): the default schedule's five kernels
+//   whole frames (gen_whole_mode; the default schedule without LOG only): the REL + GEN pair again with the whole-frame generator,
+//   and once more with the power-of-two one -- four instances
+// whole: gen_whole_mode of the launch, i.e. which member of TraceQ4Args' generator union fill_traceq4_args filled
 template <bool REL, bool GEN, bool SEMI, bool GS>
-void launch_traceq4_p(int prune, bool log, int wps, dim3 grid, size_t lds, hipStream_t st, const TraceQ4Args& q) {
+void launch_traceq4_p(int prune, bool log, int wps, int whole, dim3 grid, size_t lds, hipStream_t st, const TraceQ4Args& q) {
   const dim3 block(BLOCK);
   constexpr bool HAS_LOG = GEN || !REL; // (the default schedule's kernels)
   if (prune == 2 || GS) {
     if constexpr (REL && GEN) {
+      if (whole && !log) {
+        if (wps >= 7) {
+          if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
+          else hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 1>), grid, block, lds, st, q);
+        } else {
+          if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
+          else hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 1>), grid, block, lds, st, q);
+        }
+        return;
+      }
       if (wps >= 7) {
         if (log) hipLaunchKernelGGL((traceq4_kernel<7, REL, true, 2, GEN, SEMI, GS>), grid, block, lds, st, q);
         else hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS>), grid, block, lds, st, q);
@@ -230,7 +267,7 @@ void launch_traceq4_p(int prune, bool log, int wps, dim3 grid, size_t lds, hipSt
   }
 }
 template <bool REL, bool GEN>
-void launch_traceq4_rel(EzrtScene* s, const TraceCfg& c, const TraceQ4Args& q, hipStream_t st) {
+void launch_traceq4_rel(EzrtScene* s, const TraceCfg& c, const TraceQ4Args& q, int whole, hipStream_t st) {
   const int wps = wps4(s, REL);
   const dim3 grid(c.grid_full);
   int prune = prune_mode(s);
@@ -243,10 +280,10 @@ void launch_traceq4_rel(EzrtScene* s, const TraceCfg& c, const TraceQ4Args& q, h
   const bool semi = !REL && !GEN && (s->tune.semi == 2 || (s->tune.semi == 1 && q.q.rays_per_path == 2u));
   // the scattered draw exists for the default schedule of the bounce stages: pruning with the nearest-first order, one ray per path
   const bool gs = !REL && !GEN && !semi && prune == 2 && q.gscat_shift != 0u;
-  if (REL) launch_traceq4_p<REL, GEN, false, false>(prune, log, wps, grid, c.lds_t, st, q);
-  else if (gs) launch_traceq4_p<false, false, false, true>(prune, log, wps, grid, c.lds_t, st, q);
-  else if (semi) launch_traceq4_p<false, false, true, false>(prune, log, wps, grid, c.lds_t, st, q);
-  else launch_traceq4_p<false, false, false, false>(prune, log, wps, grid, c.lds_t, st, q);
+  if (REL) launch_traceq4_p<REL, GEN, false, false>(prune, log, wps, GEN ? whole : 0, grid, c.lds_t, st, q);
+  else if (gs) launch_traceq4_p<false, false, false, true>(prune, log, wps, 0, grid, c.lds_t, st, q);
+  else if (semi) launch_traceq4_p<false, false, true, false>(prune, log, wps, 0, grid, c.lds_t, st, q);
+  else launch_traceq4_p<false, false, false, false>(prune, log, wps, 0, grid, c.lds_t, st, q);
 }
 constexpr size_t QHEAD_SLOT_WORDS = (size_t)TRACE_HEADS * TRACE_HEAD_STRIDE;
 constexpr size_t QHEADS_WORDS = 81 * QHEAD_SLOT_WORDS; // launch slots of reservation counters: stage b, redo launch 40 + b
@@ -254,22 +291,37 @@ constexpr size_t QHEADS_WORDS = 81 * QHEAD_SLOT_WORDS; // launch slots of reserv
 // t: the stage's queue arguments as for the binary kernel (knobs already filled); rel: 4-wide records translated by
 // t.origin (or NULL)
 // gen (or NULL): the chunk's stage-0 arguments when the launch generates its primary rays itself (needs rel)
+// returns gen_whole_mode: which generator's arguments were filled, and so which instance must run
 // ovf: the scratch set's spill area of the traversal stacks (Pipe::ovf: [grid lanes][max(OVF_CAP, ovf_cap4(s))], indexed with a stride of ovf_cap4(s))
-void fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, const WfArgs* gen, uint32_t* ovf, TraceQ4Args& A) {
-  memset(&A.gen_p, 0, sizeof A.gen_p);
-  A.gen_blocks = nullptr;
-  A.gen_div_blocks = A.gen_div_sub = make_fastdiv(1u);
-  A.gen_scatter = 1u;
-  A.gen_scatter_shift = 6u;
-  A.gen_frame_first = 0u;
-  if (gen) {
-    A.gen_p = gen->p;
-    A.gen_blocks = gen->blocks;
-    A.gen_div_blocks = gen->div_blocks;
-    A.gen_div_sub = gen->div_sub;
-    A.gen_scatter = gen->scatter;
-    A.gen_scatter_shift = gen->scatter_shift;
-    A.gen_frame_first = gen->frame_first;
+int fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, const WfArgs* gen, uint32_t* ovf, TraceQ4Args& A) {
+  static_assert(sizeof(GenWhole) <= sizeof(TraceQ4Args::GenGeneral), "the whole-frame generator's arguments lie inside the general one's");
+  memset(&A.gen, 0, sizeof A.gen);
+  A.gen.div_blocks = A.gen.div_sub = make_fastdiv(1u);
+  A.gen.scatter = 1u;
+  A.gen.scatter_shift = 6u;
+  const int whole = (gen && rel && !t.wave_log) ? gen_whole_mode(s, gen->p) : 0;
+  if (whole) {
+    GenWhole& w = A.gen_whole;
+    const uint32_t bw = (uint32_t)gen->p.width / 16u, n_sub = gen->div_sub.d;
+    assert(blocks_are_raster(s, gen->p));
+    for (int k = 0; k < 12; k++) w.rot[k] = gen->p.camera_rotate[k];
+    w.sw = whole == 2 ? 1.0f / (float)gen->p.width : (float)gen->p.width;
+    w.sh = whole == 2 ? 1.0f / (float)gen->p.height : (float)gen->p.height;
+    w.div_sub = gen->div_sub;
+    w.div_bw = make_fastdiv(bw);
+    w.sh_sub = (uint32_t)__builtin_ctz(n_sub); // (whole == 2: both are powers of two)
+    w.sh_bw = (uint32_t)__builtin_ctz(bw);
+    w.scatter = gen->scatter;
+    w.scatter_shift = gen->scatter_shift;
+    w.frame_first = gen->frame_first;
+  } else if (gen) {
+    A.gen.p = gen->p;
+    A.gen.blocks = gen->blocks;
+    A.gen.div_blocks = gen->div_blocks;
+    A.gen.div_sub = gen->div_sub;
+    A.gen.scatter = gen->scatter;
+    A.gen.scatter_shift = gen->scatter_shift;
+    A.gen.frame_first = gen->frame_first;
   }
   A.q = t;
   A.q.stack_entries = (int32_t)(c4.lds / (BLOCK * sizeof(int)));
@@ -297,13 +349,14 @@ void fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs&
   A.gscat_shift = (!rel && !gen && !t.slot_map && s->tune.bounce_scatter != 0 && t.rays_per_path == 1u) ? 3u : 0u;
   A.handover = (s->tune.handover && t.steal) ? 1u : 0u;
   A.steal_bound = s->tune.steal_bound ? 1u : 0u;
+  return whole;
 }
 void launch_traceq4_cfg(EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, hipStream_t st, const WfArgs* gen, uint32_t* ovf) {
   TraceQ4Args A;
-  fill_traceq4_args(s, c4, t, rel, gen, ovf, A);
-  if (rel && gen) launch_traceq4_rel<true, true>(s, c4, A, st);
-  else if (rel) launch_traceq4_rel<true, false>(s, c4, A, st);
-  else launch_traceq4_rel<false, false>(s, c4, A, st);
+  const int whole = fill_traceq4_args(s, c4, t, rel, gen, ovf, A);
+  if (rel && gen) launch_traceq4_rel<true, true>(s, c4, A, whole, st);
+  else if (rel) launch_traceq4_rel<true, false>(s, c4, A, 0, st);
+  else launch_traceq4_rel<false, false>(s, c4, A, 0, st);
 }
 
 // The redo launch of a stage whose launch was `t`: the rays on t's redo list (exact ties beyond two candidates, rays that are not tame,
@@ -536,6 +589,10 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
     fprintf(stderr, "[ezrt] traceq4 launches: %d stack rows (binary tree depth %d); primary stage %d workgroups/CU, %zu B LDS, %d records staged; "
             "bounce stages %d workgroups/CU, %zu B LDS, %d records staged\n", s->stack_need4, s->depth, cfg4_rel.blocks_per_cu, cfg4_rel.lds_t,
             cfg4_rel.lds_nodes, cfg4_abs.blocks_per_cu, cfg4_abs.lds_t, cfg4_abs.lds_nodes);
+  if (s->tune.debug_stages && wide && gen_primary) {
+    static const char* const kGen[] = {"general", "whole frame", "whole frame, power-of-two"};
+    fprintf(stderr, "[ezrt] primary generator: %s\n", kGen[debug_stages_gen_mode(s, *p)]);
+  }
 
   const Tuning& tu = s->tune;
   const TraceCfg cfg = trace_cfg(s);

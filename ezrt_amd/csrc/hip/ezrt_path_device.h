@@ -32,20 +32,26 @@ EZD uint32_t pixel_seed(uint32_t ix, uint32_t iy, uint32_t frame) { return (ix *
 // the two jitter draws.  ONE definition for every kernel that needs the direction -- the primary stage's trace and shading kernels
 // (primary_dir), trace_kernel and ezrt_camera_rays_device -- so that the ray the trace follows, the ray the shading stage shades
 // and the ray a caller is handed are the same bits.  Of `p` it reads width, height and camera_rotate alone.
-EZD f3 camera_dir(const EzrtRenderParams& p, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t& seed) {
+// POW2: width and height are powers of two and (sw, sh) = (1 / W, 1 / H), both exact: x / W IS x * (1 / W) on the bits then (a scaling
+// by a power of two is exact while nothing becomes subnormal, and the operands here are 2^-25 .. 2^14 in size), so the four correctly
+// rounded divisions -- about eleven instructions each -- are four multiplications.  Otherwise (sw, sh) = (W, H) and the divisions are
+// the reference's.  A template parameter, not a uniform branch: the branch was built and measured in round 4 -- C2 -3.3 %: more launch-
+// invariant values in a kernel at its SGPR limit became three more VGPR spills in the refill block (profiles/r4/rcp_pow2_ab.txt) --
+// while the compile-time form takes the reciprocals IN PLACE of W and H (traceq4_kernel WHOLE == 2).  m: EzrtRenderParams::camera_rotate.
+template <bool POW2>
+EZD f3 camera_dir_scaled(float sw, float sh, const float* m, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t& seed) {
   seed = pixel_seed(ix, iy, frame);
-  const float W = (float)p.width, H = (float)p.height;
-  // (x / W for a power-of-two W IS x * (1 / W) on the bits, and every BASELINE frame is one: the four divisions below as
-  // multiplications behind a uniform branch were built and measured in round 4 -- C2 -3.3 %: four more launch-invariant values
-  // in a kernel at its SGPR limit became three more VGPR spills in the refill block; profiles/r4/rcp_pow2_ab.txt)
-  float pixx = ((float)ix + 0.5f) / W * 2.0f - 1.0f;
-  float pixy = ((float)iy + 0.5f) / H * 2.0f - 1.0f;
-  float aax = (rnd(seed) - 0.5f) / W;
-  float aay = (rnd(seed) - 0.5f) / H;
+  auto over = [](float v, float s) { return POW2 ? v * s : v / s; };
+  float pixx = over((float)ix + 0.5f, sw) * 2.0f - 1.0f;
+  float pixy = over((float)iy + 0.5f, sh) * 2.0f - 1.0f;
+  float aax = over(rnd(seed) - 0.5f, sw);
+  float aay = over(rnd(seed) - 0.5f, sh);
   float vx = pixx + aax, vy = pixy + aay, vz = -1.5f;
-  const float* m = p.camera_rotate;
   f3 dir = mk(m[0] * vx + m[4] * vy + m[8] * vz, m[1] * vx + m[5] * vy + m[9] * vz, m[2] * vx + m[6] * vy + m[10] * vz);
   return normalize(dir);
+}
+EZD f3 camera_dir(const EzrtRenderParams& p, uint32_t ix, uint32_t iy, uint32_t frame, uint32_t& seed) {
+  return camera_dir_scaled<false>((float)p.width, (float)p.height, p.camera_rotate, ix, iy, frame, seed);
 }
 
 // Where a path's ray slots are logged (ezrt_render_paths): the 1 + 2 * max_bounce ids and distances of ONE pixel

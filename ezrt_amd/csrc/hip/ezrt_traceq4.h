@@ -69,11 +69,19 @@ struct TraceQ4Args {
   // x = parent | depth << 24, y = the parent's binary record | (1 << 31 if this node is the RIGHT child); NULL: ties go to the redo list
   const int32_t* tri_leaf;
   const int2* ref_up;
-  // GEN (primary stage only): the queue holds no directions; the ray of queue position q is primary_dir(gen_*, q)
-  EzrtRenderParams gen_p;
-  const int2* gen_blocks;
-  FastDiv gen_div_blocks, gen_div_sub;
-  uint32_t gen_scatter, gen_scatter_shift, gen_frame_first;
+  // GEN (primary stage only): the queue holds no directions; the ray of queue position q is primary_dir(gen.*, q) -- or, in the
+  // whole-frame instances (WHOLE > 0), primary_dir_whole(gen_whole, q), whose few uniforms lie in the same bytes: the struct does
+  // not grow, and an instance loads only the fields it reads
+  struct GenGeneral {
+    EzrtRenderParams p;
+    const int2* blocks;
+    FastDiv div_blocks, div_sub;
+    uint32_t scatter, scatter_shift, frame_first;
+  };
+  union {
+    GenGeneral gen;
+    GenWhole gen_whole;
+  };
   // PRUNE == 2 (nearest-first: no small worst-case bound).  Round 6: the LDS rows of a lane are a RING of stack_cap rows (a power of two:
   // position p lives in row p & (stack_cap - 1)); when fewer than three rows are free after a step -- one step pushes at most three -- the
   // lane's OLDEST (up to four) entries move to its spill area in global memory (ovf: ovf_cap entries per lane) and come back, last in first out, when
@@ -232,9 +240,14 @@ EZD bool tie_precedes(const TraceQ4Args& A, int32_t tri_a, int32_t tri_b, f3 S, 
 // starts from its victim's best_t, which is t_max itself while the victim has pending subtrees (its first hit ends it).  The hit
 // record holds {-1, t_max} or A hit below t_max; rays sent to the redo list come back with their closest hit, and the query's unpack
 // kernel answers t < t_max for all of them.
-template <bool REL, bool LOG, int PRUNE, bool GEN, bool SEMI = false, bool GS = false, bool OCC = false>
+// WHOLE (with GEN): 0 the general generator; 1 the frame is whole (GenWhole: no ownership test, no blocks[] load); 2 ... and its
+// width and height are powers of two (shifts for the index divisions, exact reciprocals for camera_dir's four divisions).
+// The generator is ~400 of this kernel's 1 440 static VALU instructions and all of it sits in the refill block, which also
+// carries most of the kernel's SGPR spills: the fewer launch-uniform values it reads, the fewer v_readlane / v_writelane.
+template <bool REL, bool LOG, int PRUNE, bool GEN, bool SEMI = false, bool GS = false, bool OCC = false, int WHOLE = 0>
 EZD void traceq4_body(const TraceQ4Args& A) {
   static_assert(!GEN || REL, "generated rays start at the launch's uniform origin");
+  static_assert(WHOLE == 0 || GEN, "WHOLE selects a generator");
   static_assert(!OCC || (!REL && !LOG && PRUNE == 2), "occlusion rays carry their own origin and t_max; nearest-first order only");
   extern __shared__ __attribute__((aligned(16))) int lds_stack[];
   const TraceQArgs& a = A.q;
@@ -436,7 +449,8 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           nx_slot = rs;
           if (!REL) nx_o = a.const_origin == 1u ? make_float4(a.origin[0], a.origin[1], a.origin[2], 0.0f) : a.rq.o[rs >> (a.const_origin >> 1)];
           if (GEN) { // generate, and leave the direction in the queue for the stage's shading passes (and a redo launch)
-            nx_d = primary_dir(A.gen_p, A.gen_blocks, A.gen_div_blocks, A.gen_div_sub, A.gen_scatter, A.gen_scatter_shift, A.gen_frame_first, rs);
+            if (WHOLE) nx_d = primary_dir_whole<WHOLE == 2>(A.gen_whole, rs);
+            else nx_d = primary_dir(A.gen.p, A.gen.blocks, A.gen.div_blocks, A.gen.div_sub, A.gen.scatter, A.gen.scatter_shift, A.gen.frame_first, rs);
             a.rq.d[rs] = nx_d;
           } else {
             nx_d = a.rq.d[rs];
@@ -750,9 +764,9 @@ EZD void traceq4_body(const TraceQ4Args& A) {
 }
 
 // GS: queue positions are drawn in the scattered order (TraceQ4Args::gscat_shift; granules of 8 slots)
-template <int WPS, bool REL, bool LOG = false, int PRUNE = 0, bool GEN = false, bool SEMI = false, bool GS = false>
+template <int WPS, bool REL, bool LOG = false, int PRUNE = 0, bool GEN = false, bool SEMI = false, bool GS = false, int WHOLE = 0>
 __global__ __launch_bounds__(BLOCK, WPS) void traceq4_kernel(TraceQ4Args A) {
-  traceq4_body<REL, LOG, PRUNE, GEN, SEMI, GS>(A);
+  traceq4_body<REL, LOG, PRUNE, GEN, SEMI, GS, false, WHOLE>(A);
 }
 // ezrt_query_occluded_device: bounded any-hit rays (OCC above) in the bounce stages' schedule -- own origins, nearest-first order with
 // pruning, scattered draw -- with the NaN watch for rays with a zero direction component (SEMI)
