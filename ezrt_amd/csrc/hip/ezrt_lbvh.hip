@@ -15,6 +15,7 @@
 // subtree sizes (left child = id + 1, right child = id + 1 + size(left)).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -192,7 +193,9 @@ __global__ void k_fit(Fit f) {
     lo = t.first[v0];
     hi = t.last[v0];
   }
-  float b[6] = {3.4e38f, 3.4e38f, 3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f};
+  // +-INFINITY, not a large finite value: the box is the exact min/max for every finite input, coordinates next to FLT_MAX
+  // included.  fminf / fmaxf are minNum / maxNum: a NaN coordinate does not enter the box.
+  float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   for (int k = lo; k <= hi; k++) {
     const float* p = f.tri + (size_t)(uint32_t)f.keys[k] * TRI_F;
     for (int c = 0; c < 3; c++) {

@@ -212,7 +212,7 @@ __global__ void k_gather_tris(const float4* tri_in, const int* order, int n, flo
 
 struct HostNode { // the reference's BVHNode + what the numbering pass needs
   int left = 0, right = 0, n = 0, index = 0;
-  float AA[3], BB[3];
+  float AA[3] = {0.0f, 0.0f, 0.0f}, BB[3] = {0.0f, 0.0f, 0.0f};
   int l = 0, r = 0;
 };
 
@@ -301,7 +301,12 @@ int build_level_sync(bool median, const float* tri, int n_tri, int leaf_n, float
   std::vector<int> box_pos;
   std::vector<int> fresh; // nodes created at the previous level: their boxes are still to be read
   fresh.push_back(0);
-  for (int level = 0; level < 4096; level++) {
+  // The loop runs until no range is left to split.  A split leaves both children non-empty (checked below), so the largest
+  // range of level k holds at most n - k triangles and level n - 1 has nothing to split: n levels always suffice -- identical
+  // triangles and sets whose box has two zero extents (every cost ties, the first candidate wins) really peel one triangle
+  // per level.  Leaving the loop any other way is an error, never a partial tree.
+  bool finished = false;
+  for (int level = 0; level < n; level++) {
     const int n_segs = (int)frontier_node.size();
     segs.resize((size_t)n_segs);
     split_ids.clear();
@@ -350,7 +355,10 @@ int build_level_sync(bool median, const float* tri, int n_tri, int leaf_n, float
         }
       }
     }
-    if (n_split == 0) break;
+    if (n_split == 0) {
+      finished = true;
+      break;
+    }
     SB_TRY(hipMemcpyAsync(d_split_ids.p, split_ids.data(), (size_t)n_split * sizeof(int), hipMemcpyHostToDevice, nullptr));
     SB_TRY(hipMemcpyAsync(d_off_b.p, off_b.data(), (size_t)n_split * sizeof(int), hipMemcpyHostToDevice, nullptr));
     SB_TRY(hipMemcpyAsync(d_off_e.p, off_e.data(), (size_t)n_split * sizeof(int), hipMemcpyHostToDevice, nullptr));
@@ -428,6 +436,11 @@ int build_level_sync(bool median, const float* tri, int n_tri, int leaf_n, float
         continue;
       }
       const Best b = best[(size_t)ks++];
+      if (b.split < nodes[(size_t)id].l || b.split >= nodes[(size_t)id].r) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return ezrt_fail_msg(EZRT_ERR_DEVICE, "split outside its range: the device pass returned no valid candidate");
+      }
       HostNode lc, rc;
       lc.l = nodes[(size_t)id].l;
       lc.r = b.split;
@@ -443,6 +456,13 @@ int build_level_sync(bool median, const float* tri, int n_tri, int leaf_n, float
       next.push_back(nodes[(size_t)id].right);
     }
     frontier_node.swap(next);
+  }
+  if (!finished) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    char buf[128];
+    snprintf(buf, sizeof buf, "ranges left to split after %d levels of %d triangles", n, n);
+    return ezrt_fail_msg(EZRT_ERR_DEVICE, buf);
   }
   hipLaunchKernelGGL(k_gather_tris, dim3((unsigned)(((size_t)n * 9 + TPB - 1) / TPB)), dim3(TPB), 0, nullptr,
                      reinterpret_cast<const float4*>(d_tri.p), d_order[cur].p, n, reinterpret_cast<float4*>(d_tri_out.p));

@@ -13,7 +13,19 @@
  * tri_out must hold n_tri * 36 floats, nodes_out nodes_capacity * 12 floats; 2 * n_tri nodes always
  * suffice.  *n_nodes receives the node count (including node 0), *build_ms (optional) the device
  * time of the build without the host<->device copies.  Returns 0 or a negative EZRT_ERR_* code
- * (message in ezrt_last_error()). */
+ * (message in ezrt_last_error()).  EZRT_ERR_INVALID: a NULL pointer (build_ms excepted), n_tri <= 0, leaf_n < 1 (> 128 for
+ * ezrt_build_lbvh), or nodes_capacity below the tree's node count -- nodes_out is then left untouched.
+ * EZRT_ERR_UNSUPPORTED: n_tri >= 2^24, refused before anything is read.  An entry that fails has written no partial tree.
+ *
+ * Input in contract (tests/test_gpu_build_edges.py):
+ *   ezrt_build_sah, ezrt_build_median  equal the host builder on the bits for ANY input without NaN centroids: +-inf, +-0 and
+ *       subnormal coordinates, coordinates beyond the builder's INF = 114514 and 1145141919 start values, centroid sums that
+ *       overflow, and any depth -- n identical triangles, or triangles whose box has two zero extents, make every SAH cost tie
+ *       and peel one triangle per level (depth n - leaf_n + 1; the level loop runs until no range is left to split, n levels
+ *       at most).  With a NaN centroid the host comparator `a < b` is no strict weak order and the result is unspecified.
+ *   ezrt_build_lbvh  accepts NaN vertices as well.  Its boxes are the exact min/max of the triangles below for every finite
+ *       input, up to FLT_MAX; the fold is minNum/maxNum, so a NaN coordinate does not enter a box, and it orders the zeros:
+ *       a zero lower bound is -0 if any zero below it is, a zero upper bound +0 if any is. */
 #ifndef EZRT_BUILD_H
 #define EZRT_BUILD_H
 

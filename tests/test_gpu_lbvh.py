@@ -22,7 +22,21 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _check_tree(tri_in, tri, nodes, leaf_n):
+def _fold_boxes(q_lo, q_hi, fold_min, fold_max):
+    """min of q_lo [k, 3] and max of q_hi [k, 3] over k.  Where a bound is zero and the operands hold zeros of both signs, numpy
+    leaves the sign of the result open; the device's min / max order them, -0 < +0 (IEEE 754-2019 minimum / maximum, what
+    v_min_f32 / v_max_f32 do): the lower bound is -0 if any zero among them is, the upper bound +0 if any is."""
+    lo, hi = fold_min.reduce(q_lo, axis=0), fold_max.reduce(q_hi, axis=0)
+    any_neg0 = ((q_lo == 0) & np.signbit(q_lo)).any(axis=0)
+    any_pos0 = ((q_hi == 0) & ~np.signbit(q_hi)).any(axis=0)
+    lo = np.where(lo == 0, np.where(any_neg0, np.float32(-0.0), np.float32(0.0)), lo)
+    hi = np.where(hi == 0, np.where(any_pos0, np.float32(0.0), np.float32(-0.0)), hi)
+    return lo, hi
+
+
+def _check_tree(tri_in, tri, nodes, leaf_n, fold_min=np.minimum, fold_max=np.maximum):
+    """fold_min / fold_max: the box fold.  np.fmin / np.fmax (minNum / maxNum) for input with NaN vertices, which the builder
+    keeps out of its boxes (tests/test_gpu_build_edges.py); everything else takes the default."""
     n = tri.shape[0]
     assert np.array_equal(nodes[0], np.array([255, 128, 0, 30, 0, 0, 1, 1, 0, 0, 1, 0], np.float32))   # testNode
     # same triangles, reordered
@@ -50,9 +64,9 @@ def _check_tree(tri_in, tri, nodes, leaf_n):
     for i in range(m - 1, 0, -1):
         if cnt[i] > 0:
             q = P[first[i]:first[i] + cnt[i]].reshape(-1, 3)
-            lo[i], hi[i] = q.min(0), q.max(0)
+            lo[i], hi[i] = _fold_boxes(q, q, fold_min, fold_max)      # (q.min(0), q.max(0) by default)
         else:
-            lo[i], hi[i] = np.minimum(lo[left[i]], lo[right[i]]), np.maximum(hi[left[i]], hi[right[i]])
+            lo[i], hi[i] = _fold_boxes(lo[[left[i], right[i]]], hi[[left[i], right[i]]], fold_min, fold_max)
     assert np.array_equal(_bits(nodes[1:, 6:9]), _bits(lo[1:])) and np.array_equal(_bits(nodes[1:, 9:12]), _bits(hi[1:]))
 
 
