@@ -304,6 +304,27 @@ PLANE_ABI = {
 PLANE_TILE = 64  # planes per workgroup (ezrt_point_queries.h: PL_TILE)
 
 
+# stream-ordered plane loops on device memory, libezrt_hip.so only (include/ezrt_plane_loops.h); pointers are device addresses
+PLANE_LOOPS_ABI = {
+    # capacity: the bytes of `work` (no device work)
+    "ezrt_plane_loops_work_bytes": (C.c_size_t, [C.c_int64]),
+    # tile_rows_max: the limit as compiled (a host pointer; no device work)
+    "ezrt_plane_loops_limits": (None, [C.c_void_p]),
+    # s, offsets, n, seg, capacity, tile_rows, next, order, plane_loops, loop_capacity, loop_offsets, closed, work, work_bytes, stream
+    "ezrt_plane_loops_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
+
+def plane_loops_limits():
+    """tile_rows_max of the loaded HIP library: the longest plane that is chained in the LDS of one workgroup
+    (include/ezrt_plane_loops.h).  No device work."""
+    lib = _declare(load_hip(), PLANE_LOOPS_ABI)
+    a = C.c_int(-1)
+    lib.ezrt_plane_loops_limits(C.byref(a))
+    return a.value
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -401,7 +422,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

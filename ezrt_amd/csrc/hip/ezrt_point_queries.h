@@ -41,6 +41,11 @@
 //   plane_total_kernel               part's rows summed to n_cross
 //   plane_offsets_kernel             the exclusive prefix sum of n_cross
 //   plane_at_kernel                  the plane rule for pairs the caller holds
+//   loops_chain_kernel<LDS>          a workgroup per plane: the bit-exact join of a section's rows and their ranking into chains,
+//                                    in LDS or in the caller's work memory (include/ezrt_plane_loops.h)
+//   loops_scan_kernel                an exclusive prefix sum in place (the planes' loop counts, the loops' lengths)
+//   loops_length_kernel              the tail of every chain writes its loop's length
+//   loops_scatter_kernel             order, next, loop_offsets and closed
 #pragma once
 #include "ezrt_device.h"
 #include "ezrt_records.h"
@@ -1538,6 +1543,347 @@ __global__ __launch_bounds__(256) void plane_at_kernel(const float4* tri_geom, i
   if (seg) {
     float* out = seg + (size_t)i * 6;
     out[0] = q0.x, out[1] = q0.y, out[2] = q0.z, out[3] = q1.x, out[4] = q1.y, out[5] = q1.z;
+  }
+}
+
+// ---- plane loops (include/ezrt_plane_loops.h): the rows of a section chained into polylines, on bits alone.
+//
+// One workgroup per plane.  loops_plane is the whole of a plane's join (L4) and ranking (L5) on LOCAL row indices 0 .. m - 1 (int32:
+// m <= n_tri) over a LoopsStore of arrays that loops_chain_kernel<true> places in LDS (planes of at most `tile` rows) and
+// loops_chain_kernel<false> in the caller's `work`, at the plane's own rows of capacity-long arrays (2 x rows of the table's).  The
+// workgroup leaves nxt, prd, hd (the head; -1 for a degenerate row), ps (pos) and hl (a head's number among its plane's heads) in
+// `work` and the plane's number of loops in plane_loops[i], which loops_scan_kernel then sums in place.  loops_length_kernel has the
+// tail of every chain write its loop's length, loops_scan_kernel sums those, and loops_scatter_kernel writes the outputs.
+//
+// Termination and bounds, whatever `offsets` holds (two chained planes of a garbage array may overlap, and then share rows of
+// `work`): every probe loop runs at most T times, every list walk at most m times, every round loop K times, and every index read
+// back from a store is used only if it is below m (loops_in); every store to an output is behind a check of its index.
+// The LDS route's 512 threads are measured (profiles/r27/plane_loops_variants.txt): 256 lose 2 to 18 % on every set, 1024 lose 22 to
+// 30 % at 10 000 planes.
+constexpr int LP_TILE_MAX = 1024;                       // rows of a plane that is chained in LDS: 11 ints each, 44 KiB of the launch's 64
+constexpr int LP_LDS_BLOCK = 512, LP_GLB_BLOCK = 1024;  // threads of the two routes' workgroups
+constexpr int LP_BLOCK = 256, LP_SCAN = 1024;
+struct LoopsArgs {
+  const long long* offsets; // n + 1
+  const uint32_t* seg;      // capacity x 6: the bits
+  long long capacity;
+  int32_t n_tri;
+  uint32_t n;
+  uint32_t tile;            // the effective tile_rows
+  // work, capacity ints each (rep, oh, ih: 2 x capacity); lofs: capacity + 1
+  int32_t *nxt, *prd, *hd, *ps, *hl, *lo, *li, *ro, *rep, *oh, *ih;
+  long long* lofs;
+  // outputs
+  long long *next, *order, *plane_loops, *loop_offsets;
+  long long loop_capacity;
+  uint8_t* closed;
+};
+// the arrays of one plane: rep / oh / ih are the table (T = 2 m slots: representative row, head of the OUT list, head of the IN
+// list), lo / li the links of the two lists, ro a row's rank among the OUT rows of its key.  The ranking's double buffers lie over
+// the table, which is dead by then: {a, d} = {rep, rep + m} and {oh, oh + m}.
+struct LoopsStore {
+  int32_t *nxt, *prd, *lo, *li, *ro, *rep, *oh, *ih;
+};
+// L2: the rows [o0, o0 + m) of plane i, or false
+__device__ inline bool loops_range(const LoopsArgs& a, uint32_t i, long long& o0, uint32_t& m) {
+  const long long lo = a.offsets[i], hi = a.offsets[i + 1];
+  if (lo < 0 || hi < lo || hi > a.capacity || hi - lo > (long long)a.n_tri) return false;
+  o0 = lo, m = (uint32_t)(hi - lo);
+  return true;
+}
+__device__ inline bool loops_in(int32_t x, uint32_t m) { return (uint32_t)x < m; }
+// A load of a table word that atomics have written (rep, oh, ih): an atomic load itself, so that the global route does not read a
+// line of the vector cache that the atomics, which are performed in L2, have gone past.  EVERY OTHER word of a LoopsStore on the
+// global route (lo, li, ro, nxt, prd, and the ranking buffers, which reuse words of rep and oh that atomics modified last) is a plain
+// store read by other waves with plain loads after __syncthreads.  That is sound for ONE reason: a plane is one workgroup, a
+// workgroup's waves share their CU's vector cache, which sees its own CU's stores, and the barrier fences at workgroup scope.  It
+// does not hold in threadgroup-split mode (the library is not built for it), and it would break silently if a plane were ever split
+// over several workgroups: such a change has to make these loads and stores agent-scope atomics, or put launches between the phases.
+__device__ inline int32_t loops_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// a mix of the 12 bytes (the finaliser of MurmurHash3): coordinates on a coarse grid differ in few, high bits
+__device__ inline uint32_t loops_hash(uint32_t x, uint32_t y, uint32_t z) {
+  uint32_t h = x * 0x9E3779B1u;
+  h = (h << 13 | h >> 19) ^ (y * 0x85EBCA77u);
+  h = (h << 13 | h >> 19) ^ (z * 0xC2B2AE3Du);
+  h ^= h >> 16, h *= 0x85EBCA6Bu, h ^= h >> 13, h *= 0xC2B2AE35u, h ^= h >> 16;
+  return h;
+}
+// K rounds of doubling on the buffers {ac, dc} -> {an, dn} and back: a' = a[a], d' = MIN ? min(d, d[a]) : d + d[a].  Ends behind a
+// barrier with the result in {ac, dc} (the pointers are swapped with the rounds).
+template <int B, bool MIN>
+__device__ inline void loops_rounds(int K, uint32_t m, int32_t*& ac, int32_t*& dc, int32_t*& an, int32_t*& dn) {
+  for (int k = 0; k < K; k++) {
+    for (uint32_t r = threadIdx.x; r < m; r += B) {
+      int32_t x = ac[r];
+      if (!loops_in(x, m)) x = (int32_t)r;
+      const int32_t v = dc[r], w = dc[x], y = ac[x];
+      an[r] = loops_in(y, m) ? y : (int32_t)r;
+      dn[r] = MIN ? (w < v ? w : v) : (int32_t)((uint32_t)v + (uint32_t)w);
+    }
+    __syncthreads();
+    int32_t* t0 = ac;
+    ac = an, an = t0;
+    int32_t* t1 = dc;
+    dc = dn, dn = t1;
+  }
+}
+template <int B>
+__device__ inline void loops_plane(const LoopsArgs& a, const LoopsStore& s, uint32_t i, long long o0, uint32_t m, int32_t* sc /* LDS, B ints */) {
+  const uint32_t t = threadIdx.x, T = 2 * m;
+  const uint32_t* seg = a.seg + (size_t)o0 * 6;
+  int32_t *hd = a.hd + o0, *ps = a.ps + o0, *hl = a.hl + o0;
+  for (uint32_t e = t; e < T; e += B) s.rep[e] = -1, s.oh[e] = -1, s.ih[e] = -1;
+  __syncthreads();
+  // JOIN 1: every non-degenerate row claims or finds the slot of its q0 and pushes itself onto the slot's OUT list
+  for (uint32_t r = t; r < m; r += B) {
+    const uint32_t* q = seg + (size_t)r * 6;
+    const uint32_t x0 = q[0], x1 = q[1], x2 = q[2];
+    s.prd[r] = -1;
+    if (x0 == q[3] && x1 == q[4] && x2 == q[5]) { // L3
+      s.nxt[r] = -2;
+      continue;
+    }
+    s.nxt[r] = -1;
+    uint32_t p = loops_hash(x0, x1, x2) % T;
+    int32_t slot = -1;
+    for (uint32_t k = 0; k < T; k++) {
+      const int32_t old = atomicCAS(&s.rep[p], -1, (int32_t)r);
+      if (old == -1) {
+        slot = (int32_t)p;
+        break;
+      }
+      if (loops_in(old, m)) {
+        const uint32_t* o = seg + (size_t)old * 6;
+        if (o[0] == x0 && o[1] == x1 && o[2] == x2) {
+          slot = (int32_t)p;
+          break;
+        }
+      }
+      p = p + 1 == T ? 0 : p + 1;
+    }
+    s.ro[r] = slot; // (the rank takes its place in the next phase)
+    s.lo[r] = slot >= 0 ? atomicExch(&s.oh[slot], (int32_t)r) : -1;
+  }
+  __syncthreads();
+  // JOIN 2: the rank among the OUT rows of the key; the slot of q1, if a q0 has it, and a push onto its IN list
+  for (uint32_t r = t; r < m; r += B) {
+    if (s.nxt[r] == -2) continue;
+    const int32_t slot = s.ro[r];
+    int32_t rank = 0;
+    if (loops_in(slot, T)) {
+      int32_t e = loops_ld(&s.oh[slot]);
+      for (uint32_t k = 0; k < m && loops_in(e, m); k++) {
+        rank += e < (int32_t)r;
+        e = s.lo[e];
+      }
+    }
+    s.ro[r] = rank;
+    const uint32_t* q = seg + (size_t)r * 6;
+    const uint32_t x3 = q[3], x4 = q[4], x5 = q[5];
+    uint32_t p = loops_hash(x3, x4, x5) % T;
+    int32_t found = -1;
+    for (uint32_t k = 0; k < T; k++) {
+      const int32_t v = loops_ld(&s.rep[p]);
+      if (v == -1) break;
+      if (loops_in(v, m)) {
+        const uint32_t* o = seg + (size_t)v * 6;
+        if (o[0] == x3 && o[1] == x4 && o[2] == x5) {
+          found = (int32_t)p;
+          break;
+        }
+      }
+      p = p + 1 == T ? 0 : p + 1;
+    }
+    s.nxt[r] = found; // (the slot, until the next phase replaces it by the successor)
+    s.li[r] = found >= 0 ? atomicExch(&s.ih[found], (int32_t)r) : -1;
+  }
+  __syncthreads();
+  // JOIN 3: L4 -- the rank j among the IN rows of the key, and the OUT row of rank j
+  for (uint32_t r = t; r < m; r += B) {
+    const int32_t slot = s.nxt[r];
+    if (slot < 0) continue; // degenerate, or no q0 has this q1
+    int32_t o = -1;
+    if (loops_in(slot, T)) {
+      int32_t j = 0, e = loops_ld(&s.ih[slot]);
+      for (uint32_t k = 0; k < m && loops_in(e, m); k++) {
+        j += e < (int32_t)r;
+        e = s.li[e];
+      }
+      e = loops_ld(&s.oh[slot]);
+      for (uint32_t k = 0; k < m && loops_in(e, m); k++) {
+        if (s.ro[e] == j) {
+          o = e;
+          break;
+        }
+        e = s.lo[e];
+      }
+    }
+    s.nxt[r] = o;
+    if (o >= 0) s.prd[o] = (int32_t)r;
+  }
+  __syncthreads();
+  // RANKING 1: pointer jumping along the predecessor; a head points at itself with distance 0
+  int K = 0;
+  while ((1u << K) < m) K++;
+  int32_t *ac = s.rep, *dc = s.rep + m, *an = s.oh, *dn = s.oh + m;
+  for (uint32_t r = t; r < m; r += B) {
+    const int32_t p = s.prd[r];
+    ac[r] = loops_in(p, m) ? p : (int32_t)r;
+    dc[r] = loops_in(p, m) ? 1 : 0;
+  }
+  __syncthreads();
+  loops_rounds<B, false>(K, m, ac, dc, an, dn);
+  // a row whose pointer has not reached a head lies on a cycle (hd = -2 until ranking 3); a degenerate row gets -1
+  int cyc = 0;
+  for (uint32_t r = t; r < m; r += B) {
+    const int32_t h = ac[r];
+    const bool on = s.nxt[r] != -2 && loops_in(h, m) && s.prd[h] >= 0;
+    hd[r] = s.nxt[r] == -2 ? -1 : (on ? -2 : h);
+    ps[r] = dc[r];
+    cyc |= on;
+  }
+  if (__syncthreads_or(cyc)) {
+    // RANKING 2: min-doubling along next gives every row of a cycle the cycle's lowest row; the others stand still
+    for (uint32_t r = t; r < m; r += B) {
+      const int32_t x = s.nxt[r];
+      ac[r] = hd[r] == -2 && loops_in(x, m) ? x : (int32_t)r;
+      dc[r] = (int32_t)r;
+    }
+    __syncthreads();
+    loops_rounds<B, true>(K, m, ac, dc, an, dn);
+    // RANKING 3: the cycle is cut before its lowest row and ranked like a path; the rows of paths are fixed points of the rounds
+    for (uint32_t r = t; r < m; r += B) {
+      const int32_t low = dc[r], p = s.prd[r];
+      if (hd[r] == -2) {
+        const bool head = low == (int32_t)r || !loops_in(p, m);
+        ac[r] = head ? (int32_t)r : p;
+        dc[r] = head ? 0 : 1;
+      } else {
+        ac[r] = hd[r] >= 0 ? hd[r] : (int32_t)r;
+        dc[r] = hd[r] >= 0 ? ps[r] : 0;
+      }
+    }
+    __syncthreads();
+    loops_rounds<B, false>(K, m, ac, dc, an, dn);
+    for (uint32_t r = t; r < m; r += B)
+      if (hd[r] == -2) hd[r] = ac[r], ps[r] = dc[r];
+  }
+  // the links leave the store (the LDS route's is gone with the workgroup)
+  for (uint32_t r = t; r < m; r += B) a.nxt[o0 + r] = s.nxt[r], a.prd[o0 + r] = s.prd[r];
+  __syncthreads();
+  // COMPACTION 1: the plane's heads numbered in ascending row -- every thread a contiguous chunk, the chunk sums scanned in LDS
+  const uint32_t chunk = (m + B - 1) / B, c0 = t * chunk < m ? t * chunk : m, c1 = c0 + chunk < m ? c0 + chunk : m;
+  int32_t cnt = 0;
+  for (uint32_t r = c0; r < c1; r++) cnt += hd[r] == (int32_t)r;
+  sc[t] = cnt;
+  __syncthreads();
+  for (uint32_t o = 1; o < (uint32_t)B; o <<= 1) {
+    const int32_t add = t >= o ? sc[t - o] : 0;
+    __syncthreads();
+    sc[t] += add;
+    __syncthreads();
+  }
+  int32_t run = sc[t] - cnt;
+  for (uint32_t r = c0; r < c1; r++)
+    if (hd[r] == (int32_t)r) hl[r] = run++;
+  if (t == (uint32_t)B - 1) a.plane_loops[i] = sc[t];
+}
+// LDS: the planes of at most a.tile rows, and the planes without loops (not chained, or empty); otherwise the longer planes
+template <bool LDS>
+__global__ __launch_bounds__(LDS ? LP_LDS_BLOCK : LP_GLB_BLOCK) void loops_chain_kernel(LoopsArgs a) {
+  constexpr int B = LDS ? LP_LDS_BLOCK : LP_GLB_BLOCK;
+  __shared__ int32_t sc[B];
+  __shared__ int32_t tile[LDS ? 11 * LP_TILE_MAX : 1];
+  const uint32_t i = blockIdx.x;
+  long long o0 = 0;
+  uint32_t m = 0;
+  const bool ok = loops_range(a, i, o0, m);
+  if (!ok || m == 0) {
+    if (LDS && threadIdx.x == 0) a.plane_loops[i] = 0;
+    return;
+  }
+  if ((m <= a.tile) != LDS) return;
+  LoopsStore s;
+  if (LDS) {
+    s.nxt = tile, s.prd = tile + m, s.lo = tile + 2 * m, s.li = tile + 3 * m, s.ro = tile + 4 * m;
+    s.rep = tile + 5 * m, s.oh = tile + 7 * m, s.ih = tile + 9 * m;
+  } else {
+    s.nxt = a.nxt + o0, s.prd = a.prd + o0, s.lo = a.lo + o0, s.li = a.li + o0, s.ro = a.ro + o0;
+    s.rep = a.rep + 2 * o0, s.oh = a.oh + 2 * o0, s.ih = a.ih + 2 * o0;
+  }
+  loops_plane<B>(a, s, i, o0, m, sc);
+}
+// x[0 .. n) -> its exclusive prefix sum IN PLACE, the total in x[n]; n = min(*n_dev, n_max) where n_dev is given, else n_max.  ONE
+// workgroup, as plane_offsets_kernel: n is a number of planes or of loops, small beside the rows.
+__global__ __launch_bounds__(LP_SCAN) void loops_scan_kernel(long long* x, const long long* n_dev, long long n_max) {
+  __shared__ long long sums[LP_SCAN];
+  const uint32_t t = threadIdx.x;
+  long long nn = n_dev ? *n_dev : n_max;
+  nn = nn < 0 ? 0 : (nn > n_max ? n_max : nn);
+  const unsigned long long n = (unsigned long long)nn, chunk = (n + LP_SCAN - 1) / LP_SCAN;
+  const unsigned long long lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+  long long s = 0;
+  for (unsigned long long i = lo; i < hi; i++) s += x[i];
+  sums[t] = s;
+  __syncthreads();
+  for (uint32_t o = 1; o < LP_SCAN; o <<= 1) {
+    const long long add = t >= o ? sums[t - o] : 0;
+    __syncthreads();
+    sums[t] += add;
+    __syncthreads();
+  }
+  long long run = sums[t] - s;
+  for (unsigned long long i = lo; i < hi; i++) {
+    const long long v = x[i];
+    x[i] = run;
+    run += v;
+  }
+  if (t == LP_SCAN - 1) x[n] = sums[t];
+}
+// the number of a row's loop, or -1: plane_loops[i] (summed by now) + the head's number in its plane
+__device__ inline long long loops_id(const LoopsArgs& a, long long first, long long o0, uint32_t m, int32_t h) {
+  if (!loops_in(h, m)) return -1;
+  const long long l = first + a.hl[o0 + h];
+  return l >= 0 && l < a.capacity ? l : -1;
+}
+// COMPACTION 2: the tail of a path (no successor) and of a cut cycle (its successor is its head) is at pos = length - 1
+__global__ __launch_bounds__(LP_BLOCK) void loops_length_kernel(LoopsArgs a) {
+  const uint32_t i = blockIdx.x;
+  long long o0 = 0;
+  uint32_t m = 0;
+  if (!loops_range(a, i, o0, m)) return;
+  const long long first = a.plane_loops[i];
+  for (uint32_t r = threadIdx.x; r < m; r += LP_BLOCK) {
+    const int32_t h = a.hd[o0 + r], x = a.nxt[o0 + r];
+    if (h < 0 || (x >= 0 && x != h)) continue;
+    const long long l = loops_id(a, first, o0, m, h);
+    if (l >= 0) a.lofs[l] = (long long)a.ps[o0 + r] + 1;
+  }
+}
+// COMPACTION 3: order, next, loop_offsets and closed
+__global__ __launch_bounds__(LP_BLOCK) void loops_scatter_kernel(LoopsArgs a) {
+  const uint32_t i = blockIdx.x;
+  if (i == 0 && threadIdx.x == 0) {
+    const long long L = a.plane_loops[a.n];
+    if (L >= 0 && L <= a.loop_capacity && L <= a.capacity) a.loop_offsets[L] = a.lofs[L];
+  }
+  long long o0 = 0;
+  uint32_t m = 0;
+  if (!loops_range(a, i, o0, m)) return;
+  const long long first = a.plane_loops[i];
+  for (uint32_t r = threadIdx.x; r < m; r += LP_BLOCK) {
+    const long long g = o0 + r;
+    const int32_t h = a.hd[g], x = a.nxt[g];
+    if (a.next) a.next[g] = loops_in(x, m) ? o0 + x : -1;
+    if (h < 0) continue;
+    const long long l = loops_id(a, first, o0, m, h);
+    if (l < 0) continue;
+    const long long at = a.lofs[l], k = at + a.ps[g];
+    if (k >= 0 && k < a.capacity) a.order[k] = g;
+    if (h == (int32_t)r && l < a.loop_capacity) {
+      a.loop_offsets[l] = at;
+      if (a.closed) a.closed[l] = a.prd[g] >= 0 ? 1 : 0;
+    }
   }
 }
 

@@ -1,9 +1,9 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
 // nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
-// oriented-box, winding-number, plane and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
+// oriented-box, winding-number, plane, plane-loop and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
-// ezrt_plane.h, ezrt_overlap_list.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -24,6 +24,7 @@
 #include "ezrt_obb_overlap.h"
 #include "ezrt_winding.h"
 #include "ezrt_plane.h"
+#include "ezrt_plane_loops.h"
 #include "ezrt_overlap_list.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
@@ -668,6 +669,59 @@ int ezrt_plane_section_at_device(EzrtScene* s, const float* planes4, const int32
     return query_call(s, {{planes4, N * 4 * sizeof(float)}, {tri_id, N * sizeof(int32_t)}, {crosses, N}, {side, N * 3},
                           {seg, N * 6 * sizeof(float)}}, N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(plane_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, planes4, tri_id, (uint32_t)n, crosses, side, seg);
+    });
+  });
+}
+
+// ---- plane loops on device memory (include/ezrt_plane_loops.h): six launches on `st` -- the two routes of loops_chain_kernel, the
+// planes' scan, the lengths, the loops' scan, the scatter -- over the caller's `work`; checked, launched and ordered against a refit
+// by query_call.  `work` is lofs (capacity + 1 int64) and then 14 x capacity ints: nxt prd hd ps hl lo li ro, and rep oh ih twice as long.
+size_t ezrt_plane_loops_work_bytes(int64_t capacity) {
+  const size_t cap = capacity > 0 ? (size_t)capacity : 0;
+  return cap * (sizeof(int64_t) + 14 * sizeof(int32_t)) + sizeof(int64_t);
+}
+void ezrt_plane_loops_limits(int* tile_rows_max) {
+  if (tile_rows_max) *tile_rows_max = LP_TILE_MAX;
+}
+int ezrt_plane_loops_device(EzrtScene* s, const int64_t* offsets, int n, const float* seg, int64_t capacity, int tile_rows, int64_t* next,
+                            int64_t* order, int64_t* plane_loops, int64_t loop_capacity, int64_t* loop_offsets, uint8_t* closed, void* work,
+                            size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_plane_loops_device", [&]() -> int {
+    if (!s || !offsets || !plane_loops || !loop_offsets || !work || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (capacity < 0 || loop_capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0 or loop_capacity < 0");
+    if (tile_rows < 0) return fail(EZRT_ERR_INVALID, "tile_rows < 0");
+    // (the byte counts below must not wrap)
+    if (capacity > (int64_t)(PTRDIFF_MAX / 64) || loop_capacity > (int64_t)(PTRDIFF_MAX / 16))
+      return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
+    if ((!seg || !order) && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL seg or order with capacity > 0");
+    if (work_bytes < ezrt_plane_loops_work_bytes(capacity)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_plane_loops_work_bytes(capacity)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, cap = (size_t)capacity, lcap = (size_t)loop_capacity;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{offsets, (N + 1) * sizeof(int64_t)}, {seg, cap * 6 * sizeof(float)}, {next, cap * sizeof(int64_t)},
+                          {order, cap * sizeof(int64_t)}, {plane_loops, (N + 1) * sizeof(int64_t)}, {loop_offsets, (lcap + 1) * sizeof(int64_t)},
+                          {closed, lcap}, {work, ezrt_plane_loops_work_bytes(capacity)}}, N, st, [&](dim3, dim3) {
+      LoopsArgs a{};
+      a.offsets = (const long long*)offsets;
+      a.seg = (const uint32_t*)seg;
+      a.capacity = (long long)capacity;
+      a.n_tri = (int32_t)s->n_tri;
+      a.n = (uint32_t)n;
+      a.tile = (uint32_t)(tile_rows == 0 || tile_rows > LP_TILE_MAX ? LP_TILE_MAX : tile_rows);
+      a.lofs = (long long*)work;
+      int32_t* w = (int32_t*)(a.lofs + cap + 1);
+      a.nxt = w, a.prd = w + cap, a.hd = w + 2 * cap, a.ps = w + 3 * cap, a.hl = w + 4 * cap, a.lo = w + 5 * cap, a.li = w + 6 * cap;
+      a.ro = w + 7 * cap, a.rep = w + 8 * cap, a.oh = w + 10 * cap, a.ih = w + 12 * cap;
+      a.next = (long long*)next, a.order = (long long*)order, a.plane_loops = (long long*)plane_loops;
+      a.loop_offsets = (long long*)loop_offsets, a.loop_capacity = (long long)loop_capacity, a.closed = closed;
+      const dim3 g((unsigned)n);
+      hipLaunchKernelGGL((loops_chain_kernel<true>), g, dim3(LP_LDS_BLOCK), 0, st, a);
+      hipLaunchKernelGGL((loops_chain_kernel<false>), g, dim3(LP_GLB_BLOCK), 0, st, a);
+      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.plane_loops, (const long long*)nullptr, (long long)n);
+      hipLaunchKernelGGL(loops_length_kernel, g, dim3(LP_BLOCK), 0, st, a);
+      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.lofs, (const long long*)(a.plane_loops + n), (long long)capacity);
+      hipLaunchKernelGGL(loops_scatter_kernel, g, dim3(LP_BLOCK), 0, st, a);
     });
   });
 }

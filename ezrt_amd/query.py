@@ -1,7 +1,8 @@
 """Stream-ordered ray and point queries on device tensors (include/ezrt_query.h, include/ezrt_surface.h, include/ezrt_multihit.h,
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
-include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_overlap_list.h).
+include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
+include/ezrt_overlap_list.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -36,6 +37,9 @@ include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, incl
     n_cross = query.plane_count(scene, planes)                                # how many triangles each plane a x + b y + c z = d crosses
     offsets, tri, seg = query.plane_section(scene, planes)                    # ... and all of them with their segments, CSR (include/ezrt_plane.h)
     crosses, side, seg = query.plane_section_at(scene, planes, tri)           # ... the same rule for pairs already held
+    plane_loops, loop_offsets, closed, row, tri, seg = query.plane_loops(scene, planes)   # ... chained into polylines (include/ezrt_plane_loops.h)
+    loops = query.plane_loops_of(scene, offsets, seg)                         # ... for a section already held: next, order, CSR of the loops
+    length, area = query.loop_measures(loops, planes)                         # ... perimeter and signed area of every loop (float64)
     offsets, tri, n_found = query.box_overlap_list(scene, lo, hi)             # EVERY triangle each box touches, CSR (include/ezrt_overlap_list.h)
     ... and obb_overlap_list, tri_overlap_list, self_overlap_list, capsule_overlap_list: the inputs of the max_k call, all ids
 
@@ -78,6 +82,8 @@ SegmentDistance = collections.namedtuple("SegmentDistance", "tri dist point_quer
 CapsuleOverlap = collections.namedtuple("CapsuleOverlap", "tri n_overlap")
 ObbOverlap = collections.namedtuple("ObbOverlap", "tri n_overlap")
 OverlapList = collections.namedtuple("OverlapList", "offsets tri n_found")
+PlaneLoops = collections.namedtuple("PlaneLoops", "plane_loops loop_offsets closed row tri seg")
+PlaneLoopsOf = collections.namedtuple("PlaneLoopsOf", "next order plane_loops loop_offsets closed")
 
 
 def _scene_lib(scene, abi):
@@ -1060,6 +1066,129 @@ def plane_section_at(scene, planes, tri, stream=None):
                                                   P(side.data_ptr()), P(seg.data_ptr()), P(h)))
     _keep((planes, per_entry, tri, crosses, side, seg), ts, planes)
     return crosses.view(torch.bool), side, seg
+
+
+def _check_tile_rows(tile_rows):
+    if tile_rows is None:
+        return 0
+    if not isinstance(tile_rows, int) or isinstance(tile_rows, bool) or tile_rows < 1:
+        raise ValueError("tile_rows must be None or an int >= 1, not %r" % (tile_rows,))
+    return min(tile_rows, 2**31 - 1)
+
+
+def _check_capacity(name, x):
+    if x is not None and (not isinstance(x, int) or isinstance(x, bool) or x < 0):
+        raise ValueError("%s must be None or an int >= 0, not %r" % (name, x))
+
+
+def plane_loops_of(scene, offsets, seg, capacity=None, loop_capacity=None, want_next=False, tile_rows=None, stream=None):
+    """PlaneLoopsOf(next int64 [capacity] or None, order int64 [capacity], plane_loops int64 [n + 1], loop_offsets int64
+    [loop_capacity + 1], closed uint8 [loop_capacity]): the rows of a section already held -- `offsets` (int64 [n + 1]) and `seg`
+    (float32 [rows, 2, 3]) as plane_section returns them -- chained into polylines by comparing the bits of their end points:
+    loop l of plane i, plane_loops[i] <= l < plane_loops[i + 1], is the rows order[loop_offsets[l] .. loop_offsets[l + 1]) in walking
+    order, closed[l] says whether it returns to its first point, and next (want_next=True) is every row's successor or -1.  A row
+    of zero length is in no loop.  `capacity` (default: all rows of seg) is the number of rows that count: a plane whose rows reach
+    past it has no loops.  Entries of order past loop_offsets[L], and of next outside chained planes, are -1.  With both `capacity`
+    and `loop_capacity` given the call never synchronises; loops that do not fit are missing from loop_offsets and closed (entries
+    past the loops hold -1 and 0) -- compare plane_loops[n] with loop_capacity.  `loop_capacity=None` makes room for as many loops
+    as there are rows, synchronises the stream once to read plane_loops[n] and returns exactly L + 1 and L entries.  `tile_rows`
+    (None: the library's choice) is the longest plane that is chained in LDS; it changes the time only.  MEMORY: besides the outputs
+    (8 or 16 B per row of the capacity, 9 B per loop of the loop capacity -- with `loop_capacity=None` per ROW) the call allocates the
+    library's scratch, ezrt_plane_loops_work_bytes(capacity) = 64 B per row of the capacity: 1.5 GB for a section of 24 M rows,
+    beside the 0.6 GB of its `seg`; it is freed to torch's allocator when the stream is done with it.  The definition:
+    include/ezrt_plane_loops.h."""
+    return _plane_loops_of(scene, offsets, seg, capacity, loop_capacity, want_next, tile_rows, stream)[0]
+
+
+def _plane_loops_of(scene, offsets, seg, capacity, loop_capacity, want_next, tile_rows, stream):
+    """(plane_loops_of's answer, the number of chained rows where loop_capacity is None -- read in the same synchronisation -- else None)"""
+    c = _check_tile_rows(tile_rows)
+    _check_capacity("capacity", capacity)
+    _check_capacity("loop_capacity", loop_capacity)
+    _tensor("offsets", offsets, torch.int64)
+    if offsets.dim() != 1 or offsets.shape[0] < 1:
+        raise ValueError("offsets must have shape [n + 1], not %s" % (tuple(offsets.shape),))
+    _tensor("seg", seg, torch.float32, device=offsets.device)
+    if seg.dim() != 3 or tuple(seg.shape[1:]) != (2, 3):
+        raise ValueError("seg must have shape [rows, 2, 3], not %s" % (tuple(seg.shape),))
+    rows = seg.shape[0] if capacity is None else capacity
+    if rows > seg.shape[0]:
+        raise ValueError("capacity %d exceeds the %d rows of seg" % (rows, seg.shape[0]))
+    n = _count(offsets, 1, "planes") - 1
+    lib = _scene_lib(scene, _abi.PLANE_LOOPS_ABI)
+    dev = offsets.device
+    h, ts = _stream(offsets, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    lcap = rows if loop_capacity is None else loop_capacity
+    work_bytes = int(lib.ezrt_plane_loops_work_bytes(rows))
+    with torch.cuda.stream(own):
+        nxt = torch.full((rows,), -1, dtype=torch.int64, device=dev) if want_next else None
+        order = torch.full((rows,), -1, dtype=torch.int64, device=dev)
+        plane_loops = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        loop_offsets = torch.full((lcap + 1,), -1, dtype=torch.int64, device=dev)
+        closed = torch.zeros((lcap,), dtype=torch.uint8, device=dev)
+        work = torch.empty((work_bytes // 8 + 1,), dtype=torch.int64, device=dev)
+        if n == 0:
+            loop_offsets[0] = 0
+    P = C.c_void_p
+    if n > 0:
+        _call(scene, lib.ezrt_plane_loops_device(scene._h, P(offsets.data_ptr()), n, P(seg.data_ptr()) if rows else None, rows, c,
+                                                 P(nxt.data_ptr()) if want_next and rows else None, P(order.data_ptr()) if rows else None,
+                                                 P(plane_loops.data_ptr()), lcap, P(loop_offsets.data_ptr()),
+                                                 P(closed.data_ptr()) if lcap else None, P(work.data_ptr()), work_bytes, P(h)))
+    _keep((offsets, seg, nxt, order, plane_loops, loop_offsets, closed, work), ts, offsets)
+    R = None
+    if loop_capacity is None:
+        with torch.cuda.stream(own):                                 # the one synchronisation, of the query's stream: L, and the chained
+            L, R = torch.stack([plane_loops[n], (order >= 0).sum()]).tolist()   # rows (the entries of order that were written)
+        loop_offsets, closed = loop_offsets[:L + 1], closed[:L]
+    return PlaneLoopsOf(nxt, order, plane_loops, loop_offsets, closed), R
+
+
+def plane_loops(scene, planes, slices=None, tile_rows=None, stream=None):
+    """PlaneLoops(plane_loops int64 [n + 1], loop_offsets int64 [L + 1], closed uint8 [L], row int64 [R], tri int32 [R], seg float32
+    [R, 2, 3]): the cross-sections of the mesh with the n planes of `planes` ([..., 4], flattened row-major) as POLYLINES.  Loop l of
+    plane i, plane_loops[i] <= l < plane_loops[i + 1], is entries loop_offsets[l] .. loop_offsets[l + 1] of `tri` and `seg`: the
+    crossed triangles and their segments in walking order, each segment's q1 the next one's q0 on the bits; its points are
+    seg[loop_offsets[l]:loop_offsets[l + 1], 0], a closed loop (closed[l] == 1) returns to the first and an open one ends in the
+    last segment's q1.  `row` is the row of plane_section's answer that each entry came from.  Segments of zero length are left out.
+    On a closed, consistently wound mesh every loop is closed, outer loops run counter-clockwise seen from the side the plane's
+    normal points to and holes clockwise.  Synchronises the stream twice, for the number of rows and for the number of loops.
+    `slices` as for plane_count, `tile_rows` as for plane_loops_of.  MEMORY: the section (28 B per row) and plane_loops_of's arrays
+    and scratch (about 90 B per row while the call runs, see there) are allocated here: count the rows with plane_count first where
+    memory is tight.  The definition: include/ezrt_plane.h and include/ezrt_plane_loops.h."""
+    _check_tile_rows(tile_rows)
+    offsets, tri, seg = plane_section(scene, planes, slices=slices, stream=stream)
+    lp, R = _plane_loops_of(scene, offsets, seg, None, None, False, tile_rows, stream)
+    h, ts = _stream(planes, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=planes.device)
+    with torch.cuda.stream(own):
+        row = lp.order[:R]
+        out = PlaneLoops(lp.plane_loops, lp.loop_offsets, lp.closed, row, tri[row], seg[row])
+    _keep(out + (tri, seg, lp.order), ts, planes)
+    return out
+
+
+def loop_measures(loops, planes):
+    """(length, area), float64 [L]: of every loop of `loops` (a PlaneLoops of these `planes`) the sum of its segments' lengths
+    |q1 - q0| and the signed area 1/2 sum n^ . (q0 x q1) about the plane's unit normal -- the area enclosed by a closed loop,
+    positive for a loop that runs counter-clockwise seen from the normal's side (an outer boundary) and negative for a hole, so that
+    a plane's areas add up to its cross-section; of an open loop the area is that of the fan from the origin and means little.  Plain
+    float64 torch expressions on the current stream: NOT pinned on the bits (the order of a sum is the library's)."""
+    _check_planes(planes)
+    seg = loops.seg.to(torch.float64)
+    dev = seg.device
+    L = loops.closed.shape[0]
+    sizes = loops.loop_offsets[1:] - loops.loop_offsets[:-1]
+    loop_of = torch.repeat_interleave(torch.arange(L, device=dev), sizes, output_size=seg.shape[0])
+    per_plane = loops.plane_loops[1:] - loops.plane_loops[:-1]
+    plane_of = torch.repeat_interleave(torch.arange(per_plane.shape[0], device=dev), per_plane, output_size=L)
+    nrm = planes.reshape(-1, 4)[:, :3].to(torch.float64)
+    nrm = (nrm / nrm.square().sum(1, keepdim=True).sqrt())[plane_of][loop_of]
+    q0, q1 = seg[:, 0], seg[:, 1]
+    length = torch.zeros(L, dtype=torch.float64, device=dev).index_add_(0, loop_of, (q1 - q0).square().sum(1).sqrt())
+    area = torch.zeros(L, dtype=torch.float64, device=dev).index_add_(0, loop_of, 0.5 * (torch.linalg.cross(q0, q1) * nrm).sum(1))
+    return length, area
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
