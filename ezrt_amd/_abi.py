@@ -325,6 +325,18 @@ def plane_loops_limits():
     return a.value
 
 
+# stream-ordered mesh topology on device memory, libezrt_hip.so only (include/ezrt_topology.h); pointers are device addresses
+TOPOLOGY_ABI = {
+    # n_tri: the bytes of `work` (no device work)
+    "ezrt_topology_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, twin, edge_class, mult, root, component, comp_root, comp_size, comp_flags, summary, work, work_bytes, stream
+    "ezrt_mesh_topology_device": (C.c_int, [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
+    # s, tri_a, edge_a, tri_b, n, shared, opposite, stream
+    "ezrt_mesh_topology_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+EDGE_BOUNDARY, EDGE_MANIFOLD, EDGE_FLIPPED, EDGE_NONMANIFOLD = 1, 2, 3, 4
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -422,7 +434,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

@@ -3,7 +3,8 @@
 // nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
 // oriented-box, winding-number, plane, plane-loop and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
-// ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
+// ezrt_topology_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -26,8 +27,10 @@
 #include "ezrt_plane.h"
 #include "ezrt_plane_loops.h"
 #include "ezrt_overlap_list.h"
+#include "ezrt_topology.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
+#include "ezrt_topology_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -722,6 +725,83 @@ int ezrt_plane_loops_device(EzrtScene* s, const int64_t* offsets, int n, const f
       hipLaunchKernelGGL(loops_length_kernel, g, dim3(LP_BLOCK), 0, st, a);
       hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.lofs, (const long long*)(a.plane_loops + n), (long long)capacity);
       hipLaunchKernelGGL(loops_scatter_kernel, g, dim3(LP_BLOCK), 0, st, a);
+    });
+  });
+}
+
+// ---- mesh topology on device memory (include/ezrt_topology.h): up to eight launches on `st` -- init, join, rank, and with the
+// component group unite, flatten, loops_scan_kernel, scatter -- over the caller's `work`; checked, launched and ordered against a
+// refit by query_call.  `work` is scan (n_tri + 1 int64), then rep and head (T ints each, T the power of two >= 6 n_tri), link and
+// slot (3 n_tri ints each), parent, csize and cflag (n_tri ints each).
+static uint64_t topo_slots(int n_tri) {
+  if (n_tri <= 0) return 0;
+  uint64_t T = 8;
+  while (T < 6ull * (uint64_t)n_tri) T <<= 1;
+  return T;
+}
+size_t ezrt_topology_work_bytes(int n_tri) {
+  if (n_tri <= 0) return 8;
+  const uint64_t n = (uint64_t)n_tri, bytes = (n + 1) * 8 + topo_slots(n_tri) * 8 + 6 * n * 4 + 3 * n * 4;
+  return (size_t)((bytes + 7) / 8 * 8);
+}
+int ezrt_mesh_topology_device(EzrtScene* s, int32_t* twin, uint8_t* edge_class, int32_t* mult, int32_t* root, int32_t* component,
+                              int32_t* comp_root, int32_t* comp_size, uint8_t* comp_flags, int64_t* summary, void* work, size_t work_bytes,
+                              void* stream) {
+  return ezi::guarded("ezrt_mesh_topology_device", [&]() -> int {
+    if (!s || !twin || !edge_class || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    const int group = (root ? 1 : 0) + (component ? 1 : 0) + (comp_root ? 1 : 0) + (comp_size ? 1 : 0) + (comp_flags ? 1 : 0);
+    if (group != 0 && group != 5)
+      return fail(EZRT_ERR_INVALID, "root, component, comp_root, comp_size and comp_flags are given together or not at all");
+    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    const int n_tri = (int)s->n_tri;
+    if (work_bytes < ezrt_topology_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_topology_work_bytes(n_tri)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{twin, H * i4}, {edge_class, H}, {mult, H * i4}, {root, N * i4}, {component, N * i4}, {comp_root, N * i4},
+                          {comp_size, N * i4}, {comp_flags, N}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_topology_work_bytes(n_tri)}},
+                      H, st, [&](dim3, dim3) {
+      TopoArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = (int32_t)n_tri;
+      a.T = topo_slots(n_tri);
+      a.scan = (long long*)work;
+      a.rep = (int32_t*)(a.scan + N + 1);
+      a.head = (uint32_t*)(a.rep + a.T);
+      a.link = a.head + a.T;
+      a.slot = a.link + H;
+      a.parent = (int32_t*)(a.slot + H);
+      a.csize = a.parent + N;
+      a.cflag = (uint32_t*)(a.csize + N);
+      a.twin = twin, a.edge_class = edge_class, a.mult = mult;
+      a.root = root, a.component = component, a.comp_root = comp_root, a.comp_size = comp_size, a.comp_flags = comp_flags;
+      a.summary = (unsigned long long*)summary;
+      // grid-stride loops: at most TP_GRID_MAX workgroups, a few per CU
+      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + TP_BLOCK - 1) / TP_BLOCK, TP_GRID_MAX)); };
+      const dim3 b(TP_BLOCK), gh = grid(H), gt = grid(N);
+      hipLaunchKernelGGL(topo_init_kernel, grid(a.T), b, 0, st, a, group == 5);
+      hipLaunchKernelGGL(topo_join_kernel, gh, b, 0, st, a);
+      hipLaunchKernelGGL(topo_rank_kernel, gh, b, 0, st, a);
+      if (group == 5) {
+        hipLaunchKernelGGL(topo_unite_kernel, gh, b, 0, st, a);
+        hipLaunchKernelGGL(topo_flatten_kernel, gt, b, 0, st, a);
+        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.scan, (const long long*)nullptr, (long long)n_tri);
+        hipLaunchKernelGGL(topo_scatter_kernel, gt, b, 0, st, a);
+      }
+    });
+  });
+}
+int ezrt_mesh_topology_at_device(EzrtScene* s, const int32_t* tri_a, const int32_t* edge_a, const int32_t* tri_b, int n, int8_t* shared,
+                                 int8_t* opposite, void* stream) {
+  return ezi::guarded("ezrt_mesh_topology_at_device", [&]() -> int {
+    if (!s || !tri_a || !edge_a || !tri_b || !shared || !opposite || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri_a, N * sizeof(int32_t)}, {edge_a, N * sizeof(int32_t)}, {tri_b, N * sizeof(int32_t)}, {shared, N}, {opposite, N}},
+                      N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(topo_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tri_a, edge_a, tri_b, (uint32_t)n, shared, opposite);
     });
   });
 }

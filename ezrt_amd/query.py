@@ -2,7 +2,7 @@
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
-include/ezrt_overlap_list.h).
+include/ezrt_overlap_list.h, include/ezrt_topology.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -42,6 +42,8 @@ include/ezrt_overlap_list.h).
     length, area = query.loop_measures(loops, planes)                         # ... perimeter and signed area of every loop (float64)
     offsets, tri, n_found = query.box_overlap_list(scene, lo, hi)             # EVERY triangle each box touches, CSR (include/ezrt_overlap_list.h)
     ... and obb_overlap_list, tri_overlap_list, self_overlap_list, capsule_overlap_list: the inputs of the max_k call, all ids
+    topo = query.mesh_topology(scene)                                         # twins, edge classes, components; topo.closed, topo.oriented
+    shared, opposite = query.mesh_topology_at(scene, tri_a, edge_a, tri_b)    # ... the same rule for pairs already held (include/ezrt_topology.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -84,6 +86,7 @@ ObbOverlap = collections.namedtuple("ObbOverlap", "tri n_overlap")
 OverlapList = collections.namedtuple("OverlapList", "offsets tri n_found")
 PlaneLoops = collections.namedtuple("PlaneLoops", "plane_loops loop_offsets closed row tri seg")
 PlaneLoopsOf = collections.namedtuple("PlaneLoopsOf", "next order plane_loops loop_offsets closed")
+MeshTopology = collections.namedtuple("MeshTopology", "twin edge_class neighbours mult root component comp_root comp_size comp_flags summary closed oriented")
 
 
 def _scene_lib(scene, abi):
@@ -1189,6 +1192,78 @@ def loop_measures(loops, planes):
     length = torch.zeros(L, dtype=torch.float64, device=dev).index_add_(0, loop_of, (q1 - q0).square().sum(1).sqrt())
     area = torch.zeros(L, dtype=torch.float64, device=dev).index_add_(0, loop_of, 0.5 * (torch.linalg.cross(q0, q1) * nrm).sum(1))
     return length, area
+
+
+def mesh_topology(scene, components=True, mult=False, stream=None):
+    """MeshTopology(twin int32 [n_tri, 3], edge_class uint8 [n_tri, 3], neighbours int32 [n_tri, 3], mult int32 [n_tri, 3] or None,
+    root int32 [n_tri], component int32 [n_tri], comp_root int32 [C], comp_size int32 [C], comp_flags uint8 [C], summary int64 [8],
+    closed bool, oriented bool): the topology of the scene's triangles as they are stored, vertices compared by value on the bits
+    (-0 is +0).  twin[t, e] is the half-edge 3 t' + e' paired with edge e of triangle t (from its vertex e to vertex (e + 1) % 3) or
+    -1, neighbours[t, e] = t' or -1, edge_class[t, e] is 0 for a triangle that does not take part (a non-finite coordinate, two
+    equal vertices), 1 BOUNDARY, 2 MANIFOLD, 3 FLIPPED (the two neighbours are wound inconsistently), 4 NONMANIFOLD (three or more
+    triangles on the edge), and mult (mult=True) the number of triangles on the edge.  root[t] is the lowest id of the triangles
+    connected with t across edges and component[t] its number 0 .. C - 1 in ascending order of the roots (-1 for a triangle that
+    does not take part); comp_root, comp_size and comp_flags (bit 0 / 1 / 2: the component has a BOUNDARY / FLIPPED / NONMANIFOLD
+    edge) describe the components.  summary is [triangles taking part, edges, BOUNDARY, MANIFOLD, FLIPPED, NONMANIFOLD edges, C,
+    largest multiplicity].  `closed` (no BOUNDARY and no NONMANIFOLD edge) is what inside and signed_distance assume, `closed and
+    oriented` (no FLIPPED edge either) what plane_loops needs for closed loops and winding_number for a sign.  With
+    components=False the union-find is not run: root .. comp_flags are None and summary[6] is 0.  The tensors are on the current
+    device (the scene's, when it was created there).  Synchronises the stream once, to read the summary.  After a refit the topology
+    can change: call again.  MEMORY: the library's scratch, ezrt_topology_work_bytes(n_tri), about 100 B per triangle, is allocated
+    here and freed to torch's allocator when the stream is done with it.  The definition: include/ezrt_topology.h."""
+    if not isinstance(components, bool) or not isinstance(mult, bool):
+        raise ValueError("components and mult must be bools")
+    lib = _scene_lib(scene, _abi.TOPOLOGY_ABI)
+    n = scene.stats()["n_tri"]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    probe = torch.empty((0,), dtype=torch.int32, device=dev)
+    h, ts = _stream(probe, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    work_bytes = int(lib.ezrt_topology_work_bytes(n))
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    with torch.cuda.stream(own):
+        twin, cls = i32(n, 3), torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        mu = i32(n, 3) if mult else None
+        root, comp, croot, csize = (i32(n), i32(n), i32(n), i32(n)) if components else (None,) * 4
+        cflags = torch.empty((n,), dtype=torch.uint8, device=dev) if components else None
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_mesh_topology_device(scene._h, ptr(twin), ptr(cls), ptr(mu), ptr(root), ptr(comp), ptr(croot), ptr(csize),
+                                                   ptr(cflags), ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((twin, cls, mu, root, comp, croot, csize, cflags, summary, work), ts, probe)
+    with torch.cuda.stream(own):
+        nb = torch.where(twin >= 0, torch.div(twin, 3, rounding_mode="floor"), twin)
+        sm = summary.tolist()                                        # the one synchronisation, of the query's stream
+        if components:
+            croot, csize, cflags = croot[:sm[6]], csize[:sm[6]], cflags[:sm[6]]
+    _keep((nb,), ts, probe)
+    return MeshTopology(twin, cls, nb, mu, root, comp, croot, csize, cflags, summary, sm[2] == 0 and sm[5] == 0, sm[4] == 0 and sm[5] == 0)
+
+
+def mesh_topology_at(scene, tri_a, edge_a, tri_b, stream=None):
+    """(shared int8 tri_a.shape, opposite int8 tri_a.shape): mesh_topology's rule for pairs already held.  For edge edge_a[...] (0, 1
+    or 2) of triangle tri_a[...], shared is the edge of triangle tri_b[...] that joins the same two vertices by value, or -1, and
+    opposite is 1 when the two run in opposite directions (consistent windings), 0 when they run the same way, -1 without a shared
+    edge.  The three are contiguous int32 GPU tensors of one shape.  An id that is no triangle of the scene, an edge outside 0 .. 2
+    and a triangle that does not take part give (-1, -1)."""
+    _tensor("tri_a", tri_a, torch.int32)
+    _tensor("edge_a", edge_a, torch.int32, shape=tri_a.shape, device=tri_a.device)
+    _tensor("tri_b", tri_b, torch.int32, shape=tri_a.shape, device=tri_a.device)
+    lib = _scene_lib(scene, _abi.TOPOLOGY_ABI)
+    n = _count(tri_a, 1, "pairs")
+    shared = torch.empty(tuple(tri_a.shape), dtype=torch.int8, device=tri_a.device)
+    opposite = torch.empty(tuple(tri_a.shape), dtype=torch.int8, device=tri_a.device)
+    if n == 0:
+        return shared, opposite
+    h, ts = _stream(tri_a, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_mesh_topology_at_device(scene._h, P(tri_a.data_ptr()), P(edge_a.data_ptr()), P(tri_b.data_ptr()), n,
+                                                  P(shared.data_ptr()), P(opposite.data_ptr()), P(h)))
+    _keep((tri_a, edge_a, tri_b, shared, opposite), ts, tri_a)
+    return shared, opposite
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
