@@ -337,6 +337,23 @@ TOPOLOGY_ABI = {
 EDGE_BOUNDARY, EDGE_MANIFOLD, EDGE_FLIPPED, EDGE_NONMANIFOLD = 1, 2, 3, 4
 
 
+# stream-ordered vertex weld and smooth normals on device memory, libezrt_hip.so only (include/ezrt_vertices.h); pointers are device
+# addresses
+WELD_ABI = {
+    # n_tri: the bytes of `work` (no device work)
+    "ezrt_weld_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, vertex, vert_corner, star_offsets, star, fans, vert_flags, summary, work, work_bytes, stream
+    "ezrt_mesh_weld_device": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    # s, corner_a, corner_b, n, same, stream
+    "ezrt_mesh_weld_at_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ezrt_vertex_normals_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, tri36, n_tri, vertex, star_offsets, star, work, work_bytes, stream
+    "ezrt_vertex_normals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+}
+VERTEX_BORDER, VERTEX_NONMANIFOLD_EDGE, VERTEX_PINCHED = 1, 2, 4
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -434,7 +451,8 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, OVERLAP_LIST_ABI, REFIT_ABI):
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, OVERLAP_LIST_ABI,
+                      REFIT_ABI):
             _declare(lib, table)
         _hip = lib
     return _hip

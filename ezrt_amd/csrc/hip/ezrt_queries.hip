@@ -4,7 +4,8 @@
 // oriented-box, winding-number, plane, plane-loop and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
 // ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
-// ezrt_topology_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
+// ezrt_vertex_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -28,9 +29,11 @@
 #include "ezrt_plane_loops.h"
 #include "ezrt_overlap_list.h"
 #include "ezrt_topology.h"
+#include "ezrt_vertices.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
+#include "ezrt_vertex_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -802,6 +805,116 @@ int ezrt_mesh_topology_at_device(EzrtScene* s, const int32_t* tri_a, const int32
     return query_call(s, {{tri_a, N * sizeof(int32_t)}, {edge_a, N * sizeof(int32_t)}, {tri_b, N * sizeof(int32_t)}, {shared, N}, {opposite, N}},
                       N, st, [&](dim3 g, dim3 b) {
       hipLaunchKernelGGL(topo_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tri_a, edge_a, tri_b, (uint32_t)n, shared, opposite);
+    });
+  });
+}
+
+// ---- vertex weld and smooth normals on device memory (include/ezrt_vertices.h): up to fifteen launches on `st` for the weld -- init,
+// join, flag, a prefix sum (sums, loops_scan_kernel, scan), id, the prefix sum again, scatter, rank, and with the flags group link,
+// fans, finish -- over the caller's `work`: ids and cnt (3 n_tri + 1 int64 each), tiles (one int64 per 2048 corners, and one), rep
+// (T ints, T the topology's power of two >= 6 n_tri), then slot, cur, tmp,
+// parent, flagw and fanc (3 n_tri ints each); two launches for the normals over 3 n_tri floats of `work`.  Checked, launched and
+// ordered against a refit by query_call.
+static uint64_t weld_tiles(int n_tri) { return (3ull * (uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
+size_t ezrt_weld_work_bytes(int n_tri) {
+  if (n_tri <= 0) return 8;
+  const uint64_t h = 3ull * (uint64_t)n_tri, bytes = 2 * (h + 1) * 8 + (weld_tiles(n_tri) + 1) * 8 + topo_slots(n_tri) * 4 + 6 * h * 4;
+  return (size_t)((bytes + 7) / 8 * 8);
+}
+int ezrt_mesh_weld_device(EzrtScene* s, int32_t* vertex, int32_t* vert_corner, int32_t* star_offsets, int32_t* star, int32_t* fans,
+                          uint8_t* vert_flags, int64_t* summary, void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_mesh_weld_device", [&]() -> int {
+    if (!s || !vertex || !vert_corner || !star_offsets || !star || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (!fans != !vert_flags) return fail(EZRT_ERR_INVALID, "fans and vert_flags are given together or not at all");
+    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    const int n_tri = (int)s->n_tri;
+    if (work_bytes < ezrt_weld_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_weld_work_bytes(n_tri)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_tri <= 0) return 0;
+    const size_t H = 3 * (size_t)n_tri, i4 = sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{vertex, H * i4}, {vert_corner, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4}, {fans, H * i4}, {vert_flags, H},
+                          {summary, 8 * sizeof(int64_t)}, {work, ezrt_weld_work_bytes(n_tri)}},
+                      H, st, [&](dim3, dim3) {
+      WeldArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = (int32_t)n_tri;
+      a.T = topo_slots(n_tri);
+      a.ids = (long long*)work;
+      a.cnt = a.ids + H + 1;
+      a.tiles = a.cnt + H + 1;
+      const uint64_t B = weld_tiles(n_tri);
+      a.rep = (int32_t*)(a.tiles + B + 1);
+      a.slot = (uint32_t*)(a.rep + a.T);
+      a.cur = (int32_t*)(a.slot + H);
+      a.tmp = a.cur + H;
+      a.parent = a.tmp + H;
+      a.flagw = (uint32_t*)(a.parent + H);
+      a.fanc = (int32_t*)(a.flagw + H);
+      a.vertex = vertex, a.vert_corner = vert_corner, a.star_offsets = star_offsets, a.star = star, a.fans = fans, a.vert_flags = vert_flags;
+      a.summary = (unsigned long long*)summary;
+      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + WD_BLOCK - 1) / WD_BLOCK, WD_GRID_MAX)); };
+      const dim3 b(WD_BLOCK), gh = grid(H), scan(LP_SCAN);
+      hipLaunchKernelGGL(weld_init_kernel, grid(a.T), b, 0, st, a, fans != nullptr);
+      hipLaunchKernelGGL(weld_join_kernel, gh, b, 0, st, a);
+      hipLaunchKernelGGL(weld_flag_kernel, gh, b, 0, st, a);
+      // a prefix sum of x in place over B tiles (ezrt_vertex_kernels.h: weld_scan_kernel); n_dev: its length, read on the device
+      const auto prefix = [&](long long* x, const long long* n_dev) {
+        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)B), b, 0, st, (const long long*)x, a.tiles, n_dev, (long long)H);
+        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), scan, 0, st, a.tiles, (const long long*)nullptr, (long long)B);
+        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)B), b, 0, st, x, (const long long*)a.tiles, n_dev, (long long)H);
+      };
+      prefix(a.ids, nullptr);
+      hipLaunchKernelGGL(weld_id_kernel, gh, b, 0, st, a);
+      prefix(a.cnt, (const long long*)(a.ids + H));
+      hipLaunchKernelGGL(weld_scatter_kernel, grid(H + 1), b, 0, st, a);
+      hipLaunchKernelGGL(weld_rank_kernel, gh, b, 0, st, a);
+      if (fans) {
+        hipLaunchKernelGGL(weld_link_kernel, gh, b, 0, st, a);
+        hipLaunchKernelGGL(weld_fans_kernel, gh, b, 0, st, a);
+        hipLaunchKernelGGL(weld_finish_kernel, gh, b, 0, st, a);
+      }
+    });
+  });
+}
+int ezrt_mesh_weld_at_device(EzrtScene* s, const int32_t* corner_a, const int32_t* corner_b, int n, int8_t* same, void* stream) {
+  return ezi::guarded("ezrt_mesh_weld_at_device", [&]() -> int {
+    if (!s || !corner_a || !corner_b || !same || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{corner_a, N * sizeof(int32_t)}, {corner_b, N * sizeof(int32_t)}, {same, N}}, N, st, [&](dim3 g, dim3 b) {
+      hipLaunchKernelGGL(weld_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, corner_a, corner_b, (uint32_t)n, same);
+    });
+  });
+}
+size_t ezrt_vertex_normals_work_bytes(int n_tri) {
+  if (n_tri <= 0) return 8;
+  return (size_t)((3ull * (uint64_t)n_tri * sizeof(float) + 7) / 8 * 8);
+}
+int ezrt_vertex_normals_device(EzrtScene* s, float* tri36, int n_tri, const int32_t* vertex, const int32_t* star_offsets, const int32_t* star,
+                               void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_vertex_normals_device", [&]() -> int {
+    if (!s || !tri36 || !vertex || !star_offsets || !star || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
+    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    if (work_bytes < ezrt_vertex_normals_work_bytes(n_tri))
+      return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_vertex_normals_work_bytes(n_tri)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {vertex, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4},
+                          {work, ezrt_vertex_normals_work_bytes(n_tri)}},
+                      N, st, [&](dim3 g, dim3 b) {
+      VertexNormalArgs a{};
+      a.tri36 = tri36;
+      a.n_tri = (int32_t)n_tri;
+      a.vertex = vertex, a.star_offsets = star_offsets, a.star = star;
+      a.face = (float*)work;
+      hipLaunchKernelGGL(vn_face_kernel, g, b, 0, st, a);
+      hipLaunchKernelGGL(vn_corner_kernel, dim3((unsigned)((H + WD_BLOCK - 1) / WD_BLOCK)), b, 0, st, a);
     });
   });
 }

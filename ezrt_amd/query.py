@@ -2,7 +2,7 @@
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
-include/ezrt_overlap_list.h, include/ezrt_topology.h).
+include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -44,6 +44,11 @@ include/ezrt_overlap_list.h, include/ezrt_topology.h).
     ... and obb_overlap_list, tri_overlap_list, self_overlap_list, capsule_overlap_list: the inputs of the max_k call, all ids
     topo = query.mesh_topology(scene)                                         # twins, edge classes, components; topo.closed, topo.oriented
     shared, opposite = query.mesh_topology_at(scene, tri_a, edge_a, tri_b)    # ... the same rule for pairs already held (include/ezrt_topology.h)
+    weld = query.mesh_weld(scene)                                             # the indexed mesh: vertex of every corner, stars, fans, flags
+    same = query.mesh_weld_at(scene, corner_a, corner_b)                      # ... the same rule for pairs already held (include/ezrt_vertices.h)
+    tri36 = query.vertex_normals(scene, tri36, weld)                          # smooth normals of moved rows, into floats 9-17, before a refit
+    positions, faces = query.indexed_mesh(weld, tri36)                        # ... what every other tool takes
+    chi = query.euler_characteristic(weld, topo)                              # V - E + F
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -87,6 +92,7 @@ OverlapList = collections.namedtuple("OverlapList", "offsets tri n_found")
 PlaneLoops = collections.namedtuple("PlaneLoops", "plane_loops loop_offsets closed row tri seg")
 PlaneLoopsOf = collections.namedtuple("PlaneLoopsOf", "next order plane_loops loop_offsets closed")
 MeshTopology = collections.namedtuple("MeshTopology", "twin edge_class neighbours mult root component comp_root comp_size comp_flags summary closed oriented")
+MeshWeld = collections.namedtuple("MeshWeld", "vertex vert_corner star_offsets star fans vert_flags summary n_vert manifold_vertices")
 
 
 def _scene_lib(scene, abi):
@@ -1264,6 +1270,132 @@ def mesh_topology_at(scene, tri_a, edge_a, tri_b, stream=None):
                                                   P(shared.data_ptr()), P(opposite.data_ptr()), P(h)))
     _keep((tri_a, edge_a, tri_b, shared, opposite), ts, tri_a)
     return shared, opposite
+
+
+def mesh_weld(scene, flags=True, stream=None):
+    """MeshWeld(vertex int32 [n_tri, 3], vert_corner int32 [V], star_offsets int32 [V + 1], star int32 [L], fans int32 [V] or None,
+    vert_flags uint8 [V] or None, summary int64 [8], n_vert int, manifold_vertices bool): the scene's triangles as an indexed mesh,
+    vertices compared by value on the bits (-0 is +0), as mesh_topology compares them.  vertex[t, k] is the number 0 .. V - 1 of stored
+    vertex k of triangle t, or -1 for a triangle that does not take part (a non-finite coordinate, two equal vertices); vertices are
+    numbered by their lowest corner 3 t + k, which is vert_corner[v].  star[star_offsets[v] : star_offsets[v + 1]] is the corners
+    that are vertex v, ascending.  fans[v] is the number of cones of triangles that meet at v (1 on an ordinary vertex) and
+    vert_flags[v] has bit 0 set on the border, bit 1 at an edge of three or more triangles, bit 2 where fans[v] > 1.  summary is
+    [corners taking part, V, largest valence, vertices with bit 0, bit 1, bit 2, 0, 0]; n_vert is V and manifold_vertices says that no
+    vertex has bit 2: with mesh_topology's `closed` the mesh is a closed 2-manifold.  With flags=False fans and vert_flags are None,
+    the three counts are 0 and manifold_vertices is None.  The trimmed tensors are views of arrays of the full size, which is what
+    vertex_normals takes.  The tensors are on the current device (the scene's, when it was created there).  Synchronises the
+    stream once, to read the summary.  The weld is taken by value: it holds for every refit that moves vertices and keeps which
+    corners coincide.  MEMORY: the library's scratch, ezrt_weld_work_bytes(n_tri), up to 168 B per triangle, is allocated here and
+    freed to torch's allocator when the stream is done with it.  The definition: include/ezrt_vertices.h."""
+    if not isinstance(flags, bool):
+        raise ValueError("flags must be a bool")
+    lib = _scene_lib(scene, _abi.WELD_ABI)
+    n = scene.stats()["n_tri"]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    probe = torch.empty((0,), dtype=torch.int32, device=dev)
+    h, ts = _stream(probe, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    work_bytes = int(lib.ezrt_weld_work_bytes(n))
+    i32 = lambda k: torch.empty((k,), dtype=torch.int32, device=dev)
+    with torch.cuda.stream(own):
+        vertex, corner, offsets, star = i32(3 * n).view(n, 3), i32(3 * n), i32(3 * n + 1), i32(3 * n)
+        fans = i32(3 * n) if flags else None
+        vflags = torch.empty((3 * n,), dtype=torch.uint8, device=dev) if flags else None
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+        if n == 0:
+            offsets.zero_()
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_mesh_weld_device(scene._h, ptr(vertex), ptr(corner), ptr(offsets), ptr(star), ptr(fans), ptr(vflags),
+                                               ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((vertex, corner, offsets, star, fans, vflags, summary, work), ts, probe)
+    with torch.cuda.stream(own):
+        sm = summary.tolist()                                        # the one synchronisation, of the query's stream
+    L, V = sm[0], sm[1]
+    return MeshWeld(vertex, corner[:V], offsets[:V + 1], star[:L], fans[:V] if flags else None, vflags[:V] if flags else None, summary, V,
+                    sm[5] == 0 if flags else None)
+
+
+def mesh_weld_at(scene, corner_a, corner_b, stream=None):
+    """same int8 corner_a.shape: mesh_weld's rule for pairs already held.  1 when corners corner_a[...] and corner_b[...] (3 t + k:
+    stored vertex k of triangle t) are one vertex by value, 0 when they are two, -1 when either is no corner of the scene or belongs
+    to a triangle that does not take part.  The two are contiguous int32 GPU tensors of one shape."""
+    _tensor("corner_a", corner_a, torch.int32)
+    _tensor("corner_b", corner_b, torch.int32, shape=corner_a.shape, device=corner_a.device)
+    lib = _scene_lib(scene, _abi.WELD_ABI)
+    n = _count(corner_a, 1, "pairs")
+    same = torch.empty(tuple(corner_a.shape), dtype=torch.int8, device=corner_a.device)
+    if n == 0:
+        return same
+    h, ts = _stream(corner_a, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_mesh_weld_at_device(scene._h, P(corner_a.data_ptr()), P(corner_b.data_ptr()), n, P(same.data_ptr()), P(h)))
+    _keep((corner_a, corner_b, same), ts, corner_a)
+    return same
+
+
+def _weld_array(name, x, size, dev, own):
+    """x, an int32 array of a weld, as the `size` entries the C call may read: x itself where that much memory lies behind it (the
+    trimmed views of mesh_weld), else a zero-padded copy made on the query's stream"""
+    _tensor(name, x, torch.int32, device=dev)
+    if x.numel() >= size or (x.untyped_storage().nbytes() - x.storage_offset() * 4) >= size * 4:
+        return x
+    with torch.cuda.stream(own):
+        full = torch.zeros((size,), dtype=torch.int32, device=dev)
+        full[:x.numel()] = x.reshape(-1)
+    return full
+
+
+def vertex_normals(scene, tri36, weld, stream=None):
+    """tri36, with floats 9-17 of every row (n1 n2 n3) overwritten by the smooth normals of its OWN positions (floats 0-8) over the
+    stars of `weld` (a MeshWeld of this scene, or any object with vertex, star_offsets and star): the reference's readObj(...,
+    smoothNormal=True) -- face normals summed in fp32 from +0 in ascending corner order, normalised -- on the bits wherever the
+    mesh's vertices are distinct by value; a corner of a triangle that does not take part gets its face normal.  tri36 is the
+    caller's contiguous float32 [n_tri, 36] GPU tensor, the one about to go into refit.refit; nothing else of it is written.  Weld once,
+    then per step: deform, vertex_normals, refit, render.  Does not synchronise.  The definition: include/ezrt_vertices.h."""
+    lib = _scene_lib(scene, _abi.WELD_ABI)
+    n = scene.stats()["n_tri"]
+    _tensor("tri36", tri36, torch.float32, shape=(n, 36))
+    dev = tri36.device
+    h, ts = _stream(tri36, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, own)
+    offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, own)
+    star = _weld_array("weld.star", weld.star, 3 * n, dev, own)
+    if vertex.numel() != 3 * n:
+        raise ValueError("weld.vertex must have 3 * n_tri = %d entries, not %d" % (3 * n, vertex.numel()))
+    if n == 0:
+        return tri36
+    work_bytes = int(lib.ezrt_vertex_normals_work_bytes(n))
+    with torch.cuda.stream(own):
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_vertex_normals_device(scene._h, P(tri36.data_ptr()), n, P(vertex.data_ptr()), P(offsets.data_ptr()),
+                                                P(star.data_ptr()), P(work.data_ptr()), work_bytes, P(h)))
+    _keep((tri36, vertex, offsets, star, work), ts, tri36)
+    return tri36
+
+
+def indexed_mesh(weld, tri36):
+    """(positions float32 [V, 3], faces int32 [n_tri, 3]): the indexed mesh of a weld, by plain torch indexing on the current stream.
+    positions[v] is read from tri36 (float32 [n_tri, 36], or [n_tri, 9]: the rows the weld was made of, or moved ones) at corner
+    vert_corner[v]; faces is weld.vertex, -1 in the rows of triangles that do not take part."""
+    if not isinstance(tri36, torch.Tensor) or tri36.dim() != 2 or tri36.shape[1] not in (9, 36) or tri36.shape[0] != weld.vertex.shape[0]:
+        raise ValueError("tri36 must be a tensor of shape [n_tri, 36] or [n_tri, 9] with the weld's n_tri")
+    corner = weld.vert_corner.to(torch.int64)
+    positions = tri36[:, :9].reshape(-1, 3)[corner]
+    return positions, weld.vertex
+
+
+def euler_characteristic(weld, topo):
+    """V - E + F of the triangles that take part: weld.summary[1] - topo.summary[1] + topo.summary[0] (2 for a sphere, 0 for a
+    torus).  Reads the two summaries (a synchronisation of the current stream)."""
+    w, t = weld.summary.tolist(), topo.summary.tolist()
+    if w[0] != 3 * t[0]:
+        raise ValueError("the weld and the topology are not of the same triangles (%d live corners, %d live triangles)" % (w[0], t[0]))
+    return w[1] - t[1] + t[0]
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
