@@ -583,6 +583,10 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
   a.all_owned = (p->shard_count <= 1 && p->x0 == 0 && p->y0 == 0 && p->x1 == p->width && p->y1 == p->height && p->width % 16 == 0 &&
                  p->height % 16 == 0 && s->tune.lazy_dir) ? 1u : 0u;
   a.gen_primary = 0u; // (the shading passes read the directions the trace launch stored: see traceq4_kernel GEN)
+  // integrator 50's state into stage 1 without the s1 array while a sample slot fits its bits (any chunk of the knob's range; a single
+  // frame of more pixel-samples keeps the array).  Read by the compact state's code alone.
+  const bool lean1 = n_slots <= ((size_t)1 << LEAN_SLOT_BITS);
+  a.lean1 = lean1 ? 1u : 0u;
   if (gen_primary) hipLaunchKernelGGL(chunk_prologue_kernel, dim3((unsigned)(4 * s->num_cus)), dim3(BLOCK), 0, st, a, pro);
   else hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((n_slots + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a, pro);
   if (s->tune.debug_stages && wide)
@@ -666,6 +670,13 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
       g.st_slot = (compact || mis1) ? state(in).s1 : state(in).s2;
       g.slot_comp = compact ? (b == 1 ? 0 : 3) : (mis1 ? 1 : 3);
       g.slot_stride = (compact && b == 1) ? 2 : 4;
+      g.slot_mask = 0xffffffffu;
+      if (compact && b == 1 && lean1) { // the lean state: the slot rides in the direction's w (LEAN_LIVE)
+        g.st_slot = queue(in).d;
+        g.slot_comp = 3;
+        g.slot_stride = 4;
+        g.slot_mask = LEAN_SLOT_MASK;
+      }
       g.n_in = pp.qcounts.p + b;
       g.n_slots = (uint32_t)n_slots;
       g.bounce = b;

@@ -35,8 +35,11 @@ struct PathState { // SoA of float4, one slot per live path
   float4* s4; // shadow contribution.xyz, bits(flags)          (integrator 51 only)
   // Integrator 50 (pdf is the constant 1/(2 pi), no RNG state after ray generation, Le0 = the emission of the
   // primary hit's triangle) carries a COMPACT state instead -- the shading stages are bound by streaming this state:
-  //   into stage 1 (history = 1 and Lo = 0 exactly):  s0 = f_r.xyz, cosine   s1 = float2: bits(sample slot), bits(tri0)   24 B
-  //   (tri0 = the primary hit's triangle if its emission is not all-zero bits, else 0xffffffff)
+  //   into stage 1 (history = 1 and Lo = 0 exactly):  s0 = f_r.xyz, cosine   and the two words (sample slot, tri0)            16 B
+  //   (tri0 = the primary hit's triangle if its emission is not all-zero bits, else 0xffffffff).  The two words ride in the w
+  //   components of the path's bounce ray (WfArgs::lean1, LEAN_LIVE): the slot and an "emits" bit in the direction's w, tri0 in the
+  //   origin's w, which the stage's first pass reads for the emitting lanes alone.  Only a chunk whose sample slots do not fit 28
+  //   bits (a single frame beyond 2^28 pixel-samples) keeps them as float2 records in the s1 array: 24 B.
   //   into stages >= 2:  s0 = history.xyz, cosine   s1 = Lo.xyz, bits(sample slot)   s2 = f_r.xyz, bits(tri0)      48 B
   // (tri0 = the primary hit's triangle; Le0 is re-read from its material at the path's end)
   // The MIS integrators (51, 52) carry the general state from stage 1 on, but INTO stage 1 -- the biggest stage, and its
@@ -76,7 +79,17 @@ struct WfArgs {
   uint32_t scatter_shift;  // scattered granule = 1 << scatter_shift slots (6: 8x8 sub-block, 8: 16x16 block, 5: 8x4 pixels)
   uint32_t all_owned;      // 1: every queue position of stage 0 is a pixel-sample of this call (one shard, whole 16x16 blocks)
   uint32_t gen_primary;    // 1: queue 0 holds no directions -- stage 0 recomputes its ray from the queue position (primary_dir)
+  uint32_t lean1;          // 1: integrator 50's state into stage 1 has no s1 array (PathState, "lean"): the chunk's sample slots fit LEAN_SLOT_BITS
 };
+// Integrator 50, state into stage 1, lean form: the two words of s1 ride in the ray's own records, whose w components the render's
+// trace launches do not compute with (the direction's w is only compared with 0, the origin's w is not read).
+//   direction.w = bits(LEAN_LIVE | LEAN_EMITS if the primary hit emits | sample slot): bit 30 set, bit 29 and the sign clear -- a
+//                 normal, finite, non-zero float whatever the slot, so "w != 0" still says the slot holds a ray; an empty slot is all zeros
+//   origin.w    = bits(tri0), meaningful (and read) only with LEAN_EMITS
+constexpr uint32_t LEAN_SLOT_BITS = 28u; // (knob chunk_log2 <= 28; a single frame beyond 2^28 pixel-samples keeps the s1 array)
+constexpr uint32_t LEAN_SLOT_MASK = (1u << LEAN_SLOT_BITS) - 1u;
+constexpr uint32_t LEAN_EMITS = 1u << 28;
+constexpr uint32_t LEAN_LIVE = 1u << 30;
 
 // ---------------------------------------------------------------------------
 // raygen: P5/fsh:315-318, 920-925
@@ -210,6 +223,7 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
   } else {
     rd4 = a.rq_in.d[rslot];
   }
+  const bool lean = COMPACT && STAGE == 1 && a.lean1; // (see LEAN_LIVE)
   float4 ro4 = make_float4(p.eye[0], p.eye[1], p.eye[2], 0.0f);
   float4 s0 = make_float4(0, 0, 0, 0), s1 = s0, s2 = s0, s3 = s0, s4 = s0;
   int2 sh = make_int2(-1, 0);
@@ -218,8 +232,10 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
     if (!COMPACT && !MIS1) s3 = a.st_in.s3[ii];
     s0 = a.st_in.s0[ii];
     if (COMPACT && STAGE == 1) { // (bits(sample slot), bits(tri0)) only: 8-byte records in the s1 array
-      const float2 q = reinterpret_cast<const float2*>(a.st_in.s1)[ii];
-      s1 = make_float4(q.x, q.y, 0.0f, 0.0f);
+      if (!lean) { // (lean: both come out of the ray's records, below the pins)
+        const float2 q = reinterpret_cast<const float2*>(a.st_in.s1)[ii];
+        s1 = make_float4(q.x, q.y, 0.0f, 0.0f);
+      }
     } else {
       s1 = a.st_in.s1[ii];
     }
@@ -238,7 +254,7 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
   if (!B0) {
     if (PASS != 1) EZ_PIN4(ro4);
     EZ_PIN4(s0);
-    EZ_PIN4(s1);
+    if (!lean) EZ_PIN4(s1);
     if ((!COMPACT || STAGE >= 2) && !MIS1) EZ_PIN4(s2);
     if (!COMPACT && !MIS1) EZ_PIN4(s3);
     if (MIS) {
@@ -247,6 +263,15 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
     }
   }
 #undef EZ_PIN4
+  if (lean) {
+    // s1 = (bits(sample slot), bits(tri0)) as the s1 array held them.  tri0 is the origin's w, which the first pass -- it loads no
+    // origin -- fetches for the lanes whose primary hit emits alone: the light's pixels.  An empty slot (all zeros) decodes to
+    // slot 0 without a triangle and is dropped by shade_body on rd4.w == 0 before either is used.
+    const uint32_t w = __float_as_uint(rd4.w);
+    uint32_t t0 = 0xffffffffu;
+    if (w & LEAN_EMITS) t0 = __float_as_uint(PASS == 1 ? reinterpret_cast<const float*>(a.rq_in.o + ii)[3] : ro4.w);
+    s1 = make_float4(__uint_as_float(w & LEAN_SLOT_MASK), __uint_as_float(t0), 0.0f, 0.0f);
+  }
   in.rd4 = rd4;
   in.ro4 = ro4;
   in.s0 = s0;
@@ -500,9 +525,16 @@ EZD bool shade_path(const WfArgs& a, const uint32_t i, bool live, Counters& ctr,
 // state into stage 1 (see PathState)
 template <bool MIS, int FORM>
 EZD void shade_store(const WfArgs& a, const ShadeOut& o, const uint32_t k) {
+  float ow = 0.0f, dw = 1.0f; // the w components of the path's ray (FORM 1, lean: the state's two words -- see LEAN_LIVE)
   if (FORM == 1) {
     a.st_out.s0[k] = make_float4(o.f_r.x, o.f_r.y, o.f_r.z, o.cosine);
-    reinterpret_cast<float2*>(a.st_out.s1)[k] = make_float2(__uint_as_float(o.sslot), __uint_as_float(o.tri0));
+    if (a.lean1) {
+      const bool emits = o.tri0 != 0xffffffffu;
+      ow = emits ? __uint_as_float(o.tri0) : 0.0f;
+      dw = __uint_as_float(LEAN_LIVE | (emits ? LEAN_EMITS : 0u) | o.sslot);
+    } else {
+      reinterpret_cast<float2*>(a.st_out.s1)[k] = make_float2(__uint_as_float(o.sslot), __uint_as_float(o.tri0));
+    }
   } else if (FORM == 3) {
     a.st_out.s0[k] = make_float4(o.f_r.x, o.f_r.y, o.f_r.z, o.cosine);
     a.st_out.s1[k] = make_float4(o.pdf, __uint_as_float(o.sslot), __uint_as_float(o.seed), __uint_as_float(o.tri0));
@@ -523,8 +555,8 @@ EZD void shade_store(const WfArgs& a, const ShadeOut& o, const uint32_t k) {
     a.rq_out.d[2u * k] = make_float4(o.shadowL.x, o.shadowL.y, o.shadowL.z, (o.flags & FLAG_SHADOW_SHOT) ? 1.0f : 0.0f);
     a.rq_out.d[2u * k + 1u] = make_float4(o.rayL.x, o.rayL.y, o.rayL.z, shoot ? 1.0f : 0.0f);
   } else {
-    a.rq_out.o[k] = make_float4(o.P.x, o.P.y, o.P.z, 0.0f);
-    a.rq_out.d[k] = make_float4(o.rayL.x, o.rayL.y, o.rayL.z, 1.0f);
+    a.rq_out.o[k] = make_float4(o.P.x, o.P.y, o.P.z, ow);
+    a.rq_out.d[k] = make_float4(o.rayL.x, o.rayL.y, o.rayL.z, dw);
   }
 }
 template <int INTEG, int STAGE>
@@ -693,8 +725,11 @@ struct PathLogArgs {
   const int2* hits;      // hit records of the stage's ray queue
   const float4* rq_d;    // its ray directions (.w = 0: slot not shot)
   const float4* st_slot; // the path-state array that holds bits(sample slot) for this stage, and in which component
-  int32_t slot_comp;     //   (general state: s2.w; compact state of integrator 50: float2 s1[i].x into stage 1, s1.w later)
+  int32_t slot_comp;     //   (general state: s2.w; compact state of integrator 50: into stage 1 the queue's direction w -- lean -- or
+                         //   float2 s1[i].x, s1.w later)
   int32_t slot_stride;   //   floats per path in that array (4; 2 for the compact state into stage 1)
+  uint32_t slot_mask;    //   the word's bits that are the slot (all of them; LEAN_SLOT_MASK for the lean state into stage 1, where the
+                         //   array is the queue's directions, the component is w, and a zero word is an empty slot)
   const uint32_t* n_in;  // paths in the queue (stage >= 1)
   uint32_t n_slots;      // stage 0: pixel-samples of the chunk
   int32_t bounce;        // stage index b (0 = primary rays)
@@ -715,8 +750,9 @@ __global__ __launch_bounds__(BLOCK) void pathlog_kernel(PathLogArgs a) {
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   const uint32_t n = a.bounce == 0 ? a.n_slots : *a.n_in;
   if (i >= n) return;
-  const uint32_t sslot = a.bounce == 0 ? queue_to_sample(i, a.div_sub, a.scatter, a.scatter_shift)
-                                       : __float_as_uint(reinterpret_cast<const float*>(a.st_slot)[(size_t)i * a.slot_stride + a.slot_comp]);
+  const uint32_t word = a.bounce == 0 ? 0u : __float_as_uint(reinterpret_cast<const float*>(a.st_slot)[(size_t)i * a.slot_stride + a.slot_comp]);
+  if (a.bounce != 0 && a.slot_mask != 0xffffffffu && word == 0u) return; // (lean state: an empty slot)
+  const uint32_t sslot = a.bounce == 0 ? queue_to_sample(i, a.div_sub, a.scatter, a.scatter_shift) : (word & a.slot_mask);
   int x, y;
   uint32_t frame;
   slot_to_pixel(a.blocks, a.div_blocks, sslot, a.frame_first, x, y, frame);
