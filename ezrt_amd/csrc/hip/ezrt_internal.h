@@ -182,6 +182,8 @@ struct Tuning {
   int refill_min = 24;     // free lanes a wave waits for before it runs its refill code (publish results, adopt the
                            // prefetched ray, prefetch the next): wave-wide code for per-lane events, so batch it (+9 %)
   int lazy_dir = 1;        // the primary stage's first shading pass reads a ray's direction only after its hit record said "miss"
+  int regen_dir = 1;       // the primary stage's shading passes of a whole power-of-two frame (gen_whole_mode 2; integrators 50 / 51 / 52) generate
+                           // a ray's direction again from its queue position, and the trace launch does not store it; 0: stored and read
   int refill_min_rel = 40; // ... of the primary stage's launch (rays with a common origin; 0: refill_min): its refill also generates the rays
                            // (C2 +1.8 %, C4 +3.1 %, C3 / C5 +0.3 % over 24)
   int rel_boxes = 1;       // primary rays traverse boxes already translated by the eye
@@ -269,6 +271,7 @@ const TuningName kTuning[] = {{"megakernel", &Tuning::megakernel, 0, 1},
                               {"refill_min", &Tuning::refill_min, 1, 64},
                               {"refill_min_rel", &Tuning::refill_min_rel, 0, 64},
                               {"lazy_dir", &Tuning::lazy_dir, 0, 1},
+                              {"regen_dir", &Tuning::regen_dir, 0, 1},
                               {"static_pct", &Tuning::static_pct, 0, 95},
                               {"scatter", &Tuning::scatter, 0, 8},
                               {"wide4", &Tuning::wide4, 0, 1},

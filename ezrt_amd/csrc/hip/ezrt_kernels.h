@@ -142,13 +142,19 @@ EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, 
   y = (int)(by * 16u + (wave >> 1) * 8u + (lane >> 3));
   frame = g.frame_first + fk;
 }
+// seed: the RNG state after the two jitter draws (camera_dir_scaled), what the MIS integrators' primary stage starts from
 template <bool POW2>
-EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot) {
+EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot, uint32_t& seed) {
   int x, y;
-  uint32_t frame, seed;
+  uint32_t frame;
   slot_to_pixel_whole<POW2>(g, qslot, x, y, frame);
   const f3 dir = camera_dir_scaled<POW2>(g.sw, g.sh, g.rot, (uint32_t)x, (uint32_t)y, frame, seed);
   return make_float4(dir.x, dir.y, dir.z, 1.0f);
+}
+template <bool POW2>
+EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot) {
+  uint32_t seed;
+  return primary_dir_whole<POW2>(g, qslot, seed);
 }
 
 template <int INTEG, bool FULLCTR, bool PATHLOG>

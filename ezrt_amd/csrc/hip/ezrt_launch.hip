@@ -216,6 +216,19 @@ int gen_whole_mode(const EzrtScene* s, const EzrtRenderParams& p) {
     if (s->blocks_host[k].x != (k % bw) * 16 || s->blocks_host[k].y != (k / bw) * 16) return false;
   return true;
 }
+// EZRT_REGEN_PARTS: the three parts of the regen_dir route, each compiled in or out (A/B builds, tools/build_variant.sh): bit 0 the first pass,
+// bit 1 the second, bit 2 the trace launch without the store (needs both).
+#ifndef EZRT_REGEN_PARTS
+#define EZRT_REGEN_PARTS 7
+#endif
+// Whether the primary stage's shading passes of a chunk generate their rays' directions again instead of reading them from the queue
+// (knob regen_dir): 0 no -- every call but a whole power-of-two frame of integrators 50 / 51 / 52, the audit route (plog), the per-wave
+// log; 1 yes, the trace launch still stores them (an A/B build without all three parts); 2 yes, and the trace launch does not store.
+int regen_dir_mode(const EzrtScene* s, const EzrtRenderParams& p, bool gen_primary, bool audit) {
+  if (!s->tune.regen_dir || !gen_primary || audit || s->instr > 0 || s->tune.debug_stages >= 2) return 0;
+  if (p.integrator < EZRT_INTEGRATOR_P5_SOBOL || gen_whole_mode(s, p) != 2) return 0;
+  return (EZRT_REGEN_PARTS & 7) == 7 ? 2 : ((EZRT_REGEN_PARTS & 3) ? 1 : 0);
+}
 int debug_stages_gen_mode(const EzrtScene* s, const EzrtRenderParams& p) { // (debug_stages = 2 runs the LOG instances: general)
   return s->tune.debug_stages >= 2 ? 0 : gen_whole_mode(s, p);
 }
@@ -226,8 +239,9 @@ int debug_stages_gen_mode(const EzrtScene* s, const EzrtRenderParams& p) { // (d
 //   bounce stages drawn in the scattered order (GS): the default schedule only
 //   LOG (debug_stages = 2): the default schedule's five kernels
 //   whole frames (gen_whole_mode; the default schedule without LOG only): the REL + GEN pair again with the whole-frame generator,
-//   and once more with the power-of-two one -- four instances
-// whole: gen_whole_mode of the launch, i.e. which member of TraceQ4Args' generator union fill_traceq4_args filled
+//   once more with the power-of-two one, and that one again without the store of the directions (3: regen_dir_mode) -- six instances
+// whole: gen_whole_mode of the launch, i.e. which member of TraceQ4Args' generator union fill_traceq4_args filled; 3 = 2, and the
+// stage's shading passes generate the directions again
 template <bool REL, bool GEN, bool SEMI, bool GS>
 void launch_traceq4_p(int prune, bool log, int wps, int whole, dim3 grid, size_t lds, hipStream_t st, const TraceQ4Args& q) {
   const dim3 block(BLOCK);
@@ -236,10 +250,12 @@ void launch_traceq4_p(int prune, bool log, int wps, int whole, dim3 grid, size_t
     if constexpr (REL && GEN) {
       if (whole && !log) {
         if (wps >= 7) {
-          if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
+          if (whole == 3) hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 3>), grid, block, lds, st, q);
+          else if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
           else hipLaunchKernelGGL((traceq4_kernel<7, REL, false, 2, GEN, SEMI, GS, 1>), grid, block, lds, st, q);
         } else {
-          if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
+          if (whole == 3) hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 3>), grid, block, lds, st, q);
+          else if (whole == 2) hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 2>), grid, block, lds, st, q);
           else hipLaunchKernelGGL((traceq4_kernel<6, REL, false, 2, GEN, SEMI, GS, 1>), grid, block, lds, st, q);
         }
         return;
@@ -293,6 +309,22 @@ constexpr size_t QHEADS_WORDS = 81 * QHEAD_SLOT_WORDS; // launch slots of reserv
 // gen (or NULL): the chunk's stage-0 arguments when the launch generates its primary rays itself (needs rel)
 // returns gen_whole_mode: which generator's arguments were filled, and so which instance must run
 // ovf: the scratch set's spill area of the traversal stacks (Pipe::ovf: [grid lanes][max(OVF_CAP, ovf_cap4(s))], indexed with a stride of ovf_cap4(s))
+// the whole-frame generator's arguments for the chunk whose stage-0 arguments are `gen` (whole: its gen_whole_mode, 1 or 2)
+void fill_gen_whole(const EzrtScene* s, const WfArgs& gen, int whole, GenWhole& w) {
+  const uint32_t bw = (uint32_t)gen.p.width / 16u, n_sub = gen.div_sub.d;
+  assert(blocks_are_raster(s, gen.p));
+  (void)s;
+  for (int k = 0; k < 12; k++) w.rot[k] = gen.p.camera_rotate[k];
+  w.sw = whole == 2 ? 1.0f / (float)gen.p.width : (float)gen.p.width;
+  w.sh = whole == 2 ? 1.0f / (float)gen.p.height : (float)gen.p.height;
+  w.div_sub = gen.div_sub;
+  w.div_bw = make_fastdiv(bw);
+  w.sh_sub = (uint32_t)__builtin_ctz(n_sub); // (whole == 2: both are powers of two)
+  w.sh_bw = (uint32_t)__builtin_ctz(bw);
+  w.scatter = gen.scatter;
+  w.scatter_shift = gen.scatter_shift;
+  w.frame_first = gen.frame_first;
+}
 int fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, const WfArgs* gen, uint32_t* ovf, TraceQ4Args& A) {
   static_assert(sizeof(GenWhole) <= sizeof(TraceQ4Args::GenGeneral), "the whole-frame generator's arguments lie inside the general one's");
   memset(&A.gen, 0, sizeof A.gen);
@@ -301,19 +333,7 @@ int fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& 
   A.gen.scatter_shift = 6u;
   const int whole = (gen && rel && !t.wave_log) ? gen_whole_mode(s, gen->p) : 0;
   if (whole) {
-    GenWhole& w = A.gen_whole;
-    const uint32_t bw = (uint32_t)gen->p.width / 16u, n_sub = gen->div_sub.d;
-    assert(blocks_are_raster(s, gen->p));
-    for (int k = 0; k < 12; k++) w.rot[k] = gen->p.camera_rotate[k];
-    w.sw = whole == 2 ? 1.0f / (float)gen->p.width : (float)gen->p.width;
-    w.sh = whole == 2 ? 1.0f / (float)gen->p.height : (float)gen->p.height;
-    w.div_sub = gen->div_sub;
-    w.div_bw = make_fastdiv(bw);
-    w.sh_sub = (uint32_t)__builtin_ctz(n_sub); // (whole == 2: both are powers of two)
-    w.sh_bw = (uint32_t)__builtin_ctz(bw);
-    w.scatter = gen->scatter;
-    w.scatter_shift = gen->scatter_shift;
-    w.frame_first = gen->frame_first;
+    fill_gen_whole(s, *gen, whole, A.gen_whole);
   } else if (gen) {
     A.gen.p = gen->p;
     A.gen.blocks = gen->blocks;
@@ -351,10 +371,14 @@ int fill_traceq4_args(const EzrtScene* s, const TraceCfg& c4, const TraceQArgs& 
   A.steal_bound = s->tune.steal_bound ? 1u : 0u;
   return whole;
 }
-void launch_traceq4_cfg(EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, hipStream_t st, const WfArgs* gen, uint32_t* ovf) {
+// keep_dirs (with gen): the launch leaves the directions it generates in the queue; false -- regen_dir_mode 2 of a whole power-of-two
+// frame alone -- only those of the rays it hands to the redo list
+void launch_traceq4_cfg(EzrtScene* s, const TraceCfg& c4, const TraceQArgs& t, const float4* rel, hipStream_t st, const WfArgs* gen, uint32_t* ovf,
+                        bool keep_dirs = true) {
   TraceQ4Args A;
   const int whole = fill_traceq4_args(s, c4, t, rel, gen, ovf, A);
-  if (rel && gen) launch_traceq4_rel<true, true>(s, c4, A, whole, st);
+  assert(keep_dirs || whole == 2);
+  if (rel && gen) launch_traceq4_rel<true, true>(s, c4, A, (whole == 2 && !keep_dirs) ? 3 : whole, st);
   else if (rel) launch_traceq4_rel<true, false>(s, c4, A, 0, st);
   else launch_traceq4_rel<false, false>(s, c4, A, 0, st);
 }
@@ -417,16 +441,29 @@ void launch_shade_split_ib(const WfArgs& a, dim3 grid, dim3 grid_hit, hipStream_
   hipLaunchKernelGGL((shade_hit_kernel<INTEG, false, STAGE>), grid_hit, dim3(SHADE_BLOCK), 0, st, a);
 }
 template <int INTEG>
-void launch_shade_i(const WfArgs& a, bool full, dim3 grid, hipStream_t st) {
-  if (!full && a.bounce == 0) launch_shade_split_ib<INTEG, 0>(a, grid, grid, st);
+void launch_shade_regen_i(const WfArgs& a, dim3 grid, hipStream_t st) {
+  if constexpr (INTEG >= EZRT_INTEGRATOR_P5_SOBOL) {
+    if (EZRT_REGEN_PARTS & 1) hipLaunchKernelGGL((shade_miss_kernel<INTEG, false, STAGE_REGEN>), grid, dim3(SHADE_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((shade_miss_kernel<INTEG, false, 0>), grid, dim3(SHADE_BLOCK), 0, st, a);
+    if (EZRT_REGEN_PARTS & 2) hipLaunchKernelGGL((shade_hit_kernel<INTEG, false, STAGE_REGEN>), grid, dim3(SHADE_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((shade_hit_kernel<INTEG, false, 0>), grid, dim3(SHADE_BLOCK), 0, st, a);
+  } else {
+    launch_shade_split_ib<INTEG, 0>(a, grid, grid, st);
+  }
+}
+template <int INTEG>
+void launch_shade_i(const WfArgs& a, bool full, bool regen, dim3 grid, hipStream_t st) {
+  if (!full && a.bounce == 0 && regen) launch_shade_regen_i<INTEG>(a, grid, st);
+  else if (!full && a.bounce == 0) launch_shade_split_ib<INTEG, 0>(a, grid, grid, st);
   else if (!full && a.bounce == 1) launch_shade_split_ib<INTEG, 1>(a, grid, grid, st);
   else launch_shade_fused_i<INTEG>(a, full, grid, st);
 }
 // (The redo launch of a stage -- exact ties beyond two candidates, rays that are not tame, spill areas that ran full: normally EMPTY -- runs in
 // line before any shading.  Until round 6 a knob could put it on a side stream under the first shading pass: the two measured the same, and the
 // cross-stream waits it needed can enter a slow state on this runtime (ezrt_streams.h); removed with its stream and events.)
-void launch_shade(const WfArgs& a, bool full, dim3 grid, hipStream_t st) {
-  with_integrator(a.p.integrator, [&](auto I) { launch_shade_i<decltype(I)::value>(a, full, grid, st); });
+// regen: the primary stage's passes generate their directions again (regen_dir_mode > 0; stage 0 only)
+void launch_shade(const WfArgs& a, bool full, bool regen, dim3 grid, hipStream_t st) {
+  with_integrator(a.p.integrator, [&](auto I) { launch_shade_i<decltype(I)::value>(a, full, regen, grid, st); });
 }
 
 // The queues of one chunk (n_slots pixel-samples in flight).  hipErrorOutOfMemory leaves the pipe consistent (a DevBuf that
@@ -582,7 +619,10 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
   const bool gen_primary = wide && s->tune.rel_boxes && s->tune.gen_primary;
   a.all_owned = (p->shard_count <= 1 && p->x0 == 0 && p->y0 == 0 && p->x1 == p->width && p->y1 == p->height && p->width % 16 == 0 &&
                  p->height % 16 == 0 && s->tune.lazy_dir) ? 1u : 0u;
-  a.gen_primary = 0u; // (the shading passes read the directions the trace launch stored: see traceq4_kernel GEN)
+  // (the shading passes read the directions the trace launch stored -- see traceq4_kernel GEN -- or, regen > 0, generate them again)
+  const int regen = regen_dir_mode(s, *p, gen_primary, plog != nullptr);
+  memset(&a.gen_whole, 0, sizeof a.gen_whole);
+  if (regen) fill_gen_whole(s, a, 2, a.gen_whole);
   // integrator 50's state into stage 1 without the s1 array while a sample slot fits its bits (any chunk of the knob's range; a single
   // frame of more pixel-samples keeps the array).  Read by the compact state's code alone.
   const bool lean1 = n_slots <= ((size_t)1 << LEAN_SLOT_BITS);
@@ -596,6 +636,7 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
   if (s->tune.debug_stages && wide && gen_primary) {
     static const char* const kGen[] = {"general", "whole frame", "whole frame, power-of-two"};
     fprintf(stderr, "[ezrt] primary generator: %s\n", kGen[debug_stages_gen_mode(s, *p)]);
+    fprintf(stderr, "[ezrt] primary directions: %s\n", regen ? "regenerated" : "stored");
   }
 
   const Tuning& tu = s->tune;
@@ -652,7 +693,8 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
     {
       if (wide) {
         const bool rel = b == 0 && tu.rel_boxes;
-        launch_traceq4_cfg(s, rel ? cfg4_rel : cfg4_abs, t, rel ? pp.inner4_rel.p : nullptr, st, (rel && gen_primary) ? &a : nullptr, pp.ovf.p);
+        launch_traceq4_cfg(s, rel ? cfg4_rel : cfg4_abs, t, rel ? pp.inner4_rel.p : nullptr, st, (rel && gen_primary) ? &a : nullptr, pp.ovf.p,
+                           !(rel && regen == 2));
       }
       else launch_traceq_cfg(s, cfg, t, false, st);
       if (t.steal || wide) launch_redo(s, cfg, t, pp.qheads.p + (size_t)(40 + b) * HEAD_SLOT, st);
@@ -708,7 +750,7 @@ int wavefront_chunk(EzrtScene* s, Pipe& pp, const EzrtRenderParams* p, int nb, u
     a.bounce = b;
     a.defer_list = pp.defer_list.p;
     a.defer_count = pp.defer_count.p;
-    launch_shade(a, full, dim3(shade_grid), st);
+    launch_shade(a, full, b == 0 && regen > 0, dim3(shade_grid), st);
     if (debug_stages) { // diagnostic only: per-stage queue sizes and counters (synchronises)
       uint32_t q[2] = {0, 0};
       unsigned long long c[EZRT_CTR_COUNT];

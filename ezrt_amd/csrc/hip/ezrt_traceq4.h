@@ -196,7 +196,7 @@ EZD void chunk_prologue(const ChunkPrologue& g, uint32_t tid, uint32_t n_threads
 // GEN (with REL): primary rays are generated in the refill block -- seed, AA jitter, camera rotation, normalize:
 // primary_dir, the code raygen_kernel runs -- and stored to the queue from here (the stage's shading passes and a redo
 // launch read them there: recomputing the direction in the shading kernels cost them 30 us each on C2, more than the
-// 16-byte read).  What goes away is raygen_kernel's launch and this kernel's read of the queue: the stores ride on a
+// 16-byte read -- with the general generator; the whole-frame power-of-two one is cheap enough: WHOLE == 3 below).  What goes away is raygen_kernel's launch and this kernel's read of the queue: the stores ride on a
 // memory system the VALU-bound traversal leaves idle.
 // Which of two triangles with the SAME hit distance does the reference's hitBVH keep?  The first one it finds (strict <,
 // P5/fsh:247, 274), i.e. the one whose leaf comes first in its depth-first order: near child first at every node, ties
@@ -241,7 +241,9 @@ EZD bool tie_precedes(const TraceQ4Args& A, int32_t tri_a, int32_t tri_b, f3 S, 
 // record holds {-1, t_max} or A hit below t_max; rays sent to the redo list come back with their closest hit, and the query's unpack
 // kernel answers t < t_max for all of them.
 // WHOLE (with GEN): 0 the general generator; 1 the frame is whole (GenWhole: no ownership test, no blocks[] load); 2 ... and its
-// width and height are powers of two (shifts for the index divisions, exact reciprocals for camera_dir's four divisions).
+// width and height are powers of two (shifts for the index divisions, exact reciprocals for camera_dir's four divisions); 3 = 2 without
+// the store of the direction: the stage's shading passes generate it again (shade_load REGEN), and only a ray handed to the redo
+// list -- whose launch reads its rays from the queue -- has its direction stored, by to_redo, from the registers that hold it.
 // The generator is ~400 of this kernel's 1 440 static VALU instructions and all of it sits in the refill block, which also
 // carries most of the kernel's SGPR spills: the fewer launch-uniform values it reads, the fewer v_readlane / v_writelane.
 template <bool REL, bool LOG, int PRUNE, bool GEN, bool SEMI = false, bool GS = false, bool OCC = false, int WHOLE = 0>
@@ -307,6 +309,8 @@ EZD void traceq4_body(const TraceQ4Args& A) {
     prune_t = (best_t + pdelta) * PRUNE_REL;
   };
   auto to_redo = [&](uint32_t s) { // (rare) the in-order binary kernel decides this ray
+    // (WHOLE == 3: the queue has no direction yet.  Every caller holds the ray of slot s in d -- its own, or as a thief its victim's)
+    if constexpr (GEN && WHOLE == 3) a.rq.d[s] = make_float4(d.x, d.y, d.z, 1.0f);
     if (atomicExch(&a.redo_flag[s], 1u) == 0u) a.redo_slots[atomicAdd(a.redo_count, 1u)] = s;
     // until it has, the record says so: key (t bits 0, tri HIT_PENDING) is below every real key, so later atomicMin
     // contributions of a split ray cannot replace it; the redo launch overwrites it with a plain store
@@ -449,9 +453,9 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           nx_slot = rs;
           if (!REL) nx_o = a.const_origin == 1u ? make_float4(a.origin[0], a.origin[1], a.origin[2], 0.0f) : a.rq.o[rs >> (a.const_origin >> 1)];
           if (GEN) { // generate, and leave the direction in the queue for the stage's shading passes (and a redo launch)
-            if (WHOLE) nx_d = primary_dir_whole<WHOLE == 2>(A.gen_whole, rs);
+            if (WHOLE) nx_d = primary_dir_whole<WHOLE >= 2>(A.gen_whole, rs);
             else nx_d = primary_dir(A.gen.p, A.gen.blocks, A.gen.div_blocks, A.gen.div_sub, A.gen.scatter, A.gen.scatter_shift, A.gen.frame_first, rs);
-            a.rq.d[rs] = nx_d;
+            if (WHOLE != 3) a.rq.d[rs] = nx_d;
           } else {
             nx_d = a.rq.d[rs];
           }

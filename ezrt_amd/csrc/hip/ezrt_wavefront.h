@@ -78,8 +78,11 @@ struct WfArgs {
   uint32_t scatter;        // queue order of the primary rays: see queue_to_sample (1 = identity)
   uint32_t scatter_shift;  // scattered granule = 1 << scatter_shift slots (6: 8x8 sub-block, 8: 16x16 block, 5: 8x4 pixels)
   uint32_t all_owned;      // 1: every queue position of stage 0 is a pixel-sample of this call (one shard, whole 16x16 blocks)
-  uint32_t gen_primary;    // 1: queue 0 holds no directions -- stage 0 recomputes its ray from the queue position (primary_dir)
   uint32_t lean1;          // 1: integrator 50's state into stage 1 has no s1 array (PathState, "lean"): the chunk's sample slots fit LEAN_SLOT_BITS
+  // The REGEN instances of the primary stage's passes (shade_miss_kernel / shade_hit_kernel <.., STAGE_REGEN>) alone read this: the ray of
+  // queue position i is primary_dir_whole<true>(gen_whole, i), the function and the arguments of the trace launch that made it
+  // (TraceQ4Args::gen_whole).  At the struct's end: an instance loads only the kernel arguments it reads, so the others pay nothing.
+  GenWhole gen_whole;
 };
 // Integrator 50, state into stage 1, lean form: the two words of s1 ride in the ray's own records, whose w components the render's
 // trace launches do not compute with (the direction's w is only compared with 0, the origin's w is not read).
@@ -197,7 +200,12 @@ struct ShadeIn { // what stage b reads for one path (from the queues)
   int2 h, sh;
 };
 // entry (PASS 2 of the split kernels, or NULL): the list entry shade_miss_kernel wrote for this path
-template <int INTEG, int PASS, int STAGE>
+// REGEN (the primary stage of a whole power-of-two frame: knob regen_dir): the queue holds no directions -- the trace launch that
+// generated them did not store them (traceq4_kernel WHOLE == 3) -- and the ray of queue position i is generated again, by the
+// function that launch ran with the arguments it had: the same bits.  The second pass does that here, for every path (each needs its
+// direction, and the arithmetic runs under the loads in flight); the first pass inside the branch of a ray that left the scene
+// (shade_body), as lazy_dir reads it.  A template parameter, never a uniform branch: the branch alone cost these passes 3-5 us.
+template <int INTEG, int PASS, int STAGE, bool REGEN = false>
 EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn& in, const uint4* entry = nullptr) {
   constexpr bool MIS = integ_mis<INTEG>();
   constexpr bool B0 = (STAGE == 0);
@@ -212,8 +220,9 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
   const bool from_entry = PASS == 2 && entry && (int32_t)entry->y != HIT_PENDING && (!MIS || (int32_t)entry->w != HIT_PENDING);
   int2 h = from_entry ? make_int2((int32_t)entry->y, (int32_t)entry->z) : a.hits[rslot];
   float4 rd4;
-  if (B0 && a.gen_primary) {
-    rd4 = primary_dir(a.p, a.blocks, a.div_blocks, a.div_sub, a.scatter, a.scatter_shift, a.frame_first, rslot);
+  static_assert(!REGEN || (B0 && PASS != 0), "the regenerating instances are the primary stage's two passes");
+  if constexpr (REGEN) {
+    rd4 = make_float4(0.0f, 0.0f, 0.0f, 1.0f); // (every queue position of a whole frame holds a ray: w = 1; the second pass: below)
   } else if (B0 && PASS == 1 && a.all_owned) {
     // the first pass of the primary stage only looks at the direction of a ray that left the scene (the env lookup): 40 %
     // of C2's 268 MB of directions are not read here (a second round trip for the others; the kernel is HBM-bound)
@@ -245,11 +254,16 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
       sh = from_entry ? make_int2((int32_t)entry->w, 0) : a.hits[2u * ii];
     }
   }
+  if constexpr (REGEN && PASS == 2) { // the RNG state after the generator's two draws goes where the general state keeps a path's seed
+    uint32_t seed;
+    rd4 = primary_dir_whole<true>(a.gen_whole, rslot, seed);
+    s3.w = __uint_as_float(seed);
+  }
   // Pin the loads here: left alone, the compiler sinks every one of them into the branch that first uses
   // it and narrows it to the component used there (rd4.w, then h.x, then rd4.xyz ...), i.e. a chain of
   // three or four dependent memory round trips per path instead of one.
 #define EZ_PIN4(v) asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w))
-  EZ_PIN4(rd4);
+  if constexpr (!REGEN) EZ_PIN4(rd4);
   asm volatile("" : "+v"(h.x), "+v"(h.y));
   if (!B0) {
     if (PASS != 1) EZ_PIN4(ro4);
@@ -284,7 +298,7 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
 }
 
 // `i` is only used by stage 0 (queue position -> sample slot)
-template <int INTEG, bool FULLCTR, int PASS, int STAGE>
+template <int INTEG, bool FULLCTR, int PASS, int STAGE, bool REGEN = false>
 EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn& in, Counters& ctr, uint32_t& n_samples,
                     ShadeOut& o) {
   constexpr bool P5TRI = (INTEG >= 50);
@@ -306,7 +320,7 @@ EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn&
   bool done = false;
   if (!live) return false;
   f3 colour = mk(0, 0, 0);
-  const f3 rd = mk(rd4.x, rd4.y, rd4.z);
+  f3 rd = mk(rd4.x, rd4.y, rd4.z);
   if (B0) {
     sslot = queue_to_sample(i, a.div_sub, a.scatter, a.scatter_shift);
     if (rd4.w == 0.0f) {
@@ -315,6 +329,10 @@ EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn&
       if (PASS != 2) n_samples = n_samples + 1;
       if (PASS == 1 && h.x == HIT_PENDING) return true; // answer still with the redo launch: decided in the second pass
       if (h.x < 0) { // primary miss: P5/fsh:931-933
+        if constexpr (REGEN && PASS == 1) { // (the first pass wants the direction of a ray that left the scene alone: see shade_load)
+          const float4 g = primary_dir_whole<true>(a.gen_whole, i);
+          rd = mk(g.x, g.y, g.z);
+        }
         colour = hdr_color<FULLCTR>(sc, rd, p.env_clamp, ctr);
         done = true;
       } else {
@@ -324,7 +342,9 @@ EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn&
         // compact state: the primary hit's triangle is carried only when its emission has a set bit -- a later stage
         // then re-reads Le0 from its material, and every other path (all but the light's pixels) skips that gather
         tri0 = (__float_as_uint(Le0.x) | __float_as_uint(Le0.y) | __float_as_uint(Le0.z)) ? (uint32_t)h.x : 0xffffffffu;
-        if (INTEG != EZRT_INTEGRATOR_P5_SOBOL) { // (integrator 50 draws nothing after ray generation: Sobol + CP only)
+        if constexpr (REGEN) {
+          seed = __float_as_uint(s3.w); // (the generator's own, camera_dir_scaled: see shade_load; integrator 50 does not read it)
+        } else if (INTEG != EZRT_INTEGRATOR_P5_SOBOL) { // (integrator 50 draws nothing after ray generation: Sobol + CP only)
           // RNG state after the two anti-aliasing draws of ray generation (P5/fsh:315-318, 920-921)
           int x0, y0;
           uint32_t f0;
@@ -576,8 +596,12 @@ EZD void shade_emit(const WfArgs& a, const ShadeOut& o, uint32_t* alloc_lds) {
 // k of the second kernel takes the list of workgroup k of the first): no global atomic and no barrier
 // in the first kernel -- one list-tail atomic per 512 paths was 32 k atomics on the primary stage, four
 // times what the counter sustains in the time the kernel needs.
-template <int INTEG, bool FULLCTR, int STAGE>
+// STAGE: 0, 1, 2 as for shade_body; STAGE_REGEN = stage 0 with regenerated directions (shade_load REGEN)
+constexpr int STAGE_REGEN = 3;
+template <int INTEG, bool FULLCTR, int STAGE_>
 __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MISS_WAVES) void shade_miss_kernel(WfArgs a) {
+  constexpr bool REGEN = (STAGE_ == STAGE_REGEN);
+  constexpr int STAGE = REGEN ? 0 : STAGE_;
   constexpr bool B0 = (STAGE == 0);
   __shared__ uint32_t list_tail;
   const uint32_t n_in = B0 ? a.n_slots : *a.n_in;
@@ -592,8 +616,8 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MISS_WAVES) void shade_miss_kern
   for (uint32_t k = 0, i = blockIdx.x * SHADE_BLOCK + threadIdx.x; k < iters; k++, i += stride) {
     ShadeOut o;
     ShadeIn in;
-    shade_load<INTEG, 1, STAGE>(a, i, i < n_in, in);
-    const bool deferred = shade_body<INTEG, FULLCTR, 1, STAGE>(a, i, i < n_in, in, ctr, n_samples, o);
+    shade_load<INTEG, 1, STAGE, REGEN>(a, i, i < n_in, in);
+    const bool deferred = shade_body<INTEG, FULLCTR, 1, STAGE, REGEN>(a, i, i < n_in, in, ctr, n_samples, o);
     const unsigned long long m = ballot(deferred);
     if (m) {
       uint32_t base = 0;
@@ -618,13 +642,15 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MISS_WAVES) void shade_miss_kern
 }
 
 // launched with the grid of shade_miss_kernel
-template <int INTEG, bool FULLCTR, int STAGE>
 // (The primary stage of the MIS integrators is compiled for 6 waves/SIMD, i.e. <= 80 VGPRs: with 8-wave workgroups the 83
 // registers it would take mean two workgroups per CU, 80 mean three -- C4 +2 %.  Their later stages want 116-122 and
 // would spill 50-100 registers; integrator 50 (81 VGPRs, two workgroups per CU) measures the same at 6 and at 7 waves --
 // 76 and 72 registers, three workgroups: C2 and C3 within 0.3 % (round 3) -- and is left at 4.)
-__global__ __launch_bounds__(SHADE_BLOCK, (integ_mis<INTEG>() && STAGE == 0) ? 6 : 4) void shade_hit_kernel(WfArgs a) {
+template <int INTEG, bool FULLCTR, int STAGE_>
+__global__ __launch_bounds__(SHADE_BLOCK, (integ_mis<INTEG>() && (STAGE_ == 0 || STAGE_ == STAGE_REGEN)) ? 6 : 4) void shade_hit_kernel(WfArgs a) {
   __shared__ uint32_t alloc_lds[SHADE_BLOCK / 64 + 1];
+  constexpr bool REGEN = (STAGE_ == STAGE_REGEN);
+  constexpr int STAGE = REGEN ? 0 : STAGE_;
   constexpr bool B0 = (STAGE == 0);
   constexpr int FORM = store_form<INTEG, STAGE>();
   constexpr bool MIS = integ_mis<INTEG>();
@@ -635,8 +661,8 @@ __global__ __launch_bounds__(SHADE_BLOCK, (integ_mis<INTEG>() && STAGE == 0) ? 6
   const uint32_t cnt = a.defer_count[blockIdx.x];
   auto shade_entry = [&](const uint4 e, Counters& c, uint32_t& ns, ShadeOut& o) {
     ShadeIn in;
-    shade_load<INTEG, 2, STAGE>(a, e.x, true, in, &e);
-    shade_body<INTEG, FULLCTR, 2, STAGE>(a, e.x, true, in, c, ns, o);
+    shade_load<INTEG, 2, STAGE, REGEN>(a, e.x, true, in, &e);
+    shade_body<INTEG, FULLCTR, 2, STAGE, REGEN>(a, e.x, true, in, c, ns, o);
   };
   Counters ctr = {0, 0, 0, 0, 0, 0, 0};
   uint32_t n_samples = 0;
