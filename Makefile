@@ -74,6 +74,9 @@ negctl:
 # library is also what runs fill_rows' insertion path in tests/test_gpu_overlap_list.py, which the compiled insert_max = 0 never takes.
 OL_OTHER_OBJ = $(filter-out build/hip/ezrt_queries.o,$(HIP_OBJ))
 OL_VARIANTS = i16_t4096 i64_t4096 i0_t2048 i0_t8192 nosort
+# (the same rule builds the measurement variant of the mesh orientation, ezrt_orient_kernels.h: one atomic per lane in the volume
+# launch; EZRT_HIP_LIB selects it for a run of tools/orient_rates.py)
+OL_FLAGS_orient_lane_atomics = -DEZRT_ORIENT_LANE_ATOMICS=1
 OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
 OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
 OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048

@@ -354,6 +354,18 @@ WELD_ABI = {
 VERTEX_BORDER, VERTEX_NONMANIFOLD_EDGE, VERTEX_PINCHED = 1, 2, 4
 
 
+# stream-ordered mesh orientation on device memory, libezrt_hip.so only (include/ezrt_orient.h); pointers are device addresses
+ORIENT_ABI = {
+    # n_tri: the bytes of `work` (no device work)
+    "ezrt_orient_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, twin, edge_class, outward, flip, patch_root, patch, proot, psize, pflags, vol6, summary, work, work_bytes, stream
+    "ezrt_mesh_orient_device": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    # s, tri36, n_tri, flip, stream
+    "ezrt_rewind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+PATCH_OPEN, PATCH_NONORIENTABLE, PATCH_REWOUND, PATCH_INWARD = 1, 2, 4, 8
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -451,7 +463,7 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, OVERLAP_LIST_ABI,
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, OVERLAP_LIST_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

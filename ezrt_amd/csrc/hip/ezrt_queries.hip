@@ -5,7 +5,7 @@
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
 // ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
 // ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
-// ezrt_vertex_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// ezrt_vertex_kernels.h, and the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -30,10 +30,12 @@
 #include "ezrt_overlap_list.h"
 #include "ezrt_topology.h"
 #include "ezrt_vertices.h"
+#include "ezrt_orient.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
 #include "ezrt_vertex_kernels.h"
+#include "ezrt_orient_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -915,6 +917,75 @@ int ezrt_vertex_normals_device(EzrtScene* s, float* tri36, int n_tri, const int3
       a.face = (float*)work;
       hipLaunchKernelGGL(vn_face_kernel, g, b, 0, st, a);
       hipLaunchKernelGGL(vn_corner_kernel, dim3((unsigned)((H + WD_BLOCK - 1) / WD_BLOCK)), b, 0, st, a);
+    });
+  });
+}
+
+// ---- mesh orientation on device memory (include/ezrt_orient.h): nine launches on `st` -- init, union, flatten, check, the weld's
+// prefix sum (sums, loops_scan_kernel, scan), volume, finish -- over the caller's `work`: scan (n_tri + 1 int64), tiles (one int64 per
+// 2048 triangles, and one), vol (n_tri int64), then par, flat, pf and psz (n_tri ints each) and two words for A; one launch for the
+// rewind.  Checked, launched and ordered against a refit by query_call.
+static uint64_t orient_tiles(int n_tri) { return ((uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
+size_t ezrt_orient_work_bytes(int n_tri) {
+  if (n_tri <= 0) return 8;
+  return (size_t)(32ull * (uint64_t)n_tri + 8ull * orient_tiles(n_tri) + 24ull);
+}
+int ezrt_mesh_orient_device(EzrtScene* s, const int32_t* twin, const uint8_t* edge_class, int outward, uint8_t* flip, int32_t* patch_root,
+                            int32_t* patch, int32_t* proot, int32_t* psize, uint8_t* pflags, int64_t* vol6, int64_t* summary, void* work,
+                            size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_mesh_orient_device", [&]() -> int {
+    if (!s || !twin || !edge_class || !flip || !patch_root || !patch || !proot || !psize || !pflags || !vol6 || !summary || !work)
+      return fail(EZRT_ERR_INVALID, "NULL argument");
+    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    const int n_tri = (int)s->n_tri;
+    if (work_bytes < ezrt_orient_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_orient_work_bytes(n_tri)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{twin, H * i4}, {edge_class, H}, {flip, N}, {patch_root, N * i4}, {patch, N * i4}, {proot, N * i4}, {psize, N * i4},
+                          {pflags, N}, {vol6, N * sizeof(int64_t)}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_orient_work_bytes(n_tri)}},
+                      H, st, [&](dim3, dim3) {
+      OrientArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = (int32_t)n_tri;
+      a.twin = twin, a.edge_class = edge_class, a.outward = outward != 0 ? 1 : 0;
+      const uint64_t B = orient_tiles(n_tri);
+      a.scan = (long long*)work;
+      a.tiles = a.scan + N + 1;
+      a.vol = a.tiles + B + 1;
+      a.par = (uint32_t*)(a.vol + N);
+      a.flat = a.par + N;
+      a.pf = a.flat + N;
+      a.psz = (int32_t*)(a.pf + N);
+      a.amax = (uint32_t*)(a.psz + N);
+      a.flip = flip, a.patch_root = patch_root, a.patch = patch, a.proot = proot, a.psize = psize, a.pflags = pflags;
+      a.vol6 = (long long*)vol6, a.summary = (unsigned long long*)summary;
+      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + OR_BLOCK - 1) / OR_BLOCK, OR_GRID_MAX)); };
+      const dim3 b(OR_BLOCK), gh = grid(H), gt = grid(N);
+      hipLaunchKernelGGL(orient_init_kernel, gt, b, 0, st, a);
+      hipLaunchKernelGGL(orient_union_kernel, gh, b, 0, st, a);
+      hipLaunchKernelGGL(orient_flatten_kernel, gt, b, 0, st, a);
+      hipLaunchKernelGGL(orient_check_kernel, gt, b, 0, st, a);
+      // the prefix sum of the roots' flags in place over B tiles (ezrt_vertex_kernels.h: weld_scan_kernel)
+      hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)B), dim3(WD_BLOCK), 0, st, (const long long*)a.scan, a.tiles, (const long long*)nullptr, (long long)N);
+      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.tiles, (const long long*)nullptr, (long long)B);
+      hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)B), dim3(WD_BLOCK), 0, st, a.scan, (const long long*)a.tiles, (const long long*)nullptr, (long long)N);
+      hipLaunchKernelGGL(orient_volume_kernel, gt, b, 0, st, a);
+      hipLaunchKernelGGL(orient_finish_kernel, gt, b, 0, st, a);
+    });
+  });
+}
+int ezrt_rewind_device(EzrtScene* s, float* tri36, int n_tri, const uint8_t* flip, void* stream) {
+  return ezi::guarded("ezrt_rewind_device", [&]() -> int {
+    if (!s || !tri36 || !flip) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
+    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {flip, N}}, N, st, [&](dim3, dim3) {
+      hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((N + OR_BLOCK - 1) / OR_BLOCK)), dim3(OR_BLOCK), 0, st, tri36, (uint32_t)n_tri, flip);
     });
   });
 }

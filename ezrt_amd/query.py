@@ -2,7 +2,7 @@
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
-include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h).
+include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -49,6 +49,9 @@ include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h).
     tri36 = query.vertex_normals(scene, tri36, weld)                          # smooth normals of moved rows, into floats 9-17, before a refit
     positions, faces = query.indexed_mesh(weld, tri36)                        # ... what every other tool takes
     chi = query.euler_characteristic(weld, topo)                              # V - E + F
+    orient = query.mesh_orient(scene, topo)                                   # which triangles to reverse, patches, signed volumes
+    tri36 = query.rewind(scene, tri36, orient)                                # ... reverse the marked rows, before a refit (include/ezrt_orient.h)
+    volume = query.patch_volume(orient)                                       # ... the signed volume of every patch (float64)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -93,6 +96,7 @@ PlaneLoops = collections.namedtuple("PlaneLoops", "plane_loops loop_offsets clos
 PlaneLoopsOf = collections.namedtuple("PlaneLoopsOf", "next order plane_loops loop_offsets closed")
 MeshTopology = collections.namedtuple("MeshTopology", "twin edge_class neighbours mult root component comp_root comp_size comp_flags summary closed oriented")
 MeshWeld = collections.namedtuple("MeshWeld", "vertex vert_corner star_offsets star fans vert_flags summary n_vert manifold_vertices")
+MeshOrient = collections.namedtuple("MeshOrient", "flip patch_root patch proot psize pflags vol6 summary n_patch orientable scale")
 
 
 def _scene_lib(scene, abi):
@@ -1396,6 +1400,83 @@ def euler_characteristic(weld, topo):
     if w[0] != 3 * t[0]:
         raise ValueError("the weld and the topology are not of the same triangles (%d live corners, %d live triangles)" % (w[0], t[0]))
     return w[1] - t[1] + t[0]
+
+
+def mesh_orient(scene, topo=None, outward=True, stream=None):
+    """MeshOrient(flip uint8 [n_tri], patch_root int32 [n_tri], patch int32 [n_tri], proot int32 [P], psize int32 [P], pflags uint8 [P],
+    vol6 int64 [P], summary int64 [8], n_patch int, orientable bool, scale int): a consistent winding of the scene's triangles as
+    they are stored.  `topo` is a MeshTopology of this scene (or any object with twin and edge_class); with topo=None
+    mesh_topology(scene, components=False) is run on the same stream first.  Triangles joined across MANIFOLD and FLIPPED edges form
+    a patch; patch_root[t] is the lowest id of t's patch and patch[t] its number 0 .. P - 1 in ascending order of the roots (-1 for a
+    triangle that does not take part); flip[t] is 1 where the triangle has to be reversed for its patch to be wound like the patch's
+    root -- or, with outward=True on a closed orientable patch, so that the patch faces outward.  pflags[p] has _abi.PATCH_OPEN,
+    PATCH_NONORIENTABLE (a Moebius band: flip is 0 on all of it), PATCH_REWOUND (some flip is 1) and PATCH_INWARD (closed, orientable
+    and of negative volume as stored); vol6[p] * 2 ** scale / 6 is the patch's signed volume (patch_volume).  summary is [triangles
+    taking part, P, orientable patches, closed patches, flips, INWARD patches, scale, 0]; `orientable` says that every patch is: the
+    mesh can be made consistently wound, by query.rewind and a refit.  The tensors are on the device of topo's.  Synchronises the
+    stream once, to read the summary.  The topology is taken by value: after a refit that changes windings make both again.  MEMORY:
+    the library's scratch, ezrt_orient_work_bytes(n_tri), 32 B per triangle, is allocated here and freed to torch's allocator when the
+    stream is done with it.  The definition: include/ezrt_orient.h."""
+    if not isinstance(outward, bool):
+        raise ValueError("outward must be a bool")
+    lib = _scene_lib(scene, _abi.ORIENT_ABI)
+    n = scene.stats()["n_tri"]
+    if topo is None:
+        topo = mesh_topology(scene, components=False, stream=stream)
+    twin = _tensor("topo.twin", topo.twin, torch.int32)
+    cls = _tensor("topo.edge_class", topo.edge_class, torch.uint8, device=twin.device)
+    if twin.numel() != 3 * n or cls.numel() != 3 * n:
+        raise ValueError("topo.twin and topo.edge_class must have 3 * n_tri = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
+    dev = twin.device
+    h, ts = _stream(twin, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    work_bytes = int(lib.ezrt_orient_work_bytes(n))
+    i32 = lambda: torch.empty((n,), dtype=torch.int32, device=dev)
+    u8 = lambda: torch.empty((n,), dtype=torch.uint8, device=dev)
+    with torch.cuda.stream(own):
+        flip, root, patch, proot, psize, pflags = u8(), i32(), i32(), i32(), i32(), u8()
+        vol6 = torch.empty((n,), dtype=torch.int64, device=dev)
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr())
+    if n > 0:
+        _call(scene, lib.ezrt_mesh_orient_device(scene._h, ptr(twin), ptr(cls), 1 if outward else 0, ptr(flip), ptr(root), ptr(patch), ptr(proot),
+                                                 ptr(psize), ptr(pflags), ptr(vol6), ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((twin, cls, flip, root, patch, proot, psize, pflags, vol6, summary, work), ts, twin)
+    with torch.cuda.stream(own):
+        sm = summary.tolist()                                        # the one synchronisation, of the query's stream
+    k = sm[1]
+    return MeshOrient(flip, root, patch, proot[:k], psize[:k], pflags[:k], vol6[:k], summary, k, sm[2] == sm[1], sm[6])
+
+
+def rewind(scene, tri36, orient, stream=None):
+    """tri36, with the rows that `orient` (a MeshOrient of this scene, or any object with flip) marks reversed in place: p2 <-> p3
+    (floats 3-5 and 6-8) and n2 <-> n3 (floats 12-14 and 15-17); a normal travels with its vertex.  tri36 is the caller's contiguous
+    float32 [n_tri, 36] GPU tensor, the one about to go into refit.refit; nothing else of it is written, and a second call restores it.
+    For smooth normals of the new winding call vertex_normals afterwards.  Does not synchronise.  The definition:
+    include/ezrt_orient.h."""
+    lib = _scene_lib(scene, _abi.ORIENT_ABI)
+    n = scene.stats()["n_tri"]
+    _tensor("tri36", tri36, torch.float32, shape=(n, 36))
+    flip = _tensor("orient.flip", orient.flip, torch.uint8, shape=(n,), device=tri36.device)
+    if n == 0:
+        return tri36
+    h, ts = _stream(tri36, stream)
+    P = C.c_void_p
+    _call(scene, lib.ezrt_rewind_device(scene._h, P(tri36.data_ptr()), n, P(flip.data_ptr()), P(h)))
+    _keep((tri36, flip), ts, tri36)
+    return tri36
+
+
+def patch_volume(orient):
+    """float64 [P]: the signed volume of every patch of a MeshOrient in scene units, vol6 * 2.0 ** scale / 6, on vol6's device and
+    torch's current stream.  Exact wherever the header says so (small integer coordinates); the volume of an open patch depends on
+    the origin."""
+    if not isinstance(orient.vol6, torch.Tensor) or orient.vol6.dtype != torch.int64 or not isinstance(orient.scale, int):
+        raise TypeError("orient must be a MeshOrient: vol6 an int64 tensor, scale an int")
+    v = orient.vol6.to(torch.float64) * 2.0 ** orient.scale                    # exact: a power of two
+    return v / torch.full_like(v, 6.0)                                         # (a tensor divisor: torch multiplies by the reciprocal of a scalar one)
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
