@@ -366,6 +366,18 @@ ORIENT_ABI = {
 PATCH_OPEN, PATCH_NONORIENTABLE, PATCH_REWOUND, PATCH_INWARD = 1, 2, 4, 8
 
 
+# stream-ordered boundary loops and caps on device memory, libezrt_hip.so only (include/ezrt_boundary.h); pointers are device addresses
+BOUNDARY_ABI = {
+    # n_tri: the bytes of `work` (no device work)
+    "ezrt_boundary_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, twin, edge_class, next, loop, pos, order, loop_offsets, lflags, area2 (or None), summary, work, work_bytes, stream
+    "ezrt_mesh_boundary_device": (C.c_int, [C.c_void_p] * 12 + [C.c_size_t, C.c_void_p]),
+    # s, tri36, n_tri, order, loop, pos, loop_offsets, lflags, summary, cap, cap_valid, stream
+    "ezrt_cap_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
+}
+LOOP_CLOSED = 1
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -463,7 +475,8 @@ def load_hip():
         lib = declare_trace_abi(C.CDLL(path), strict=True)
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
-                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, OVERLAP_LIST_ABI,
+                      OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, BOUNDARY_ABI,
+                      OVERLAP_LIST_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

@@ -5,7 +5,8 @@
 // ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
 // ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
 // ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
-// ezrt_vertex_kernels.h, and the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// ezrt_vertex_kernels.h, the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h, and the boundary
+// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -31,11 +32,13 @@
 #include "ezrt_topology.h"
 #include "ezrt_vertices.h"
 #include "ezrt_orient.h"
+#include "ezrt_boundary.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
 #include "ezrt_vertex_kernels.h"
 #include "ezrt_orient_kernels.h"
+#include "ezrt_boundary_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -986,6 +989,98 @@ int ezrt_rewind_device(EzrtScene* s, float* tri36, int n_tri, const uint8_t* fli
     hipStream_t st = (hipStream_t)stream;
     return query_call(s, {{tri36, N * 36 * sizeof(float)}, {flip, N}}, N, st, [&](dim3, dim3) {
       hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((N + OR_BLOCK - 1) / OR_BLOCK)), dim3(OR_BLOCK), 0, st, tri36, (uint32_t)n_tri, flip);
+    });
+  });
+}
+
+// ---- boundary loops on device memory (include/ezrt_boundary.h): 17 launches and the rounds of the ranking on `st` -- init, next,
+// union, open, a prefix sum (sums, loops_scan_kernel, scan) that compacts the BOUNDARY half-edges, rank init, ceil(log2(3 n_tri)) jumping
+// rounds, flag, the prefix sum over the compacted list that numbers the heads, number, the prefix sum of the lengths, scatter -- over the
+// caller's `work`: scan_c and scan_n (3 n_tri + 1 int64 each), tiles (one int64 per 2048 half-edges, and one), the two buffers of the
+// ranking (3 n_tri int64 each), four int64 of counts, then pred, par and comp (3 n_tri ints each); one launch for the cap.  Checked,
+// launched and ordered against a refit by query_call.
+static uint64_t boundary_tiles(int n_tri) { return (3ull * (uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
+size_t ezrt_boundary_work_bytes(int n_tri) {
+  if (n_tri <= 0) return 8;
+  return (size_t)(132ull * (uint64_t)n_tri + 4ull * ((uint64_t)n_tri & 1ull) + 8ull * boundary_tiles(n_tri) + 56ull);
+}
+int ezrt_mesh_boundary_device(EzrtScene* s, const int32_t* twin, const uint8_t* edge_class, int32_t* next, int32_t* loop, int32_t* pos,
+                              int32_t* order, int32_t* loop_offsets, uint8_t* lflags, int64_t* area2, int64_t* summary, void* work,
+                              size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_mesh_boundary_device", [&]() -> int {
+    if (!s || !twin || !edge_class || !next || !loop || !pos || !order || !loop_offsets || !lflags || !summary || !work)
+      return fail(EZRT_ERR_INVALID, "NULL argument");
+    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    const int n_tri = (int)s->n_tri;
+    if (work_bytes < ezrt_boundary_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_boundary_work_bytes(n_tri)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t), i8 = sizeof(int64_t);
+    hipStream_t st = (hipStream_t)stream;
+    // (a null area2 is skipped by the check, as a null input of the overlap lists is)
+    return query_call(s, {{twin, H * i4}, {edge_class, H}, {next, H * i4}, {loop, H * i4}, {pos, H * i4}, {order, H * i4},
+                          {loop_offsets, (H + 1) * i4}, {lflags, H}, {area2, 3 * H * i8}, {summary, 8 * i8},
+                          {work, ezrt_boundary_work_bytes(n_tri)}},
+                      H, st, [&](dim3, dim3) {
+      BoundaryArgs a{};
+      a.tri_geom = s->tri_geom.p;
+      a.n_tri = (int32_t)n_tri;
+      a.twin = twin, a.edge_class = edge_class;
+      const uint64_t T = boundary_tiles(n_tri);
+      a.scan_c = (long long*)work;
+      a.scan_n = a.scan_c + H + 1;
+      a.tiles = a.scan_n + H + 1;
+      a.jump[0] = (unsigned long long*)(a.tiles + T + 1);
+      a.jump[1] = a.jump[0] + H;
+      a.cnt = (long long*)(a.jump[1] + H);
+      a.pred = (int32_t*)(a.cnt + 4);
+      a.par = (uint32_t*)(a.pred + H);
+      a.comp = (int32_t*)(a.par + H);
+      a.open = (uint32_t*)a.scan_n;
+      a.lens = a.scan_c;
+      int rounds = 0;
+      while ((1ull << rounds) < (uint64_t)H) rounds++; // ceil(log2(3 n_tri)): at most 32
+      a.rounds = rounds;
+      a.next = next, a.loop = loop, a.pos = pos, a.order = order, a.loop_offsets = loop_offsets, a.lflags = lflags;
+      a.area2 = (long long*)area2, a.summary = (unsigned long long*)summary;
+      const dim3 b(BD_BLOCK), g((unsigned)std::min<uint64_t>((H + BD_BLOCK - 1) / BD_BLOCK, BD_GRID_MAX));
+      // a prefix sum of x in place over T tiles (ezrt_vertex_kernels.h: weld_scan_kernel); n_dev: its length, read on the device
+      const auto scan = [&](long long* x, const long long* n_dev) {
+        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, (const long long*)x, a.tiles, n_dev, (long long)H);
+        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.tiles, (const long long*)nullptr, (long long)T);
+        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, x, (const long long*)a.tiles, n_dev, (long long)H);
+      };
+      hipLaunchKernelGGL(bd_init_kernel, g, b, 0, st, a);
+      hipLaunchKernelGGL(bd_next_kernel, g, b, 0, st, a);
+      hipLaunchKernelGGL(bd_union_kernel, g, b, 0, st, a);
+      hipLaunchKernelGGL(bd_open_kernel, g, b, 0, st, a);
+      scan(a.scan_c, nullptr);
+      hipLaunchKernelGGL(bd_rank_init_kernel, g, b, 0, st, a);
+      for (int r = 0; r < rounds; r++) hipLaunchKernelGGL(bd_jump_kernel, g, b, 0, st, a, r & 1); // rounds are separated by launches
+      hipLaunchKernelGGL(bd_flag_kernel, g, b, 0, st, a);
+      scan(a.scan_n, a.cnt);
+      hipLaunchKernelGGL(bd_number_kernel, g, b, 0, st, a);
+      scan(a.lens, a.cnt + 1);
+      hipLaunchKernelGGL(bd_scatter_kernel, g, b, 0, st, a);
+    });
+  });
+}
+int ezrt_cap_rows_device(EzrtScene* s, const float* tri36, int n_tri, const int32_t* order, const int32_t* loop, const int32_t* pos,
+                         const int32_t* loop_offsets, const uint8_t* lflags, const int64_t* summary, float* cap, uint8_t* cap_valid,
+                         void* stream) {
+  return ezi::guarded("ezrt_cap_rows_device", [&]() -> int {
+    if (!s || !tri36 || !order || !loop || !pos || !loop_offsets || !lflags || !summary || !cap || !cap_valid)
+      return fail(EZRT_ERR_INVALID, "NULL argument");
+    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
+    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
+    if (n_tri <= 0) return 0;
+    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {order, H * i4}, {loop, H * i4}, {pos, H * i4}, {loop_offsets, (H + 1) * i4},
+                          {lflags, H}, {summary, 8 * sizeof(int64_t)}, {cap, H * 36 * sizeof(float)}, {cap_valid, H}},
+                      H, st, [&](dim3, dim3) {
+      hipLaunchKernelGGL(cap_rows_kernel, dim3((unsigned)((H + BD_BLOCK - 1) / BD_BLOCK)), dim3(BD_BLOCK), 0, st, tri36, (int32_t)n_tri, order, loop,
+                         pos, loop_offsets, lflags, (const long long*)summary, cap, cap_valid);
     });
   });
 }

@@ -2,7 +2,7 @@
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
-include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h).
+include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h, include/ezrt_boundary.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -52,6 +52,9 @@ include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, i
     orient = query.mesh_orient(scene, topo)                                   # which triangles to reverse, patches, signed volumes
     tri36 = query.rewind(scene, tri36, orient)                                # ... reverse the marked rows, before a refit (include/ezrt_orient.h)
     volume = query.patch_volume(orient)                                       # ... the signed volume of every patch (float64)
+    boundary = query.mesh_boundary(scene, topo)                               # the holes of the mesh as ordered loops of half-edges
+    points = query.boundary_points(boundary, tri36)                           # ... their points in order; query.loop_area(boundary) their area vectors
+    cap = query.cap_rows(scene, tri36, boundary)                              # ... the triangles that close them (include/ezrt_boundary.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -97,6 +100,7 @@ PlaneLoopsOf = collections.namedtuple("PlaneLoopsOf", "next order plane_loops lo
 MeshTopology = collections.namedtuple("MeshTopology", "twin edge_class neighbours mult root component comp_root comp_size comp_flags summary closed oriented")
 MeshWeld = collections.namedtuple("MeshWeld", "vertex vert_corner star_offsets star fans vert_flags summary n_vert manifold_vertices")
 MeshOrient = collections.namedtuple("MeshOrient", "flip patch_root patch proot psize pflags vol6 summary n_patch orientable scale")
+MeshBoundary = collections.namedtuple("MeshBoundary", "next loop pos order loop_offsets lflags area2 summary n_boundary n_loops closed scale")
 
 
 def _scene_lib(scene, abi):
@@ -1477,6 +1481,123 @@ def patch_volume(orient):
         raise TypeError("orient must be a MeshOrient: vol6 an int64 tensor, scale an int")
     v = orient.vol6.to(torch.float64) * 2.0 ** orient.scale                    # exact: a power of two
     return v / torch.full_like(v, 6.0)                                         # (a tensor divisor: torch multiplies by the reciprocal of a scalar one)
+
+
+def mesh_boundary(scene, topo=None, area=True, stream=None):
+    """MeshBoundary(next int32 [3 n_tri], loop int32 [3 n_tri], pos int32 [3 n_tri], order int32 [B], loop_offsets int32 [L + 1],
+    lflags uint8 [L], area2 int64 [L, 3] or None, summary int64 [8], n_boundary int, n_loops int, closed bool, scale int): the
+    boundary of the scene's triangles as they are stored, as ordered loops of half-edges.  `topo` is a MeshTopology of this scene (or
+    any object with twin and edge_class); with topo=None mesh_topology(scene, components=False) is run on the same stream first.
+    Half-edge h = 3 t + e runs from vertex e of triangle t to vertex (e + 1) % 3; next[h] is the boundary half-edge that follows a
+    boundary half-edge h (-1: none, or h is no boundary), found by rotating about the end vertex across MANIFOLD edges; loop[h] and
+    pos[h] are its loop and its position in it (-1 for other half-edges); order[loop_offsets[l] : loop_offsets[l + 1]] are the
+    half-edges of loop l in order, loops numbered by ascending head (of a cycle its lowest half-edge); lflags[l] has _abi.LOOP_CLOSED
+    where the loop is a cycle -- a chain that ends at a FLIPPED or NONMANIFOLD edge is an open path: orient and rewind first.  With
+    area=True, area2[l] * 2 ** scale / 2 is the vector area of loop l (loop_area).  summary is [B, L, closed loops, the longest loop,
+    boundary half-edges without a successor, scale, 0, 0]; `closed` says that every loop is a cycle.  The tensors are on the device of
+    topo's.  Synchronises the stream once, to read the summary.  The topology is taken by value: after a refit make both again.
+    MEMORY: the library's scratch, ezrt_boundary_work_bytes(n_tri), 132 B per triangle, is allocated here and freed to torch's
+    allocator when the stream is done with it.  The definition: include/ezrt_boundary.h."""
+    if not isinstance(area, bool):
+        raise ValueError("area must be a bool")
+    lib = _scene_lib(scene, _abi.BOUNDARY_ABI)
+    n = scene.stats()["n_tri"]
+    if topo is None:
+        topo = mesh_topology(scene, components=False, stream=stream)
+    twin = _tensor("topo.twin", topo.twin, torch.int32)
+    cls = _tensor("topo.edge_class", topo.edge_class, torch.uint8, device=twin.device)
+    if twin.numel() != 3 * n or cls.numel() != 3 * n:
+        raise ValueError("topo.twin and topo.edge_class must have 3 * n_tri = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
+    dev = twin.device
+    h, ts = _stream(twin, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    work_bytes = int(lib.ezrt_boundary_work_bytes(n))
+    H = 3 * n
+    i32 = lambda k: torch.empty((k,), dtype=torch.int32, device=dev)
+    with torch.cuda.stream(own):
+        nxt, loop, pos, order, offsets = i32(H), i32(H), i32(H), i32(H), i32(H + 1)
+        lflags = torch.empty((H,), dtype=torch.uint8, device=dev)
+        area2 = torch.empty((H, 3), dtype=torch.int64, device=dev) if area else None
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        offsets[:1] = 0                                                        # (a scene without triangles: L = 0, B = 0)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_mesh_boundary_device(scene._h, ptr(twin), ptr(cls), ptr(nxt), ptr(loop), ptr(pos), ptr(order), ptr(offsets),
+                                                   ptr(lflags), ptr(area2), ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((twin, cls, nxt, loop, pos, order, offsets, lflags, area2, summary, work), ts, twin)
+    with torch.cuda.stream(own):
+        sm = summary.tolist()                                        # the one synchronisation, of the query's stream
+    B, L = sm[0], sm[1]
+    return MeshBoundary(nxt, loop, pos, order[:B], offsets[:L + 1], lflags[:L], area2[:L] if area else None, summary, B, L, sm[2] == sm[1],
+                        sm[5])
+
+
+def _boundary(boundary):
+    if not isinstance(boundary, MeshBoundary) or not all(isinstance(x, torch.Tensor) for x in boundary[:6] + (boundary.summary,)):
+        raise TypeError("boundary must be a MeshBoundary of query.mesh_boundary")
+    return boundary
+
+
+def boundary_points(boundary, tri36):
+    """float32 [B, 3]: the start points of the boundary half-edges in `order`, loop after loop -- points[loop_offsets[l] :
+    loop_offsets[l + 1]] is the polygon of loop l.  tri36 is the rows the scene was made of, a float32 [n_tri, 36] GPU tensor on the
+    boundary's device.  A gather on torch's current stream."""
+    b = _boundary(boundary)
+    n = b.next.numel() // 3
+    _tensor("tri36", tri36, torch.float32, shape=(n, 36), device=b.order.device)
+    return tri36[:, :9].reshape(-1, 3)[b.order.to(torch.int64)]
+
+
+def loop_area(boundary):
+    """float64 [L, 3]: the vector area of every loop of a MeshBoundary made with area=True, area2 * 2.0 ** scale / 2, on area2's
+    device and torch's current stream.  Of a closed loop it is the vector area of any surface that spans it, exact wherever the header
+    says so (small integer coordinates); of an open path it depends on the origin."""
+    if not isinstance(boundary, MeshBoundary) or not isinstance(boundary.area2, torch.Tensor) or boundary.area2.dtype != torch.int64 or \
+            not isinstance(boundary.scale, int):
+        raise TypeError("boundary must be a MeshBoundary made with area=True: area2 an int64 tensor, scale an int")
+    return boundary.area2.to(torch.float64) * 2.0 ** (boundary.scale - 1)     # exact: a power of two
+
+
+def cap_rows(scene, tri36, boundary, stream=None):
+    """float32 [n_cap, 36]: the triangles that close the closed loops of `boundary` (a MeshBoundary of this scene), a fan from each
+    loop's head, k - 2 triangles for a loop of k edges, in row order; torch.cat([tri36, cap]) is the closed mesh, for a new scene.
+    Positions and materials are read from tri36, the caller's contiguous float32 [n_tri, 36] GPU rows: each new triangle has the face
+    normal at its three corners and the material of the triangle it closes against.  A fan closes a hole topologically; a non-planar
+    or non-convex hole gets a folded cap.  Synchronises (the compaction of the valid rows).  The definition: include/ezrt_boundary.h."""
+    lib = _scene_lib(scene, _abi.BOUNDARY_ABI)
+    n = scene.stats()["n_tri"]
+    _tensor("tri36", tri36, torch.float32, shape=(n, 36))
+    b = _boundary(boundary)
+    dev = tri36.device
+    H = 3 * n
+    for name, x, dt, k in (("next", b.next, torch.int32, H), ("loop", b.loop, torch.int32, H), ("pos", b.pos, torch.int32, H),
+                           ("order", b.order, torch.int32, b.n_boundary), ("loop_offsets", b.loop_offsets, torch.int32, b.n_loops + 1),
+                           ("lflags", b.lflags, torch.uint8, b.n_loops), ("summary", b.summary, torch.int64, 8)):
+        _tensor("boundary." + name, x, dt, shape=(k,), device=dev)
+    if not 0 <= b.n_loops <= b.n_boundary <= H:
+        raise ValueError("boundary is not of this scene: %d loops, %d boundary half-edges, %d half-edges" % (b.n_loops, b.n_boundary, H))
+    B = b.n_boundary
+    h, ts = _stream(tri36, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    with torch.cuda.stream(own):
+        # the library takes arrays of the full size; order, loop_offsets and lflags were cut to what was written
+        room = lambda x: x.untyped_storage().nbytes() // x.element_size() - x.storage_offset()
+        pad = lambda x, k: x if x.numel() and room(x) >= k else torch.cat([x, torch.zeros((k - x.numel(),), dtype=x.dtype, device=dev)])
+        order, offsets, lflags = pad(b.order, H), pad(b.loop_offsets, H + 1), pad(b.lflags, H)
+        cap = torch.empty((H, 36), dtype=torch.float32, device=dev)
+        valid = torch.zeros((H,), dtype=torch.uint8, device=dev)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr())
+    if n > 0:
+        _call(scene, lib.ezrt_cap_rows_device(scene._h, ptr(tri36), n, ptr(order), ptr(b.loop), ptr(b.pos), ptr(offsets), ptr(lflags),
+                                              ptr(b.summary), ptr(cap), ptr(valid), P(h)))
+    _keep((tri36, order, b.loop, b.pos, offsets, lflags, b.summary, cap, valid), ts, tri36)
+    with torch.cuda.stream(own):
+        out = cap[:B][valid[:B] != 0]
+    _keep((out,), ts, tri36)
+    return out
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
