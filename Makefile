@@ -77,6 +77,9 @@ OL_VARIANTS = i16_t4096 i64_t4096 i0_t2048 i0_t8192 nosort
 # (the same rule builds the measurement variant of the mesh orientation, ezrt_orient_kernels.h: one atomic per lane in the volume
 # launch; EZRT_HIP_LIB selects it for a run of tools/orient_rates.py)
 OL_FLAGS_orient_lane_atomics = -DEZRT_ORIENT_LANE_ATOMICS=1
+# (and that of the plane clipping, ezrt_clip_kernels.h: the fill with every lane copying its own row, whatever the alignment;
+# EZRT_HIP_LIB selects it for a run of tools/clip_rates.py)
+OL_FLAGS_clip_per_lane = -DEZRT_CLIP_PER_LANE=1
 OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
 OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
 OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048

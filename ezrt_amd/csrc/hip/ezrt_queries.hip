@@ -6,7 +6,8 @@
 // ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
 // ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
 // ezrt_vertex_kernels.h, the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h, and the boundary
-// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h, and the plane clipping of include/ezrt_clip.h,
+// whose kernels are in ezrt_clip_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -33,12 +34,14 @@
 #include "ezrt_vertices.h"
 #include "ezrt_orient.h"
 #include "ezrt_boundary.h"
+#include "ezrt_clip.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
 #include "ezrt_vertex_kernels.h"
 #include "ezrt_orient_kernels.h"
 #include "ezrt_boundary_kernels.h"
+#include "ezrt_clip_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -1081,6 +1084,77 @@ int ezrt_cap_rows_device(EzrtScene* s, const float* tri36, int n_tri, const int3
                       H, st, [&](dim3, dim3) {
       hipLaunchKernelGGL(cap_rows_kernel, dim3((unsigned)((H + BD_BLOCK - 1) / BD_BLOCK)), dim3(BD_BLOCK), 0, st, tri36, (int32_t)n_tri, order, loop,
                          pos, loop_offsets, lflags, (const long long*)summary, cap, cap_valid);
+    });
+  });
+}
+
+// ---- plane clipping on device memory (include/ezrt_clip.h).  Count: a memset of the summary, clip_count_kernel, and the weld's tiled
+// prefix sum (sums, loops_scan_kernel, scan) of offsets in place over the caller's `work`, the tiles' sums and their total.  Fill: one
+// launch, the staged instance where tri36 and out are 16-byte aligned, else the per-lane one (always, in the measurement variant
+// EZRT_CLIP_PER_LANE).  Checked, launched and ordered against a refit by query_call; the scene's records are not read.
+#ifndef EZRT_CLIP_PER_LANE
+#define EZRT_CLIP_PER_LANE 0
+#endif
+static uint64_t clip_tiles(int n_rows) { return ((uint64_t)n_rows + WD_TILE - 1) / WD_TILE; }
+size_t ezrt_clip_work_bytes(int n_rows) {
+  if (n_rows <= 0) return 8;
+  return (size_t)(8ull * clip_tiles(n_rows) + 8ull);
+}
+int ezrt_clip_count_device(EzrtScene* s, const float* tri36, int n_rows, const float* plane4, int64_t* offsets, int64_t* summary, void* work,
+                           size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_clip_count_device", [&]() -> int {
+    if (!s || !tri36 || !plane4 || !offsets || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 2) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 2 rows");
+    if (work_bytes < ezrt_clip_work_bytes(n_rows)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_clip_work_bytes(n_rows)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, i8 = sizeof(int64_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {plane4, 4 * sizeof(float)}, {offsets, (N + 1) * i8}, {summary, 8 * i8},
+                          {work, ezrt_clip_work_bytes(n_rows)}},
+                      N, st, [&](dim3, dim3) -> int {
+      const uint64_t T = clip_tiles(n_rows);
+      long long *x = (long long*)offsets, *tiles = (long long*)work;
+      HIP_TRY(hipMemsetAsync(summary, 0, 8 * i8, st));
+      hipLaunchKernelGGL(clip_count_kernel, dim3((unsigned)((N + CL_BLOCK - 1) / CL_BLOCK)), dim3(CL_BLOCK), 0, st, tri36, (int32_t)n_rows, plane4, x,
+                         (unsigned long long*)summary);
+      // the prefix sum of the counts in place over T tiles (ezrt_vertex_kernels.h: weld_scan_kernel); the total lands in offsets[n_rows]
+      hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, (const long long*)x, tiles, (const long long*)nullptr, (long long)N);
+      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, tiles, (const long long*)nullptr, (long long)T);
+      hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, x, (const long long*)tiles, (const long long*)nullptr, (long long)N);
+      return 0;
+    });
+  });
+}
+int ezrt_clip_rows_device(EzrtScene* s, const float* tri36, int n_rows, const float* plane4, const int64_t* offsets, int64_t capacity, float* out,
+                          int32_t* src, int8_t* cut_edge, void* stream) {
+  return ezi::guarded("ezrt_clip_rows_device", [&]() -> int {
+    if (!s || !tri36 || !plane4 || !offsets) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 2) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 2 rows");
+    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
+    // (the byte count below must not wrap: a wrapped one would pass the buffer check and leave the kernel a capacity that is none)
+    if (capacity > (int64_t)(PTRDIFF_MAX / (36 * sizeof(float)))) return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
+    if (!out && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL out with capacity > 0");
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, cap = (size_t)capacity, row = 36 * sizeof(float);
+    if (out && cap > 0) {
+      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + cap * row;
+      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * row}, {plane4, 4 * sizeof(float)}, {offsets, (N + 1) * sizeof(int64_t)}, {cap ? out : nullptr, cap * row},
+                          {cap ? src : nullptr, cap * sizeof(int32_t)}, {cap ? cut_edge : nullptr, cap}},
+                      N, st, [&](dim3, dim3) {
+      if (cap == 0) return; // nothing fits: nothing is written
+      ClipFillArgs a{};
+      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.plane4 = plane4, a.offsets = (const long long*)offsets, a.capacity = (long long)capacity;
+      a.out = out, a.src = src, a.cut_edge = cut_edge;
+      const dim3 g((unsigned)((N + CL_BLOCK - 1) / CL_BLOCK)), b(CL_BLOCK);
+      const bool staged = !EZRT_CLIP_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
+      if (staged) hipLaunchKernelGGL(clip_fill_kernel<true>, g, b, 0, st, a);
+      else hipLaunchKernelGGL(clip_fill_kernel<false>, g, b, 0, st, a);
     });
   });
 }

@@ -2,7 +2,8 @@
 include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, include/ezrt_box_overlap.h,
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
-include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h, include/ezrt_boundary.h).
+include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h, include/ezrt_boundary.h,
+include/ezrt_clip.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -55,6 +56,8 @@ include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, i
     boundary = query.mesh_boundary(scene, topo)                               # the holes of the mesh as ordered loops of half-edges
     points = query.boundary_points(boundary, tri36)                           # ... their points in order; query.loop_area(boundary) their area vectors
     cap = query.cap_rows(scene, tri36, boundary)                              # ... the triangles that close them (include/ezrt_boundary.h)
+    clip = query.clip_rows(scene, tri36, plane)                               # the rows of tri36 on the side a x + b y + c z >= d of a plane
+    seg = query.cut_segments(clip)                                            # ... the edges the cut made, start to end (include/ezrt_clip.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -101,6 +104,7 @@ MeshTopology = collections.namedtuple("MeshTopology", "twin edge_class neighbour
 MeshWeld = collections.namedtuple("MeshWeld", "vertex vert_corner star_offsets star fans vert_flags summary n_vert manifold_vertices")
 MeshOrient = collections.namedtuple("MeshOrient", "flip patch_root patch proot psize pflags vol6 summary n_patch orientable scale")
 MeshBoundary = collections.namedtuple("MeshBoundary", "next loop pos order loop_offsets lflags area2 summary n_boundary n_loops closed scale")
+ClipRows = collections.namedtuple("ClipRows", "rows src cut_edge summary n_rows")
 
 
 def _scene_lib(scene, abi):
@@ -1598,6 +1602,79 @@ def cap_rows(scene, tri36, boundary, stream=None):
         out = cap[:B][valid[:B] != 0]
     _keep((out,), ts, tri36)
     return out
+
+
+def clip_rows(scene, tri36, plane, src=True, stream=None):
+    """ClipRows(rows float32 [T, 36], src int32 [T] or None, cut_edge int8 [T] or None, summary int64 [8], n_rows int): the part of
+    the caller's triangle rows `tri36` (a contiguous float32 [n, 36] GPU tensor: p1 p2 p3, n1 n2 n3, material -- the rows a scene is
+    made of) on the side a x + b y + c z >= d of `plane`, a float32 [4] tensor (a, b, c, d) on tri36's device or a sequence of four
+    numbers.  A row with every vertex on that side (a vertex ON the plane counts) is kept on the bits, a row on the other side is
+    dropped, and a row the plane crosses is replaced by one or two triangles with the winding of the row, whose new vertices are the
+    points of plane_section on the bits, with the row's normals interpolated along the edge (not renormalised) and its material.
+    rows are in ascending source row; with src=True, src[r] is the source row of output row r and cut_edge[r] the edge (0, 1, 2:
+    from vertex e to vertex (e + 1) % 3) of output row r that the cut made, -1 where there is none (cut_segments gathers them: they
+    are plane_section's segments of the rows that were cut; on a closed, consistently wound mesh the boundary of a scene of `rows` is
+    the section).  summary is [T, rows kept whole,
+    rows cut, finite rows dropped, rows with a non-finite coordinate (dropped), cut edges, plane live, 0]; n_rows is n.  A plane with a
+    non-finite entry or a zero normal keeps nothing.  `scene` supplies the library and the device only: the rows need not be the
+    scene's, and the rows of one call are the input of the next -- six calls trim a mesh to a box.  To go on, make a scene of
+    `rows` and run mesh_topology, mesh_boundary and cap_rows on it: torch.cat([rows, cap]) is the closed half.  Synchronises the
+    stream once, to read T; rows, src and cut_edge are allocated to exactly T rows.  MEMORY besides the result: 8 B per input row of
+    offsets and the library's scratch, ezrt_clip_work_bytes(n), freed to torch's allocator when the stream is done with them.  The
+    definition: include/ezrt_clip.h."""
+    if not isinstance(src, bool):
+        raise ValueError("src must be a bool")
+    lib = _scene_lib(scene, _abi.CLIP_ABI)
+    _tensor("tri36", tri36, torch.float32, last=36)
+    if tri36.dim() != 2:
+        raise ValueError("tri36 must have shape [n, 36], not %s" % (tuple(tri36.shape),))
+    n = tri36.shape[0]
+    if n > (2**31 - 1) // 2:
+        raise ValueError("at most (2^31 - 1) / 2 rows per call")
+    dev = tri36.device
+    h, ts = _stream(tri36, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    if isinstance(plane, torch.Tensor):
+        _tensor("plane", plane, torch.float32, shape=(4,), device=dev)
+    else:
+        p = [float(x) for x in plane]
+        if len(p) != 4:
+            raise ValueError("plane must have four entries (a, b, c, d), not %d" % len(p))
+        with torch.cuda.stream(own):
+            plane = torch.tensor(p, dtype=torch.float64).to(torch.float32).to(dev)
+    work_bytes = int(lib.ezrt_clip_work_bytes(n))
+    with torch.cuda.stream(own):
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_clip_count_device(scene._h, ptr(tri36), n, ptr(plane), ptr(offsets), ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((tri36, plane, offsets, summary, work), ts, tri36)
+    with torch.cuda.stream(own):
+        T = int(offsets[n].item())                                   # the one synchronisation, of the query's stream
+        rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
+        srcs = torch.empty((T,), dtype=torch.int32, device=dev) if src else None
+        cut = torch.empty((T,), dtype=torch.int8, device=dev) if src else None
+    if n > 0 and T > 0:
+        _call(scene, lib.ezrt_clip_rows_device(scene._h, ptr(tri36), n, ptr(plane), ptr(offsets), T, ptr(rows), ptr(srcs), ptr(cut), P(h)))
+    _keep((rows, srcs, cut), ts, tri36)
+    return ClipRows(rows, srcs, cut, summary, n)
+
+
+def cut_segments(clip):
+    """float32 [n_cut, 2, 3]: the cut edges of a ClipRows made with src=True, start to end, in row order -- of every output row r
+    with cut_edge[r] = e >= 0 its vertices e and (e + 1) % 3.  Each is plane_section's segment q0 -> q1 of its source row for the same
+    plane, on the bits and in direction; a source row that emits cut pieces has exactly one.  A gather on torch's current stream."""
+    if not isinstance(clip, ClipRows) or not isinstance(clip.rows, torch.Tensor) or not isinstance(clip.cut_edge, torch.Tensor):
+        raise TypeError("clip must be a ClipRows of query.clip_rows made with src=True")
+    _tensor("clip.rows", clip.rows, torch.float32, last=36)
+    _tensor("clip.cut_edge", clip.cut_edge, torch.int8, shape=(clip.rows.shape[0],), device=clip.rows.device)
+    r = torch.nonzero(clip.cut_edge >= 0).reshape(-1)
+    e = clip.cut_edge[r].to(torch.int64)
+    v = clip.rows[:, :9].reshape(-1, 3, 3)
+    return torch.stack([v[r, e], v[r, (e + 1) % 3]], dim=1)
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
