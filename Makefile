@@ -80,6 +80,11 @@ OL_FLAGS_orient_lane_atomics = -DEZRT_ORIENT_LANE_ATOMICS=1
 # (and that of the plane clipping, ezrt_clip_kernels.h: the fill with every lane copying its own row, whatever the alignment;
 # EZRT_HIP_LIB selects it for a run of tools/clip_rates.py)
 OL_FLAGS_clip_per_lane = -DEZRT_CLIP_PER_LANE=1
+# (and those of the subdivision, ezrt_subdiv_kernels.h: the fill with every lane writing its own four rows, whatever the alignment,
+# and Loop mode without its vertex pass, whose output means nothing: for timing the fill alone; EZRT_HIP_LIB selects one for a run of
+# tools/subdivide_rates.py)
+OL_FLAGS_subdiv_per_lane = -DEZRT_SUBDIV_PER_LANE=1
+OL_FLAGS_subdiv_no_vertex = -DEZRT_SUBDIV_SKIP_VERTEX=1
 OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
 OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
 OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048

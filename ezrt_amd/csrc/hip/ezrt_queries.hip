@@ -6,8 +6,8 @@
 // ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
 // ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
 // ezrt_vertex_kernels.h, the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h, and the boundary
-// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h, and the plane clipping of include/ezrt_clip.h,
-// whose kernels are in ezrt_clip_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h, the plane clipping of include/ezrt_clip.h,
+// whose kernels are in ezrt_clip_kernels.h, and the subdivision of include/ezrt_subdivide.h, whose kernels are in ezrt_subdiv_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -35,6 +35,7 @@
 #include "ezrt_orient.h"
 #include "ezrt_boundary.h"
 #include "ezrt_clip.h"
+#include "ezrt_subdivide.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
@@ -42,6 +43,7 @@
 #include "ezrt_orient_kernels.h"
 #include "ezrt_boundary_kernels.h"
 #include "ezrt_clip_kernels.h"
+#include "ezrt_subdiv_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -1155,6 +1157,61 @@ int ezrt_clip_rows_device(EzrtScene* s, const float* tri36, int n_rows, const fl
       const bool staged = !EZRT_CLIP_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
       if (staged) hipLaunchKernelGGL(clip_fill_kernel<true>, g, b, 0, st, a);
       else hipLaunchKernelGGL(clip_fill_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+
+// ---- subdivision on device memory (include/ezrt_subdivide.h): a memset of the summary, in Loop mode subdiv_vertex_kernel over the
+// caller's `work` (four words per possible vertex), and one fill launch, the staged instance where tri36 and out are 16-byte aligned,
+// else the per-lane one (always, in the measurement variant EZRT_SUBDIV_PER_LANE).  The output's size is known, so there is no count.
+// Checked, launched and ordered against a refit by query_call; the scene's records are not read.
+#ifndef EZRT_SUBDIV_PER_LANE
+#define EZRT_SUBDIV_PER_LANE 0
+#endif
+#ifndef EZRT_SUBDIV_SKIP_VERTEX // measurement variant: Loop mode without its vertex pass, for timing the fill alone (the slots are whatever `work` held)
+#define EZRT_SUBDIV_SKIP_VERTEX 0
+#endif
+size_t ezrt_subdivide_work_bytes(int n_rows, int mode) {
+  if (n_rows <= 0 || mode != EZRT_SUBDIVIDE_LOOP) return 8;
+  return (size_t)(48ull * (uint64_t)n_rows + 8ull);
+}
+int ezrt_subdivide_rows_device(EzrtScene* s, const float* tri36, int n_rows, int mode, const int32_t* twin, const uint8_t* edge_class,
+                               const int32_t* vertex, const int32_t* star_offsets, const int32_t* star, const uint8_t* vert_flags, float* out,
+                               int64_t* summary, void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_subdivide_rows_device", [&]() -> int {
+    if (!s || !tri36 || !out || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 12) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 12 rows");
+    if (mode != EZRT_SUBDIVIDE_MIDPOINT && mode != EZRT_SUBDIVIDE_LOOP) return fail(EZRT_ERR_INVALID, "mode %d is neither MIDPOINT nor LOOP", mode);
+    const int given = !!twin + !!edge_class + !!vertex + !!star_offsets + !!star + !!vert_flags;
+    if (given != 0 && given != 6)
+      return fail(EZRT_ERR_INVALID, "twin, edge_class, vertex, star_offsets, star and vert_flags are given together or not at all");
+    if (mode == EZRT_SUBDIVIDE_MIDPOINT && given) return fail(EZRT_ERR_INVALID, "the topology and weld arrays must be NULL in MIDPOINT mode");
+    if (mode == EZRT_SUBDIVIDE_LOOP && !given) return fail(EZRT_ERR_INVALID, "LOOP mode needs the topology and weld arrays");
+    if (work_bytes < ezrt_subdivide_work_bytes(n_rows, mode))
+      return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_subdivide_work_bytes(n_rows, mode)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, H = 3 * N, row = 36 * sizeof(float), i4 = sizeof(int32_t);
+    {
+      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + 4 * N * row;
+      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * row}, {out, 4 * N * row}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_subdivide_work_bytes(n_rows, mode)},
+                          {twin, H * i4}, {edge_class, H}, {vertex, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4}, {vert_flags, H}},
+                      N, st, [&](dim3, dim3) -> int {
+      SubdivArgs a{};
+      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.mode = (int32_t)mode;
+      a.twin = twin, a.edge_class = edge_class, a.vertex = vertex, a.star_offsets = star_offsets, a.star = star, a.vert_flags = vert_flags;
+      a.out = out, a.summary = (unsigned long long*)summary, a.slot = (uint32_t*)work;
+      HIP_TRY(hipMemsetAsync(summary, 0, 8 * sizeof(int64_t), st));
+      const dim3 b(SD_BLOCK);
+      if (mode == EZRT_SUBDIVIDE_LOOP && !EZRT_SUBDIV_SKIP_VERTEX) hipLaunchKernelGGL(subdiv_vertex_kernel, dim3((unsigned)((H + SD_BLOCK - 1) / SD_BLOCK)), b, 0, st, a);
+      const bool staged = !EZRT_SUBDIV_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
+      if (staged) hipLaunchKernelGGL(subdiv_fill_kernel<true>, dim3((unsigned)std::min<uint64_t>((N + SD_TILE - 1) / SD_TILE, SD_GRID_MAX)), b, 0, st, a);
+      else hipLaunchKernelGGL(subdiv_fill_kernel<false>, dim3((unsigned)((N + SD_BLOCK - 1) / SD_BLOCK)), b, 0, st, a);
+      return 0;
     });
   });
 }

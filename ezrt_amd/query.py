@@ -3,7 +3,7 @@ include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, inc
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
 include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h, include/ezrt_boundary.h,
-include/ezrt_clip.h).
+include/ezrt_clip.h, include/ezrt_subdivide.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -58,6 +58,7 @@ include/ezrt_clip.h).
     cap = query.cap_rows(scene, tri36, boundary)                              # ... the triangles that close them (include/ezrt_boundary.h)
     clip = query.clip_rows(scene, tri36, plane)                               # the rows of tri36 on the side a x + b y + c z >= d of a plane
     seg = query.cut_segments(clip)                                            # ... the edges the cut made, start to end (include/ezrt_clip.h)
+    sub = query.subdivide_rows(scene, tri36, "loop", topo, weld)              # four rows per row, by midpoints or Loop's scheme (include/ezrt_subdivide.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -105,6 +106,7 @@ MeshWeld = collections.namedtuple("MeshWeld", "vertex vert_corner star_offsets s
 MeshOrient = collections.namedtuple("MeshOrient", "flip patch_root patch proot psize pflags vol6 summary n_patch orientable scale")
 MeshBoundary = collections.namedtuple("MeshBoundary", "next loop pos order loop_offsets lflags area2 summary n_boundary n_loops closed scale")
 ClipRows = collections.namedtuple("ClipRows", "rows src cut_edge summary n_rows")
+SubdivRows = collections.namedtuple("SubdivRows", "rows summary n_rows")
 
 
 def _scene_lib(scene, abi):
@@ -1348,14 +1350,14 @@ def mesh_weld_at(scene, corner_a, corner_b, stream=None):
     return same
 
 
-def _weld_array(name, x, size, dev, own):
-    """x, an int32 array of a weld, as the `size` entries the C call may read: x itself where that much memory lies behind it (the
-    trimmed views of mesh_weld), else a zero-padded copy made on the query's stream"""
-    _tensor(name, x, torch.int32, device=dev)
-    if x.numel() >= size or (x.untyped_storage().nbytes() - x.storage_offset() * 4) >= size * 4:
+def _weld_array(name, x, size, dev, own, dtype=torch.int32):
+    """x, an int32 array of a weld (or its uint8 flags), as the `size` entries the C call may read: x itself where that much memory
+    lies behind it (the trimmed views of mesh_weld), else a zero-padded copy made on the query's stream"""
+    _tensor(name, x, dtype, device=dev)
+    if x.numel() >= size or (x.untyped_storage().nbytes() - x.storage_offset() * x.element_size()) >= size * x.element_size():
         return x
     with torch.cuda.stream(own):
-        full = torch.zeros((size,), dtype=torch.int32, device=dev)
+        full = torch.zeros((size,), dtype=dtype, device=dev)
         full[:x.numel()] = x.reshape(-1)
     return full
 
@@ -1675,6 +1677,69 @@ def cut_segments(clip):
     e = clip.cut_edge[r].to(torch.int64)
     v = clip.rows[:, :9].reshape(-1, 3, 3)
     return torch.stack([v[r, e], v[r, (e + 1) % 3]], dim=1)
+
+
+def subdivide_rows(scene, tri36, mode="midpoint", topo=None, weld=None, stream=None):
+    """SubdivRows(rows float32 [4 n, 36], summary int64 [8], n_rows int): every row t of the caller's triangle rows `tri36` (a
+    contiguous float32 [n, 36] GPU tensor: p1 p2 p3, n1 n2 n3, material -- the rows a scene is made of) split in four, rows 4 t .. 4 t + 3
+    of `rows`: the three corner pieces (P0 E0 E2), (E0 P1 E1), (E2 E1 P2) and the middle one (E0 E1 E2), each with the winding and the
+    material of its row.  mode="midpoint" keeps every corner and puts the edge points at (a + b) * 0.5f -- scenes.subdivide on the
+    bits -- with the corner normals kept and averaged along the edges.  mode="loop" is Loop's scheme with Warren's weights: smooth
+    vertices and interior edges are averaged over their neighbours, border vertices and edges along the border, and vertices on a
+    non-manifold edge or pinched stay where they are; every output row gets its face normal (for smooth ones: a scene of `rows`,
+    mesh_weld, vertex_normals).  It requires `topo`, a MeshTopology, and `weld`, a MeshWeld made with flags=True, of a scene of these
+    rows (or any objects with twin, edge_class and vertex, star_offsets, star, vert_flags); both are taken by value: the rows may have
+    been moved since, as long as the same corners coincide.  summary is [4 n, corners smoothed, corners on a border, corners kept,
+    interior half-edges, midpoint half-edges, mode, 0]; n_rows is n.  `scene` supplies the library and the device only: the rows need
+    not be the scene's, and the rows of one call are the input of the next (Loop mode: with a topology and a weld of a scene of
+    them).  Does not synchronise: the size of the answer is known.  MEMORY besides the result: the library's scratch,
+    ezrt_subdivide_work_bytes(n, mode) -- 8 B, in Loop mode 48 B per input row -- freed to torch's allocator when the stream is
+    done with it.  The definition: include/ezrt_subdivide.h."""
+    if mode not in ("midpoint", "loop"):
+        raise ValueError('mode must be "midpoint" or "loop"')
+    loop = mode == "loop"
+    lib = _scene_lib(scene, _abi.SUBDIVIDE_ABI)
+    _tensor("tri36", tri36, torch.float32, last=36)
+    if tri36.dim() != 2:
+        raise ValueError("tri36 must have shape [n, 36], not %s" % (tuple(tri36.shape),))
+    n = tri36.shape[0]
+    if n > (2**31 - 1) // 12:
+        raise ValueError("at most (2^31 - 1) / 12 rows per call")
+    dev = tri36.device
+    h, ts = _stream(tri36, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    arrays = (None,) * 6
+    if loop:
+        if topo is None or weld is None or getattr(weld, "vert_flags", None) is None:
+            raise ValueError('mode="loop" needs topo, a MeshTopology, and weld, a MeshWeld made with flags=True')
+        twin = _tensor("topo.twin", topo.twin, torch.int32, device=dev)
+        cls = _tensor("topo.edge_class", topo.edge_class, torch.uint8, device=dev)
+        if twin.numel() != 3 * n or cls.numel() != 3 * n:
+            raise ValueError("topo.twin and topo.edge_class must have 3 * n = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
+        vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, own)
+        if vertex.numel() != 3 * n:
+            raise ValueError("weld.vertex must have 3 * n = %d entries, not %d" % (3 * n, vertex.numel()))
+        offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, own)
+        star = _weld_array("weld.star", weld.star, 3 * n, dev, own)
+        vflags = _weld_array("weld.vert_flags", weld.vert_flags, 3 * n, dev, own, torch.uint8)
+        arrays = (twin, cls, vertex, offsets, star, vflags)
+    elif topo is not None or weld is not None:
+        raise ValueError('mode="midpoint" takes no topo and no weld')
+    code = _abi.SUBDIVIDE_LOOP if loop else _abi.SUBDIVIDE_MIDPOINT
+    work_bytes = int(lib.ezrt_subdivide_work_bytes(n, code))
+    with torch.cuda.stream(own):
+        rows = torch.empty((4 * n, 36), dtype=torch.float32, device=dev)
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+        if n == 0:
+            summary[6] = code
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_subdivide_rows_device(scene._h, ptr(tri36), n, code, *[ptr(x) for x in arrays], ptr(rows), ptr(summary),
+                                                    ptr(work), work_bytes, P(h)))
+    _keep((tri36, rows, summary, work) + arrays, ts, tri36)
+    return SubdivRows(rows, summary, n)
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
