@@ -85,6 +85,9 @@ OL_FLAGS_clip_per_lane = -DEZRT_CLIP_PER_LANE=1
 # tools/subdivide_rates.py)
 OL_FLAGS_subdiv_per_lane = -DEZRT_SUBDIV_PER_LANE=1
 OL_FLAGS_subdiv_no_vertex = -DEZRT_SUBDIV_SKIP_VERTEX=1
+# (and that of the decimation, ezrt_decimate_kernels.h: the fill with every lane writing its own row, whatever the alignment;
+# EZRT_HIP_LIB selects it for a run of tools/decimate_rates.py)
+OL_FLAGS_decimate_per_lane = -DEZRT_DECIMATE_PER_LANE=1
 OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
 OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
 OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048

@@ -400,6 +400,18 @@ SUBDIVIDE_ABI = {
 SUBDIVIDE_MIDPOINT, SUBDIVIDE_LOOP = 0, 1
 
 
+# stream-ordered decimation on device memory, libezrt_hip.so only (include/ezrt_decimate.h); pointers are device addresses
+DECIMATE_ABI = {
+    # n_rows: the bytes of `work` (no device work)
+    "ezrt_decimate_work_bytes": (C.c_size_t, [C.c_int]),
+    # s, tri36, n_rows, grid4, flags, cell, cell_corner, cell_point, offsets, summary, work, work_bytes, stream
+    "ezrt_decimate_count_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    # s, tri36, n_rows, cell, cell_point, offsets, capacity, out, src (or None), stream
+    "ezrt_decimate_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
+}
+DECIMATE_DEDUP = 1
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -498,7 +510,7 @@ def load_hip():
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
                       OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, BOUNDARY_ABI,
-                      CLIP_ABI, SUBDIVIDE_ABI, OVERLAP_LIST_ABI,
+                      CLIP_ABI, SUBDIVIDE_ABI, DECIMATE_ABI, OVERLAP_LIST_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

@@ -7,7 +7,8 @@
 // ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
 // ezrt_vertex_kernels.h, the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h, and the boundary
 // loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h, the plane clipping of include/ezrt_clip.h,
-// whose kernels are in ezrt_clip_kernels.h, and the subdivision of include/ezrt_subdivide.h, whose kernels are in ezrt_subdiv_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
+// whose kernels are in ezrt_clip_kernels.h, the subdivision of include/ezrt_subdivide.h, whose kernels are in ezrt_subdiv_kernels.h, and the decimation of
+// include/ezrt_decimate.h, whose kernels are in ezrt_decimate_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
 // and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
 // of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
 // kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
@@ -36,6 +37,7 @@
 #include "ezrt_boundary.h"
 #include "ezrt_clip.h"
 #include "ezrt_subdivide.h"
+#include "ezrt_decimate.h"
 #include "ezrt_query_kernels.h"
 #include "ezrt_point_queries.h"
 #include "ezrt_topology_kernels.h"
@@ -44,6 +46,7 @@
 #include "ezrt_boundary_kernels.h"
 #include "ezrt_clip_kernels.h"
 #include "ezrt_subdiv_kernels.h"
+#include "ezrt_decimate_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
@@ -1212,6 +1215,109 @@ int ezrt_subdivide_rows_device(EzrtScene* s, const float* tri36, int n_rows, int
       if (staged) hipLaunchKernelGGL(subdiv_fill_kernel<true>, dim3((unsigned)std::min<uint64_t>((N + SD_TILE - 1) / SD_TILE, SD_GRID_MAX)), b, 0, st, a);
       else hipLaunchKernelGGL(subdiv_fill_kernel<false>, dim3((unsigned)((N + SD_BLOCK - 1) / SD_BLOCK)), b, 0, st, a);
       return 0;
+    });
+  });
+}
+
+// ---- decimation on device memory (include/ezrt_decimate.h).  Count: init, insert, flag, the weld's tiled prefix sum (sums,
+// loops_scan_kernel, scan) over the corners, cells, with EZRT_DECIMATE_DEDUP classify, keep, and the prefix sum again over the rows,
+// in place in offsets -- up to twelve launches over the caller's `work`: ids (3 n_rows + 1 int64), tiles (one int64 per 2048 corners,
+// and one), key (T int64, T the topology's power of two >= 6 n_rows), sum (3 T int64), cnt, low (T ints each), mn, mx (3 T ints each),
+// slot (3 n_rows ints), rep2 (T2 ints, T2 the power of two >= 2 n_rows), slot2 (n_rows ints).  Fill: one launch, the staged instance
+// where tri36 and out are 16-byte aligned, else the per-lane one (always, in the measurement variant EZRT_DECIMATE_PER_LANE).
+// Checked, launched and ordered against a refit by query_call; the scene's records are not read.
+#ifndef EZRT_DECIMATE_PER_LANE
+#define EZRT_DECIMATE_PER_LANE 0
+#endif
+static uint64_t dec_slots2(int n_rows) {
+  uint64_t T = 8;
+  while (T < 2ull * (uint64_t)n_rows) T <<= 1;
+  return T;
+}
+size_t ezrt_decimate_work_bytes(int n_rows) {
+  if (n_rows <= 0) return 8;
+  const uint64_t n = (uint64_t)n_rows;
+  return (size_t)(40ull * n + 8ull * weld_tiles(n_rows) + 64ull * topo_slots(n_rows) + 4ull * dec_slots2(n_rows) + 16ull);
+}
+int ezrt_decimate_count_device(EzrtScene* s, const float* tri36, int n_rows, const float* grid4, int flags, int32_t* cell, int32_t* cell_corner,
+                               float* cell_point, int64_t* offsets, int64_t* summary, void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_decimate_count_device", [&]() -> int {
+    if (!s || !tri36 || !grid4 || !cell || !cell_corner || !cell_point || !offsets || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 rows");
+    if (flags & ~EZRT_DECIMATE_DEDUP) return fail(EZRT_ERR_INVALID, "flags %d has a bit that is not EZRT_DECIMATE_DEDUP", flags);
+    if (work_bytes < ezrt_decimate_work_bytes(n_rows)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_decimate_work_bytes(n_rows)");
+    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, H = 3 * N, i4 = sizeof(int32_t), i8 = sizeof(int64_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {grid4, 4 * sizeof(float)}, {cell, H * i4}, {cell_corner, H * i4},
+                          {cell_point, H * 3 * sizeof(float)}, {offsets, (N + 1) * i8}, {summary, 8 * i8}, {work, ezrt_decimate_work_bytes(n_rows)}},
+                      H, st, [&](dim3, dim3) {
+      DecArgs a{};
+      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.grid4 = grid4, a.flags = (int32_t)flags;
+      a.T = topo_slots(n_rows), a.T2 = dec_slots2(n_rows);
+      const uint64_t B = weld_tiles(n_rows), R = clip_tiles(n_rows);
+      a.ids = (long long*)work;
+      a.tiles = a.ids + H + 1;
+      a.key = (unsigned long long*)(a.tiles + B + 1);
+      a.sum = a.key + a.T;
+      a.cnt = (uint32_t*)(a.sum + 3 * a.T);
+      a.low = (int32_t*)(a.cnt + a.T);
+      a.mn = (uint32_t*)(a.low + a.T);
+      a.mx = a.mn + 3 * a.T;
+      a.slot = a.mx + 3 * a.T;
+      a.rep2 = (int32_t*)(a.slot + H);
+      a.slot2 = (uint32_t*)(a.rep2 + a.T2);
+      a.cell = cell, a.cell_corner = cell_corner, a.cell_point = cell_point, a.offsets = (long long*)offsets;
+      a.summary = (unsigned long long*)summary;
+      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + DC_BLOCK - 1) / DC_BLOCK, DC_GRID_MAX)); };
+      const dim3 b(DC_BLOCK), gh = grid(H), scan(LP_SCAN), wb(WD_BLOCK);
+      // a prefix sum of x[0 .. n) in place over `tl` tiles (ezrt_vertex_kernels.h: weld_scan_kernel); the total lands in x[n]
+      const auto prefix = [&](long long* x, uint64_t n, uint64_t tl) {
+        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)tl), wb, 0, st, (const long long*)x, a.tiles, (const long long*)nullptr, (long long)n);
+        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), scan, 0, st, a.tiles, (const long long*)nullptr, (long long)tl);
+        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)tl), wb, 0, st, x, (const long long*)a.tiles, (const long long*)nullptr, (long long)n);
+      };
+      hipLaunchKernelGGL(dec_init_kernel, grid(3 * a.T), b, 0, st, a);
+      hipLaunchKernelGGL(dec_insert_kernel, gh, b, 0, st, a);
+      hipLaunchKernelGGL(dec_flag_kernel, gh, b, 0, st, a);
+      prefix(a.ids, H, B);
+      hipLaunchKernelGGL(dec_cells_kernel, gh, b, 0, st, a);
+      if (flags & EZRT_DECIMATE_DEDUP) hipLaunchKernelGGL(dec_classify_kernel, grid(N), b, 0, st, a);
+      hipLaunchKernelGGL(dec_keep_kernel, dim3((unsigned)((N + DC_BLOCK - 1) / DC_BLOCK)), b, 0, st, a);
+      prefix(a.offsets, N, R);
+    });
+  });
+}
+int ezrt_decimate_rows_device(EzrtScene* s, const float* tri36, int n_rows, const int32_t* cell, const float* cell_point, const int64_t* offsets,
+                              int64_t capacity, float* out, int32_t* src, void* stream) {
+  return ezi::guarded("ezrt_decimate_rows_device", [&]() -> int {
+    if (!s || !tri36 || !cell || !cell_point || !offsets) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 rows");
+    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
+    // (the byte count below must not wrap: a wrapped one would pass the buffer check and leave the kernel a capacity that is none)
+    if (capacity > (int64_t)(PTRDIFF_MAX / (36 * sizeof(float)))) return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
+    if (!out && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL out with capacity > 0");
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, H = 3 * N, cap = (size_t)capacity, row = 36 * sizeof(float);
+    if (out && cap > 0) {
+      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + cap * row;
+      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * row}, {cell, H * sizeof(int32_t)}, {cell_point, H * 3 * sizeof(float)}, {offsets, (N + 1) * sizeof(int64_t)},
+                          {cap ? out : nullptr, cap * row}, {cap ? src : nullptr, cap * sizeof(int32_t)}},
+                      N, st, [&](dim3, dim3) {
+      if (cap == 0) return; // nothing fits: nothing is written
+      DecFillArgs a{};
+      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.cell = cell, a.cell_point = cell_point, a.offsets = (const long long*)offsets;
+      a.capacity = (long long)capacity, a.out = out, a.src = src;
+      const dim3 g((unsigned)((N + DC_BLOCK - 1) / DC_BLOCK)), b(DC_BLOCK);
+      const bool staged = !EZRT_DECIMATE_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
+      if (staged) hipLaunchKernelGGL(dec_fill_kernel<true>, g, b, 0, st, a);
+      else hipLaunchKernelGGL(dec_fill_kernel<false>, g, b, 0, st, a);
     });
   });
 }

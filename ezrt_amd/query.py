@@ -107,6 +107,7 @@ MeshOrient = collections.namedtuple("MeshOrient", "flip patch_root patch proot p
 MeshBoundary = collections.namedtuple("MeshBoundary", "next loop pos order loop_offsets lflags area2 summary n_boundary n_loops closed scale")
 ClipRows = collections.namedtuple("ClipRows", "rows src cut_edge summary n_rows")
 SubdivRows = collections.namedtuple("SubdivRows", "rows summary n_rows")
+DecimatedRows = collections.namedtuple("DecimatedRows", "rows src cell cell_point summary n_rows")
 
 
 def _scene_lib(scene, abi):
@@ -1740,6 +1741,70 @@ def subdivide_rows(scene, tri36, mode="midpoint", topo=None, weld=None, stream=N
                                                     ptr(work), work_bytes, P(h)))
     _keep((tri36, rows, summary, work) + arrays, ts, tri36)
     return SubdivRows(rows, summary, n)
+
+
+def decimate_rows(scene, tri36, cell_size, origin=(0, 0, 0), dedup=True, src=True, stream=None):
+    """DecimatedRows(rows float32 [T, 36], src int32 [T] or None, cell int32 [n, 3], cell_point float32 [n_cells, 3], summary int64 [8],
+    n_rows int): the caller's triangle rows `tri36` (a contiguous float32 [n, 36] GPU tensor: p1 p2 p3, n1 n2 n3, material -- the rows a
+    scene is made of) with their vertices CLUSTERED on the uniform grid of cubes of edge `cell_size` that has a corner at `origin`
+    (a number and three numbers; both are rounded to float32).  All vertices in one cell become one point -- the mean of their
+    positions in the cell's fixed-point coordinates, exact and independent of any order, and per axis the common value itself where
+    they all agree, so a vertex alone in its cell does not move and an axis-aligned flat face stays flat.  A row whose three vertices
+    fall into three different cells is kept, with the winding and the material of its row and its face normal at all three corners;
+    every other row has collapsed and is dropped; with dedup=True, of the rows that come out with the same three cells only the lowest
+    is kept (the two faces of a thin plate).  rows are in ascending source row; with src=True, src[r] is the source row of output row
+    r.  cell[t] are the cells of row t's three vertices (-1: the row has a non-finite coordinate or lies more than 2^20 cells from
+    the origin, and takes no part) and cell_point their points: together the decimated mesh in INDEXED form.  summary is [T,
+    collapsed rows, duplicates, rows that take no part, n_cells, cells not moved at all, flags, grid live]; n_rows is n.  A cell_size
+    that is not a finite number above zero, or a non-finite origin, keeps nothing.  Clustering does not preserve manifoldness: the
+    output of a closed mesh may have non-manifold and boundary edges (mesh_topology says).  `scene` supplies the library and the
+    device only: the rows need not be the scene's, and the rows of one call are the input of the next.  Synchronises the stream once,
+    to read T; rows and src are allocated to exactly T rows and cell_point is cut to n_cells.  MEMORY besides the result: 8 B per
+    input row of offsets, 12 B per corner for the lowest corners and the points of up to 3 n cells, and the library's scratch,
+    ezrt_decimate_work_bytes(n) -- between 430 and 830 B per input row, the table is sized for one cell per corner -- freed to
+    torch's allocator when the stream is done with them.  The definition: include/ezrt_decimate.h."""
+    if not isinstance(src, bool) or not isinstance(dedup, bool):
+        raise ValueError("src and dedup must be bools")
+    lib = _scene_lib(scene, _abi.DECIMATE_ABI)
+    _tensor("tri36", tri36, torch.float32, last=36)
+    if tri36.dim() != 2:
+        raise ValueError("tri36 must have shape [n, 36], not %s" % (tuple(tri36.shape),))
+    n = tri36.shape[0]
+    if n > (2**31 - 1) // 3:
+        raise ValueError("at most (2^31 - 1) / 3 rows per call")
+    o = [float(x) for x in origin]
+    if len(o) != 3:
+        raise ValueError("origin must have three entries, not %d" % len(o))
+    dev = tri36.device
+    h, ts = _stream(tri36, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    flags = _abi.DECIMATE_DEDUP if dedup else 0
+    work_bytes = int(lib.ezrt_decimate_work_bytes(n))
+    with torch.cuda.stream(own):
+        grid = torch.tensor(o + [float(cell_size)], dtype=torch.float64).to(torch.float32).to(dev)
+        cell = torch.full((n, 3), -1, dtype=torch.int32, device=dev)
+        corner = torch.empty((3 * n,), dtype=torch.int32, device=dev)
+        point = torch.empty((3 * n, 3), dtype=torch.float32, device=dev)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+        if n == 0:
+            summary[6] = flags
+            summary[7] = int(bool(torch.isfinite(grid).all()) and float(grid[3]) > 0)
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n > 0:
+        _call(scene, lib.ezrt_decimate_count_device(scene._h, ptr(tri36), n, ptr(grid), flags, ptr(cell), ptr(corner), ptr(point), ptr(offsets),
+                                                    ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((tri36, grid, cell, corner, point, offsets, summary, work), ts, tri36)
+    with torch.cuda.stream(own):
+        T, n_cells = (int(x) for x in torch.stack([offsets[n], summary[4]]).tolist())   # the one synchronisation, of the query's stream
+        rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
+        srcs = torch.empty((T,), dtype=torch.int32, device=dev) if src else None
+    if n > 0 and T > 0:
+        _call(scene, lib.ezrt_decimate_rows_device(scene._h, ptr(tri36), n, ptr(cell), ptr(point), ptr(offsets), T, ptr(rows), ptr(srcs), P(h)))
+    _keep((rows, srcs), ts, tri36)
+    return DecimatedRows(rows, srcs, cell, point[:n_cells], summary, n)
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
