@@ -11,7 +11,7 @@ ARCH ?= gfx950
 
 LIBDIR = ezrt_amd/lib
 HOST_SRC = ezrt_amd/csrc/host/scene.cpp ezrt_amd/csrc/host/hdr.cpp ezrt_amd/csrc/host/p2_query.cpp ezrt_amd/csrc/host/host_c_api.cpp
-HIP_SRC = ezrt_amd/csrc/hip/ezrt_hip.hip ezrt_amd/csrc/hip/ezrt_scene_build.hip ezrt_amd/csrc/hip/ezrt_launch.hip ezrt_amd/csrc/hip/ezrt_queries.hip ezrt_amd/csrc/hip/ezrt_lbvh.hip ezrt_amd/csrc/hip/ezrt_sahbvh.hip ezrt_amd/csrc/hip/ezrt_mgpu.hip ezrt_amd/csrc/hip/ezrt_refit.hip
+HIP_SRC = ezrt_amd/csrc/hip/ezrt_hip.hip ezrt_amd/csrc/hip/ezrt_scene_build.hip ezrt_amd/csrc/hip/ezrt_launch.hip ezrt_amd/csrc/hip/ezrt_queries.hip ezrt_amd/csrc/hip/ezrt_mesh.hip ezrt_amd/csrc/hip/ezrt_lbvh.hip ezrt_amd/csrc/hip/ezrt_sahbvh.hip ezrt_amd/csrc/hip/ezrt_mgpu.hip ezrt_amd/csrc/hip/ezrt_refit.hip
 HIP_DEPS = $(wildcard ezrt_amd/csrc/hip/*.h) $(wildcard ezrt_amd/csrc/hip/*.hip) $(wildcard include/*)
 
 # -ffp-contract=off everywhere: the trace's discrete decisions must be
@@ -72,10 +72,13 @@ negctl:
 # library with other limits compiled in, and one without the sort launch (its long rows are unsorted: for timing the fill kernel
 # alone).  Only ezrt_queries.hip is compiled again; never loaded by the product (EZRT_HIP_LIB selects one for a run).  The i16
 # library is also what runs fill_rows' insertion path in tests/test_gpu_overlap_list.py, which the compiled insert_max = 0 never takes.
-OL_OTHER_OBJ = $(filter-out build/hip/ezrt_queries.o,$(HIP_OBJ))
 OL_VARIANTS = i16_t4096 i64_t4096 i0_t2048 i0_t8192 nosort
-# (the same rule builds the measurement variant of the mesh orientation, ezrt_orient_kernels.h: one atomic per lane in the volume
-# launch; EZRT_HIP_LIB selects it for a run of tools/orient_rates.py)
+# The measurement variants of the mesh processing recompile ezrt_mesh.hip instead: the one unit a variant compiles again is
+# VARIANT_UNIT_<name>, ezrt_queries where none is named.
+MESH_VARIANTS = orient_lane_atomics clip_per_lane subdiv_per_lane subdiv_no_vertex decimate_per_lane
+$(foreach v,$(MESH_VARIANTS),$(eval VARIANT_UNIT_$(v) = ezrt_mesh))
+# (the mesh orientation, ezrt_orient_kernels.h: one atomic per lane in the volume launch; EZRT_HIP_LIB selects it for a run of
+# tools/orient_rates.py)
 OL_FLAGS_orient_lane_atomics = -DEZRT_ORIENT_LANE_ATOMICS=1
 # (and that of the plane clipping, ezrt_clip_kernels.h: the fill with every lane copying its own row, whatever the alignment;
 # EZRT_HIP_LIB selects it for a run of tools/clip_rates.py)
@@ -94,7 +97,8 @@ OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048
 OL_FLAGS_i0_t8192 = -DEZRT_OL_TILE_MAX=8192
 OL_FLAGS_nosort = -DEZRT_OL_SKIP_SORT=1
 olvariants: $(addprefix build_ab/libezrt_hip_,$(addsuffix .so,$(OL_VARIANTS)))
-build_ab/libezrt_hip_%.so: ezrt_amd/csrc/hip/ezrt_queries.hip $(OL_OTHER_OBJ) $(wildcard ezrt_amd/csrc/hip/*.h) $(wildcard include/*)
+variant_unit = $(or $(VARIANT_UNIT_$(1)),ezrt_queries)
+build_ab/libezrt_hip_%.so: $(HIP_OBJ) $(HIP_DEPS)
 	@mkdir -p build_ab
-	$(HIPCC) $(HIP_FLAGS) $(OL_FLAGS_$*) -c -o build_ab/ezrt_queries_$*.o ezrt_amd/csrc/hip/ezrt_queries.hip
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OL_OTHER_OBJ) build_ab/ezrt_queries_$*.o -ldl -pthread
+	$(HIPCC) $(HIP_FLAGS) $(OL_FLAGS_$*) -c -o build_ab/$(call variant_unit,$*)_$*.o ezrt_amd/csrc/hip/$(call variant_unit,$*).hip
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(filter-out build/hip/$(call variant_unit,$*).o,$(HIP_OBJ)) build_ab/$(call variant_unit,$*)_$*.o -ldl -pthread

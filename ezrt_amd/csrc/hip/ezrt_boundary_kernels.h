@@ -1,7 +1,7 @@
 // ezrt_boundary_kernels.h -- the kernels of the boundary loops and of the cap (include/ezrt_boundary.h, rules B1 to B8 and C1 to C4):
 // the holes of a mesh as ordered cycles of half-edges, their area vectors, and the fan of triangles that closes each.  Included by
-// ezrt_queries.hip, after ezrt_orient_kernels.h (it uses orient_takes, orient_runs, orient_block_sum, orient_block_max, topo_finite,
-// loops_scan_kernel and the weld's tiled prefix sum, weld_sums_kernel / weld_scan_kernel).
+// ezrt_mesh.hip, after ezrt_orient_kernels.h (it uses orient_takes, orient_runs, orient_block_sum, orient_block_max, topo_finite;
+// its three prefix sums are scan_tiled of ezrt_scan_kernels.h, launched by the host).
 //
 //   bd_init_kernel       the union-find, the predecessors, the open marks, the counts and the summary, whatever `work` held
 //   bd_next_kernel       B1, B2, B6: one lane per half-edge; the walk about the end vertex, next, the predecessor, the flag that the first
@@ -32,7 +32,6 @@
 #pragma once
 
 constexpr int BD_BLOCK = OR_BLOCK;          // orient_block_sum and orient_block_max are written for workgroups of OR_BLOCK
-constexpr unsigned BD_GRID_MAX = 4096;      // workgroups of a grid-stride launch: 16 per CU
 constexpr unsigned long long BD_LOW = 0xFFFFFFFFull;
 
 struct BoundaryArgs {
@@ -43,7 +42,7 @@ struct BoundaryArgs {
   // work
   long long* scan_c;           // 3 n_tri + 1: 1 at a BOUNDARY half-edge, then its exclusive prefix sum, [3 n_tri] = B; afterwards `lens`
   long long* scan_n;           // 3 n_tri + 1: first `open`; then 1 at a head of the compacted list and its prefix sum, [B] = L
-  long long* tiles;            // ceil(3 n_tri / WD_TILE) + 1: the sums of a scan's tiles
+  long long* tiles;            // ceil(3 n_tri / SCAN_TILE) + 1: the sums of a scan's tiles
   unsigned long long* jump[2]; // 3 n_tri each: per compacted member, ancestor << 32 | steps to it
   long long* cnt;              // 4: B, L, the bits of A, 0
   int32_t* pred;               // 3 n_tri: the half-edge whose next this is, or -1

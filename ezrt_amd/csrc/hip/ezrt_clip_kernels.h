@@ -1,7 +1,7 @@
 // ezrt_clip_kernels.h -- the kernels of the plane clipping (include/ezrt_clip.h, rules K1 to K8): the rows of the caller's mesh on the
-// side a x + b y + c z >= d of a plane.  Included by ezrt_queries.hip, after ezrt_boundary_kernels.h (it uses plane_load, plane_side and
-// plane_point of ezrt_device.h; the prefix sum between the two kernels is the weld's, weld_sums_kernel / loops_scan_kernel /
-// weld_scan_kernel, launched by the host).
+// side a x + b y + c z >= d of a plane.  Included by ezrt_mesh.hip, after ezrt_boundary_kernels.h (it uses plane_load, plane_side and
+// plane_point of ezrt_device.h; the prefix sum between the two kernels is scan_tiled of ezrt_scan_kernels.h,
+// launched by the host).
 //
 //   clip_count_kernel    K2, K3, K7: one lane per row; the row's count into offsets[k], the terms of the summary reduced over the wave
 //   clip_fill_kernel     K3 .. K6, K8: a workgroup per tile of CL_BLOCK consecutive rows; STAGED or per lane

@@ -1,6 +1,6 @@
 // ezrt_decimate_kernels.h -- the kernels of the decimation (include/ezrt_decimate.h, rules D1 to D10): the caller's rows with their
-// vertices clustered on a uniform grid.  Included by ezrt_queries.hip, after ezrt_subdiv_kernels.h (it uses loops_hash, topo_bits and
-// ezi::tri_normal; the two prefix sums are the weld's, weld_sums_kernel / loops_scan_kernel / weld_scan_kernel, launched by the host).
+// vertices clustered on a uniform grid.  Included by ezrt_mesh.hip, after ezrt_subdiv_kernels.h (it uses loops_hash, topo_bits and
+// ezi::tri_normal; the two prefix sums are scan_tiled of ezrt_scan_kernels.h, launched by the host).
 //
 //   dec_init_kernel      the two tables, the accumulators and the summary, whatever `work` held
 //   dec_insert_kernel    D2, D3, D4, D5: one lane per corner; THE HOT KERNEL.  A run of neighbouring lanes with the same cell claims or
@@ -36,7 +36,6 @@
 #pragma once
 
 constexpr int DC_BLOCK = 256;            // lanes of a workgroup, and rows of a fill tile
-constexpr unsigned DC_GRID_MAX = 4096;   // workgroups of a grid-stride launch: 16 per CU
 constexpr unsigned long long DC_EMPTY = ~0ull; // an empty slot: a key has 63 bits
 constexpr uint32_t DC_NONE = 0xFFFFFFFFu;
 
@@ -87,7 +86,7 @@ struct DecArgs {
   uint64_t T, T2;           // slots of the two tables, powers of two, at most 2^32
   // work
   long long* ids;           // 3 n_rows + 1: 1 at the lowest corner of a cell, then its exclusive prefix sum; [3 n_rows] = n_cells
-  long long* tiles;         // ceil(3 n_rows / WD_TILE) + 1: the sums of a scan's tiles
+  long long* tiles;         // ceil(3 n_rows / SCAN_TILE) + 1: the sums of a scan's tiles
   unsigned long long* key;  // T: the cell of the slot, three 21-bit indices; DC_EMPTY
   unsigned long long* sum;  // 3 T, axis by axis: the sum of the fractions q
   uint32_t* cnt;            // T: the corners of the cell

@@ -555,3 +555,10 @@ inline int device_call(EzrtScene* s, const void* records, std::initializer_list<
   return 0;
 }
 } // namespace ezi
+
+// Every call of ezrt_queries.hip and ezrt_mesh.hip goes through ezi::device_call like this: buffers checked against the scene's
+// device, launch(grid, block), then the event of the scratch-free queries (QueryScratch::ev_shade_end), which a later refit waits for.
+template <class Launch>
+static int query_call(EzrtScene* s, std::initializer_list<ezi::DeviceBuf> bufs, size_t n, hipStream_t st, Launch&& launch) {
+  return ezi::device_call(s, s->tri_shade.p, bufs, n, "inputs and outputs", "elements", &QueryScratch::ev_shade_end, st, launch);
+}

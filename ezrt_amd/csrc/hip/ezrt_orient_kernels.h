@@ -1,6 +1,6 @@
 // ezrt_orient_kernels.h -- the kernels of the mesh orientation (include/ezrt_orient.h, rules O1 to O8): the patches of a mesh, a
-// consistent winding of each, its signed volume, and the reversal of the marked rows.  Included by ezrt_queries.hip, after
-// ezrt_vertex_kernels.h (it uses topo_finite, loops_scan_kernel and the weld's tiled prefix sum, weld_sums_kernel / weld_scan_kernel).
+// consistent winding of each, its signed volume, and the reversal of the marked rows.  Included by ezrt_mesh.hip, after
+// ezrt_vertex_kernels.h (it uses topo_finite; its prefix sum is scan_tiled of ezrt_scan_kernels.h, launched by the host).
 //
 //   orient_init_kernel      the union-find, the accumulators, A and the summary, whatever `work` held
 //   orient_union_kernel     O2, O3, O4: one lane per half-edge; a link, taken at its lower half-edge, unites its two triangles with parity
@@ -38,7 +38,6 @@
 #endif
 
 constexpr int OR_BLOCK = 256;
-constexpr unsigned OR_GRID_MAX = 4096;      // workgroups of a grid-stride launch: 16 per CU
 constexpr uint32_t OR_DEAD = 0xFFFFFFFFu;  // flat[t] of a triangle that does not take part (a word is at most 2 n_tri - 1 < 2^31)
 constexpr uint32_t OR_OPEN = 1u, OR_NONORIENTABLE = 2u, OR_ODD = 4u;   // pf at a root; OR_ODD: f0 is 1 somewhere in the patch
 
@@ -50,7 +49,7 @@ struct OrientArgs {
   int32_t outward;
   // work
   long long* scan;   // n_tri + 1: 1 at a root, then its exclusive prefix sum; [n_tri] = P
-  long long* tiles;  // ceil(n_tri / WD_TILE) + 1: the sums of the scan's tiles
+  long long* tiles;  // ceil(n_tri / SCAN_TILE) + 1: the sums of the scan's tiles
   long long* vol;    // n_tri: at a root, vol6_0 of its patch
   uint32_t* par;     // n_tri: parent << 1 | parity(t -> parent), parent <= t
   uint32_t* flat;    // n_tri: root << 1 | parity(t -> root), or OR_DEAD

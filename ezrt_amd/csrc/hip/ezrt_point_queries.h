@@ -3,7 +3,7 @@
 // self-overlap, triangle-distance, sphere-cast, segment, oriented-box, winding-number and plane queries (include/ezrt_box_overlap.h,
 // include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h, include/ezrt_segment.h,
 // include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h).  One query point, box, triangle, ray or segment per lane
-// (the plane queries: one TRIANGLE per lane, the plane uniform), a workgroup of one wave.  Included by ezrt_queries.hip alone.
+// (the plane queries: one TRIANGLE per lane, the plane uniform), a workgroup of one wave.  Included by ezrt_queries.hip alone, after ezrt_scan_kernels.h.
 //
 //   point_walk                       the best-first walk over the 4-wide records that closest point, nearest, signed distance and
 //                                    triangle distance share: the lower bound of a slot's box is the caller's
@@ -43,7 +43,7 @@
 //   plane_at_kernel                  the plane rule for pairs the caller holds
 //   loops_chain_kernel<LDS>          a workgroup per plane: the bit-exact join of a section's rows and their ranking into chains,
 //                                    in LDS or in the caller's work memory (include/ezrt_plane_loops.h)
-//   loops_scan_kernel                an exclusive prefix sum in place (the planes' loop counts, the loops' lengths)
+//   (scan_block_kernel               ezrt_scan_kernels.h: an exclusive prefix sum in place -- the planes' loop counts, the loops' lengths)
 //   loops_length_kernel              the tail of every chain writes its loop's length
 //   loops_scatter_kernel             order, next, loop_offsets and closed
 #pragma once
@@ -1552,8 +1552,8 @@ __global__ __launch_bounds__(256) void plane_at_kernel(const float4* tri_geom, i
 // m <= n_tri) over a LoopsStore of arrays that loops_chain_kernel<true> places in LDS (planes of at most `tile` rows) and
 // loops_chain_kernel<false> in the caller's `work`, at the plane's own rows of capacity-long arrays (2 x rows of the table's).  The
 // workgroup leaves nxt, prd, hd (the head; -1 for a degenerate row), ps (pos) and hl (a head's number among its plane's heads) in
-// `work` and the plane's number of loops in plane_loops[i], which loops_scan_kernel then sums in place.  loops_length_kernel has the
-// tail of every chain write its loop's length, loops_scan_kernel sums those, and loops_scatter_kernel writes the outputs.
+// `work` and the plane's number of loops in plane_loops[i], which scan_block_kernel then sums in place.  loops_length_kernel has the
+// tail of every chain write its loop's length, scan_block_kernel sums those, and loops_scatter_kernel writes the outputs.
 //
 // Termination and bounds, whatever `offsets` holds (two chained planes of a garbage array may overlap, and then share rows of
 // `work`): every probe loop runs at most T times, every list walk at most m times, every round loop K times, and every index read
@@ -1562,7 +1562,7 @@ __global__ __launch_bounds__(256) void plane_at_kernel(const float4* tri_geom, i
 // 30 % at 10 000 planes.
 constexpr int LP_TILE_MAX = 1024;                       // rows of a plane that is chained in LDS: 11 ints each, 44 KiB of the launch's 64
 constexpr int LP_LDS_BLOCK = 512, LP_GLB_BLOCK = 1024;  // threads of the two routes' workgroups
-constexpr int LP_BLOCK = 256, LP_SCAN = 1024;
+constexpr int LP_BLOCK = 256;
 struct LoopsArgs {
   const long long* offsets; // n + 1
   const uint32_t* seg;      // capacity x 6: the bits
@@ -1600,14 +1600,7 @@ __device__ inline bool loops_in(int32_t x, uint32_t m) { return (uint32_t)x < m;
 // does not hold in threadgroup-split mode (the library is not built for it), and it would break silently if a plane were ever split
 // over several workgroups: such a change has to make these loads and stores agent-scope atomics, or put launches between the phases.
 __device__ inline int32_t loops_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// a mix of the 12 bytes (the finaliser of MurmurHash3): coordinates on a coarse grid differ in few, high bits
-__device__ inline uint32_t loops_hash(uint32_t x, uint32_t y, uint32_t z) {
-  uint32_t h = x * 0x9E3779B1u;
-  h = (h << 13 | h >> 19) ^ (y * 0x85EBCA77u);
-  h = (h << 13 | h >> 19) ^ (z * 0xC2B2AE3Du);
-  h ^= h >> 16, h *= 0x85EBCA6Bu, h ^= h >> 13, h *= 0xC2B2AE35u, h ^= h >> 16;
-  return h;
-}
+// (the hash of the table's keys, loops_hash, is in ezrt_scan_kernels.h: the mesh processing's tables use it too)
 // K rounds of doubling on the buffers {ac, dc} -> {an, dn} and back: a' = a[a], d' = MIN ? min(d, d[a]) : d + d[a].  Ends behind a
 // barrier with the result in {ac, dc} (the pointers are swapped with the rounds).
 template <int B, bool MIN>
@@ -1812,33 +1805,6 @@ __global__ __launch_bounds__(LDS ? LP_LDS_BLOCK : LP_GLB_BLOCK) void loops_chain
     s.rep = a.rep + 2 * o0, s.oh = a.oh + 2 * o0, s.ih = a.ih + 2 * o0;
   }
   loops_plane<B>(a, s, i, o0, m, sc);
-}
-// x[0 .. n) -> its exclusive prefix sum IN PLACE, the total in x[n]; n = min(*n_dev, n_max) where n_dev is given, else n_max.  ONE
-// workgroup, as plane_offsets_kernel: n is a number of planes or of loops, small beside the rows.
-__global__ __launch_bounds__(LP_SCAN) void loops_scan_kernel(long long* x, const long long* n_dev, long long n_max) {
-  __shared__ long long sums[LP_SCAN];
-  const uint32_t t = threadIdx.x;
-  long long nn = n_dev ? *n_dev : n_max;
-  nn = nn < 0 ? 0 : (nn > n_max ? n_max : nn);
-  const unsigned long long n = (unsigned long long)nn, chunk = (n + LP_SCAN - 1) / LP_SCAN;
-  const unsigned long long lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-  long long s = 0;
-  for (unsigned long long i = lo; i < hi; i++) s += x[i];
-  sums[t] = s;
-  __syncthreads();
-  for (uint32_t o = 1; o < LP_SCAN; o <<= 1) {
-    const long long add = t >= o ? sums[t - o] : 0;
-    __syncthreads();
-    sums[t] += add;
-    __syncthreads();
-  }
-  long long run = sums[t] - s;
-  for (unsigned long long i = lo; i < hi; i++) {
-    const long long v = x[i];
-    x[i] = run;
-    run += v;
-  }
-  if (t == LP_SCAN - 1) x[n] = sums[t];
 }
 // the number of a row's loop, or -1: plane_loops[i] (summed by now) + the head's number in its plane
 __device__ inline long long loops_id(const LoopsArgs& a, long long first, long long o0, uint32_t m, int32_t h) {

@@ -1,18 +1,16 @@
 // ezrt_queries.hip -- the device queries that are ONE kernel on the caller's stream and need no scratch: shading queries
 // (include/ezrt_shade.h), path queries (include/ezrt_path.h), all-hits queries and surface_at (include/ezrt_multihit.h), closest-point,
 // nearest-K, inside / signed-distance, box-overlap, triangle-overlap, self-overlap, triangle-distance, sphere-cast, segment,
-// oriented-box, winding-number, plane, plane-loop and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h, ezrt_box_overlap.h,
-// ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h, ezrt_obb_overlap.h, ezrt_winding.h,
-// ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h; the mesh topology of include/ezrt_topology.h, whose kernels are in
-// ezrt_topology_kernels.h, and the vertex weld and smooth normals of include/ezrt_vertices.h, whose kernels are in
-// ezrt_vertex_kernels.h, the mesh orientation of include/ezrt_orient.h, whose kernels are in ezrt_orient_kernels.h, and the boundary
-// loops and caps of include/ezrt_boundary.h, whose kernels are in ezrt_boundary_kernels.h, the plane clipping of include/ezrt_clip.h,
-// whose kernels are in ezrt_clip_kernels.h, the subdivision of include/ezrt_subdivide.h, whose kernels are in ezrt_subdiv_kernels.h, and the decimation of
-// include/ezrt_decimate.h, whose kernels are in ezrt_decimate_kernels.h; the sliced winding call is a memset, a kernel and a finishing kernel on the caller's stream, the plane count a sweep
-// and two small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort).  A translation unit of its own: none
-// of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a register of a timed
-// kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device, ezrt_query_occluded_device,
-// ezrt_query_surface_device) are in ezrt_launch.hip.  DESIGN.md 5.
+// oriented-box, winding-number, plane, plane-loop and overlap-list queries (include/ezrt_closest_point.h, ezrt_nearest.h, ezrt_inside.h,
+// ezrt_box_overlap.h, ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_tri_distance.h, ezrt_sphere_cast.h, ezrt_segment.h,
+// ezrt_obb_overlap.h, ezrt_winding.h, ezrt_plane.h, ezrt_plane_loops.h, ezrt_overlap_list.h).  The few that are more than one kernel
+// are a handful of launches each: the sliced winding call is a memset, a kernel and a finishing kernel, the plane count a sweep and two
+// small kernels, an overlap list's fill a routed kernel and, on the walk route, a sort, and the plane loops six launches over the
+// caller's `work`.  The mesh processing, whose calls are many launches over a work buffer, is in ezrt_mesh.hip.  A translation unit of
+// its own: none of its kernels is compiled together with the render pipeline's (ezrt_launch.hip), so a change here cannot move a
+// register of a timed kernel.  The ray queries that run the pipeline's trace kernels (ezrt_query_closest_device,
+// ezrt_query_occluded_device, ezrt_query_surface_device) are in ezrt_launch.hip.  Every call here goes through query_call
+// (ezrt_internal.h).  DESIGN.md 5.
 #include "ezrt_internal.h"
 #include "ezrt_shade.h"
 #include "ezrt_path.h"
@@ -31,32 +29,12 @@
 #include "ezrt_plane.h"
 #include "ezrt_plane_loops.h"
 #include "ezrt_overlap_list.h"
-#include "ezrt_topology.h"
-#include "ezrt_vertices.h"
-#include "ezrt_orient.h"
-#include "ezrt_boundary.h"
-#include "ezrt_clip.h"
-#include "ezrt_subdivide.h"
-#include "ezrt_decimate.h"
 #include "ezrt_query_kernels.h"
+#include "ezrt_scan_kernels.h"
 #include "ezrt_point_queries.h"
-#include "ezrt_topology_kernels.h"
-#include "ezrt_vertex_kernels.h"
-#include "ezrt_orient_kernels.h"
-#include "ezrt_boundary_kernels.h"
-#include "ezrt_clip_kernels.h"
-#include "ezrt_subdiv_kernels.h"
-#include "ezrt_decimate_kernels.h"
 
 using ezi::known_integrator;
 using ezi::stack_lds_bytes;
-
-// Every call here goes through ezi::device_call: buffers checked against the scene's device, launch(grid, block), then the event of
-// the scratch-free queries (QueryScratch::ev_shade_end), which a later refit waits for.
-template <class Launch>
-static int query_call(EzrtScene* s, std::initializer_list<ezi::DeviceBuf> bufs, size_t n, hipStream_t st, Launch&& launch) {
-  return ezi::device_call(s, s->tri_shade.p, bufs, n, "inputs and outputs", "elements", &QueryScratch::ev_shade_end, st, launch);
-}
 
 template <int INTEG>
 static void launch_shade_eval(EzrtScene* s, dim3 g, dim3 b, hipStream_t st, const int32_t* tri_id, const float* V, const float* N,
@@ -737,587 +715,10 @@ int ezrt_plane_loops_device(EzrtScene* s, const int64_t* offsets, int n, const f
       const dim3 g((unsigned)n);
       hipLaunchKernelGGL((loops_chain_kernel<true>), g, dim3(LP_LDS_BLOCK), 0, st, a);
       hipLaunchKernelGGL((loops_chain_kernel<false>), g, dim3(LP_GLB_BLOCK), 0, st, a);
-      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.plane_loops, (const long long*)nullptr, (long long)n);
+      scan_small(st, a.plane_loops, nullptr, (long long)n);
       hipLaunchKernelGGL(loops_length_kernel, g, dim3(LP_BLOCK), 0, st, a);
-      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.lofs, (const long long*)(a.plane_loops + n), (long long)capacity);
+      scan_small(st, a.lofs, (const long long*)(a.plane_loops + n), (long long)capacity);
       hipLaunchKernelGGL(loops_scatter_kernel, g, dim3(LP_BLOCK), 0, st, a);
-    });
-  });
-}
-
-// ---- mesh topology on device memory (include/ezrt_topology.h): up to eight launches on `st` -- init, join, rank, and with the
-// component group unite, flatten, loops_scan_kernel, scatter -- over the caller's `work`; checked, launched and ordered against a
-// refit by query_call.  `work` is scan (n_tri + 1 int64), then rep and head (T ints each, T the power of two >= 6 n_tri), link and
-// slot (3 n_tri ints each), parent, csize and cflag (n_tri ints each).
-static uint64_t topo_slots(int n_tri) {
-  if (n_tri <= 0) return 0;
-  uint64_t T = 8;
-  while (T < 6ull * (uint64_t)n_tri) T <<= 1;
-  return T;
-}
-size_t ezrt_topology_work_bytes(int n_tri) {
-  if (n_tri <= 0) return 8;
-  const uint64_t n = (uint64_t)n_tri, bytes = (n + 1) * 8 + topo_slots(n_tri) * 8 + 6 * n * 4 + 3 * n * 4;
-  return (size_t)((bytes + 7) / 8 * 8);
-}
-int ezrt_mesh_topology_device(EzrtScene* s, int32_t* twin, uint8_t* edge_class, int32_t* mult, int32_t* root, int32_t* component,
-                              int32_t* comp_root, int32_t* comp_size, uint8_t* comp_flags, int64_t* summary, void* work, size_t work_bytes,
-                              void* stream) {
-  return ezi::guarded("ezrt_mesh_topology_device", [&]() -> int {
-    if (!s || !twin || !edge_class || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    const int group = (root ? 1 : 0) + (component ? 1 : 0) + (comp_root ? 1 : 0) + (comp_size ? 1 : 0) + (comp_flags ? 1 : 0);
-    if (group != 0 && group != 5)
-      return fail(EZRT_ERR_INVALID, "root, component, comp_root, comp_size and comp_flags are given together or not at all");
-    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    const int n_tri = (int)s->n_tri;
-    if (work_bytes < ezrt_topology_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_topology_work_bytes(n_tri)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{twin, H * i4}, {edge_class, H}, {mult, H * i4}, {root, N * i4}, {component, N * i4}, {comp_root, N * i4},
-                          {comp_size, N * i4}, {comp_flags, N}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_topology_work_bytes(n_tri)}},
-                      H, st, [&](dim3, dim3) {
-      TopoArgs a{};
-      a.tri_geom = s->tri_geom.p;
-      a.n_tri = (int32_t)n_tri;
-      a.T = topo_slots(n_tri);
-      a.scan = (long long*)work;
-      a.rep = (int32_t*)(a.scan + N + 1);
-      a.head = (uint32_t*)(a.rep + a.T);
-      a.link = a.head + a.T;
-      a.slot = a.link + H;
-      a.parent = (int32_t*)(a.slot + H);
-      a.csize = a.parent + N;
-      a.cflag = (uint32_t*)(a.csize + N);
-      a.twin = twin, a.edge_class = edge_class, a.mult = mult;
-      a.root = root, a.component = component, a.comp_root = comp_root, a.comp_size = comp_size, a.comp_flags = comp_flags;
-      a.summary = (unsigned long long*)summary;
-      // grid-stride loops: at most TP_GRID_MAX workgroups, a few per CU
-      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + TP_BLOCK - 1) / TP_BLOCK, TP_GRID_MAX)); };
-      const dim3 b(TP_BLOCK), gh = grid(H), gt = grid(N);
-      hipLaunchKernelGGL(topo_init_kernel, grid(a.T), b, 0, st, a, group == 5);
-      hipLaunchKernelGGL(topo_join_kernel, gh, b, 0, st, a);
-      hipLaunchKernelGGL(topo_rank_kernel, gh, b, 0, st, a);
-      if (group == 5) {
-        hipLaunchKernelGGL(topo_unite_kernel, gh, b, 0, st, a);
-        hipLaunchKernelGGL(topo_flatten_kernel, gt, b, 0, st, a);
-        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.scan, (const long long*)nullptr, (long long)n_tri);
-        hipLaunchKernelGGL(topo_scatter_kernel, gt, b, 0, st, a);
-      }
-    });
-  });
-}
-int ezrt_mesh_topology_at_device(EzrtScene* s, const int32_t* tri_a, const int32_t* edge_a, const int32_t* tri_b, int n, int8_t* shared,
-                                 int8_t* opposite, void* stream) {
-  return ezi::guarded("ezrt_mesh_topology_at_device", [&]() -> int {
-    if (!s || !tri_a || !edge_a || !tri_b || !shared || !opposite || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri_a, N * sizeof(int32_t)}, {edge_a, N * sizeof(int32_t)}, {tri_b, N * sizeof(int32_t)}, {shared, N}, {opposite, N}},
-                      N, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(topo_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, tri_a, edge_a, tri_b, (uint32_t)n, shared, opposite);
-    });
-  });
-}
-
-// ---- vertex weld and smooth normals on device memory (include/ezrt_vertices.h): up to fifteen launches on `st` for the weld -- init,
-// join, flag, a prefix sum (sums, loops_scan_kernel, scan), id, the prefix sum again, scatter, rank, and with the flags group link,
-// fans, finish -- over the caller's `work`: ids and cnt (3 n_tri + 1 int64 each), tiles (one int64 per 2048 corners, and one), rep
-// (T ints, T the topology's power of two >= 6 n_tri), then slot, cur, tmp,
-// parent, flagw and fanc (3 n_tri ints each); two launches for the normals over 3 n_tri floats of `work`.  Checked, launched and
-// ordered against a refit by query_call.
-static uint64_t weld_tiles(int n_tri) { return (3ull * (uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
-size_t ezrt_weld_work_bytes(int n_tri) {
-  if (n_tri <= 0) return 8;
-  const uint64_t h = 3ull * (uint64_t)n_tri, bytes = 2 * (h + 1) * 8 + (weld_tiles(n_tri) + 1) * 8 + topo_slots(n_tri) * 4 + 6 * h * 4;
-  return (size_t)((bytes + 7) / 8 * 8);
-}
-int ezrt_mesh_weld_device(EzrtScene* s, int32_t* vertex, int32_t* vert_corner, int32_t* star_offsets, int32_t* star, int32_t* fans,
-                          uint8_t* vert_flags, int64_t* summary, void* work, size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_mesh_weld_device", [&]() -> int {
-    if (!s || !vertex || !vert_corner || !star_offsets || !star || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (!fans != !vert_flags) return fail(EZRT_ERR_INVALID, "fans and vert_flags are given together or not at all");
-    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    const int n_tri = (int)s->n_tri;
-    if (work_bytes < ezrt_weld_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_weld_work_bytes(n_tri)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_tri <= 0) return 0;
-    const size_t H = 3 * (size_t)n_tri, i4 = sizeof(int32_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{vertex, H * i4}, {vert_corner, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4}, {fans, H * i4}, {vert_flags, H},
-                          {summary, 8 * sizeof(int64_t)}, {work, ezrt_weld_work_bytes(n_tri)}},
-                      H, st, [&](dim3, dim3) {
-      WeldArgs a{};
-      a.tri_geom = s->tri_geom.p;
-      a.n_tri = (int32_t)n_tri;
-      a.T = topo_slots(n_tri);
-      a.ids = (long long*)work;
-      a.cnt = a.ids + H + 1;
-      a.tiles = a.cnt + H + 1;
-      const uint64_t B = weld_tiles(n_tri);
-      a.rep = (int32_t*)(a.tiles + B + 1);
-      a.slot = (uint32_t*)(a.rep + a.T);
-      a.cur = (int32_t*)(a.slot + H);
-      a.tmp = a.cur + H;
-      a.parent = a.tmp + H;
-      a.flagw = (uint32_t*)(a.parent + H);
-      a.fanc = (int32_t*)(a.flagw + H);
-      a.vertex = vertex, a.vert_corner = vert_corner, a.star_offsets = star_offsets, a.star = star, a.fans = fans, a.vert_flags = vert_flags;
-      a.summary = (unsigned long long*)summary;
-      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + WD_BLOCK - 1) / WD_BLOCK, WD_GRID_MAX)); };
-      const dim3 b(WD_BLOCK), gh = grid(H), scan(LP_SCAN);
-      hipLaunchKernelGGL(weld_init_kernel, grid(a.T), b, 0, st, a, fans != nullptr);
-      hipLaunchKernelGGL(weld_join_kernel, gh, b, 0, st, a);
-      hipLaunchKernelGGL(weld_flag_kernel, gh, b, 0, st, a);
-      // a prefix sum of x in place over B tiles (ezrt_vertex_kernels.h: weld_scan_kernel); n_dev: its length, read on the device
-      const auto prefix = [&](long long* x, const long long* n_dev) {
-        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)B), b, 0, st, (const long long*)x, a.tiles, n_dev, (long long)H);
-        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), scan, 0, st, a.tiles, (const long long*)nullptr, (long long)B);
-        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)B), b, 0, st, x, (const long long*)a.tiles, n_dev, (long long)H);
-      };
-      prefix(a.ids, nullptr);
-      hipLaunchKernelGGL(weld_id_kernel, gh, b, 0, st, a);
-      prefix(a.cnt, (const long long*)(a.ids + H));
-      hipLaunchKernelGGL(weld_scatter_kernel, grid(H + 1), b, 0, st, a);
-      hipLaunchKernelGGL(weld_rank_kernel, gh, b, 0, st, a);
-      if (fans) {
-        hipLaunchKernelGGL(weld_link_kernel, gh, b, 0, st, a);
-        hipLaunchKernelGGL(weld_fans_kernel, gh, b, 0, st, a);
-        hipLaunchKernelGGL(weld_finish_kernel, gh, b, 0, st, a);
-      }
-    });
-  });
-}
-int ezrt_mesh_weld_at_device(EzrtScene* s, const int32_t* corner_a, const int32_t* corner_b, int n, int8_t* same, void* stream) {
-  return ezi::guarded("ezrt_mesh_weld_at_device", [&]() -> int {
-    if (!s || !corner_a || !corner_b || !same || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n;
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{corner_a, N * sizeof(int32_t)}, {corner_b, N * sizeof(int32_t)}, {same, N}}, N, st, [&](dim3 g, dim3 b) {
-      hipLaunchKernelGGL(weld_at_kernel, g, b, 0, st, s->tri_geom.p, (int32_t)s->n_tri, corner_a, corner_b, (uint32_t)n, same);
-    });
-  });
-}
-size_t ezrt_vertex_normals_work_bytes(int n_tri) {
-  if (n_tri <= 0) return 8;
-  return (size_t)((3ull * (uint64_t)n_tri * sizeof(float) + 7) / 8 * 8);
-}
-int ezrt_vertex_normals_device(EzrtScene* s, float* tri36, int n_tri, const int32_t* vertex, const int32_t* star_offsets, const int32_t* star,
-                               void* work, size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_vertex_normals_device", [&]() -> int {
-    if (!s || !tri36 || !vertex || !star_offsets || !star || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
-    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    if (work_bytes < ezrt_vertex_normals_work_bytes(n_tri))
-      return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_vertex_normals_work_bytes(n_tri)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {vertex, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4},
-                          {work, ezrt_vertex_normals_work_bytes(n_tri)}},
-                      N, st, [&](dim3 g, dim3 b) {
-      VertexNormalArgs a{};
-      a.tri36 = tri36;
-      a.n_tri = (int32_t)n_tri;
-      a.vertex = vertex, a.star_offsets = star_offsets, a.star = star;
-      a.face = (float*)work;
-      hipLaunchKernelGGL(vn_face_kernel, g, b, 0, st, a);
-      hipLaunchKernelGGL(vn_corner_kernel, dim3((unsigned)((H + WD_BLOCK - 1) / WD_BLOCK)), b, 0, st, a);
-    });
-  });
-}
-
-// ---- mesh orientation on device memory (include/ezrt_orient.h): nine launches on `st` -- init, union, flatten, check, the weld's
-// prefix sum (sums, loops_scan_kernel, scan), volume, finish -- over the caller's `work`: scan (n_tri + 1 int64), tiles (one int64 per
-// 2048 triangles, and one), vol (n_tri int64), then par, flat, pf and psz (n_tri ints each) and two words for A; one launch for the
-// rewind.  Checked, launched and ordered against a refit by query_call.
-static uint64_t orient_tiles(int n_tri) { return ((uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
-size_t ezrt_orient_work_bytes(int n_tri) {
-  if (n_tri <= 0) return 8;
-  return (size_t)(32ull * (uint64_t)n_tri + 8ull * orient_tiles(n_tri) + 24ull);
-}
-int ezrt_mesh_orient_device(EzrtScene* s, const int32_t* twin, const uint8_t* edge_class, int outward, uint8_t* flip, int32_t* patch_root,
-                            int32_t* patch, int32_t* proot, int32_t* psize, uint8_t* pflags, int64_t* vol6, int64_t* summary, void* work,
-                            size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_mesh_orient_device", [&]() -> int {
-    if (!s || !twin || !edge_class || !flip || !patch_root || !patch || !proot || !psize || !pflags || !vol6 || !summary || !work)
-      return fail(EZRT_ERR_INVALID, "NULL argument");
-    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    const int n_tri = (int)s->n_tri;
-    if (work_bytes < ezrt_orient_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_orient_work_bytes(n_tri)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{twin, H * i4}, {edge_class, H}, {flip, N}, {patch_root, N * i4}, {patch, N * i4}, {proot, N * i4}, {psize, N * i4},
-                          {pflags, N}, {vol6, N * sizeof(int64_t)}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_orient_work_bytes(n_tri)}},
-                      H, st, [&](dim3, dim3) {
-      OrientArgs a{};
-      a.tri_geom = s->tri_geom.p;
-      a.n_tri = (int32_t)n_tri;
-      a.twin = twin, a.edge_class = edge_class, a.outward = outward != 0 ? 1 : 0;
-      const uint64_t B = orient_tiles(n_tri);
-      a.scan = (long long*)work;
-      a.tiles = a.scan + N + 1;
-      a.vol = a.tiles + B + 1;
-      a.par = (uint32_t*)(a.vol + N);
-      a.flat = a.par + N;
-      a.pf = a.flat + N;
-      a.psz = (int32_t*)(a.pf + N);
-      a.amax = (uint32_t*)(a.psz + N);
-      a.flip = flip, a.patch_root = patch_root, a.patch = patch, a.proot = proot, a.psize = psize, a.pflags = pflags;
-      a.vol6 = (long long*)vol6, a.summary = (unsigned long long*)summary;
-      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + OR_BLOCK - 1) / OR_BLOCK, OR_GRID_MAX)); };
-      const dim3 b(OR_BLOCK), gh = grid(H), gt = grid(N);
-      hipLaunchKernelGGL(orient_init_kernel, gt, b, 0, st, a);
-      hipLaunchKernelGGL(orient_union_kernel, gh, b, 0, st, a);
-      hipLaunchKernelGGL(orient_flatten_kernel, gt, b, 0, st, a);
-      hipLaunchKernelGGL(orient_check_kernel, gt, b, 0, st, a);
-      // the prefix sum of the roots' flags in place over B tiles (ezrt_vertex_kernels.h: weld_scan_kernel)
-      hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)B), dim3(WD_BLOCK), 0, st, (const long long*)a.scan, a.tiles, (const long long*)nullptr, (long long)N);
-      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.tiles, (const long long*)nullptr, (long long)B);
-      hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)B), dim3(WD_BLOCK), 0, st, a.scan, (const long long*)a.tiles, (const long long*)nullptr, (long long)N);
-      hipLaunchKernelGGL(orient_volume_kernel, gt, b, 0, st, a);
-      hipLaunchKernelGGL(orient_finish_kernel, gt, b, 0, st, a);
-    });
-  });
-}
-int ezrt_rewind_device(EzrtScene* s, float* tri36, int n_tri, const uint8_t* flip, void* stream) {
-  return ezi::guarded("ezrt_rewind_device", [&]() -> int {
-    if (!s || !tri36 || !flip) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
-    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri;
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {flip, N}}, N, st, [&](dim3, dim3) {
-      hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((N + OR_BLOCK - 1) / OR_BLOCK)), dim3(OR_BLOCK), 0, st, tri36, (uint32_t)n_tri, flip);
-    });
-  });
-}
-
-// ---- boundary loops on device memory (include/ezrt_boundary.h): 17 launches and the rounds of the ranking on `st` -- init, next,
-// union, open, a prefix sum (sums, loops_scan_kernel, scan) that compacts the BOUNDARY half-edges, rank init, ceil(log2(3 n_tri)) jumping
-// rounds, flag, the prefix sum over the compacted list that numbers the heads, number, the prefix sum of the lengths, scatter -- over the
-// caller's `work`: scan_c and scan_n (3 n_tri + 1 int64 each), tiles (one int64 per 2048 half-edges, and one), the two buffers of the
-// ranking (3 n_tri int64 each), four int64 of counts, then pred, par and comp (3 n_tri ints each); one launch for the cap.  Checked,
-// launched and ordered against a refit by query_call.
-static uint64_t boundary_tiles(int n_tri) { return (3ull * (uint64_t)n_tri + WD_TILE - 1) / WD_TILE; }
-size_t ezrt_boundary_work_bytes(int n_tri) {
-  if (n_tri <= 0) return 8;
-  return (size_t)(132ull * (uint64_t)n_tri + 4ull * ((uint64_t)n_tri & 1ull) + 8ull * boundary_tiles(n_tri) + 56ull);
-}
-int ezrt_mesh_boundary_device(EzrtScene* s, const int32_t* twin, const uint8_t* edge_class, int32_t* next, int32_t* loop, int32_t* pos,
-                              int32_t* order, int32_t* loop_offsets, uint8_t* lflags, int64_t* area2, int64_t* summary, void* work,
-                              size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_mesh_boundary_device", [&]() -> int {
-    if (!s || !twin || !edge_class || !next || !loop || !pos || !order || !loop_offsets || !lflags || !summary || !work)
-      return fail(EZRT_ERR_INVALID, "NULL argument");
-    if ((int64_t)s->n_tri > (int64_t)(INT32_MAX / 3)) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    const int n_tri = (int)s->n_tri;
-    if (work_bytes < ezrt_boundary_work_bytes(n_tri)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_boundary_work_bytes(n_tri)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t), i8 = sizeof(int64_t);
-    hipStream_t st = (hipStream_t)stream;
-    // (a null area2 is skipped by the check, as a null input of the overlap lists is)
-    return query_call(s, {{twin, H * i4}, {edge_class, H}, {next, H * i4}, {loop, H * i4}, {pos, H * i4}, {order, H * i4},
-                          {loop_offsets, (H + 1) * i4}, {lflags, H}, {area2, 3 * H * i8}, {summary, 8 * i8},
-                          {work, ezrt_boundary_work_bytes(n_tri)}},
-                      H, st, [&](dim3, dim3) {
-      BoundaryArgs a{};
-      a.tri_geom = s->tri_geom.p;
-      a.n_tri = (int32_t)n_tri;
-      a.twin = twin, a.edge_class = edge_class;
-      const uint64_t T = boundary_tiles(n_tri);
-      a.scan_c = (long long*)work;
-      a.scan_n = a.scan_c + H + 1;
-      a.tiles = a.scan_n + H + 1;
-      a.jump[0] = (unsigned long long*)(a.tiles + T + 1);
-      a.jump[1] = a.jump[0] + H;
-      a.cnt = (long long*)(a.jump[1] + H);
-      a.pred = (int32_t*)(a.cnt + 4);
-      a.par = (uint32_t*)(a.pred + H);
-      a.comp = (int32_t*)(a.par + H);
-      a.open = (uint32_t*)a.scan_n;
-      a.lens = a.scan_c;
-      int rounds = 0;
-      while ((1ull << rounds) < (uint64_t)H) rounds++; // ceil(log2(3 n_tri)): at most 32
-      a.rounds = rounds;
-      a.next = next, a.loop = loop, a.pos = pos, a.order = order, a.loop_offsets = loop_offsets, a.lflags = lflags;
-      a.area2 = (long long*)area2, a.summary = (unsigned long long*)summary;
-      const dim3 b(BD_BLOCK), g((unsigned)std::min<uint64_t>((H + BD_BLOCK - 1) / BD_BLOCK, BD_GRID_MAX));
-      // a prefix sum of x in place over T tiles (ezrt_vertex_kernels.h: weld_scan_kernel); n_dev: its length, read on the device
-      const auto scan = [&](long long* x, const long long* n_dev) {
-        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, (const long long*)x, a.tiles, n_dev, (long long)H);
-        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, a.tiles, (const long long*)nullptr, (long long)T);
-        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, x, (const long long*)a.tiles, n_dev, (long long)H);
-      };
-      hipLaunchKernelGGL(bd_init_kernel, g, b, 0, st, a);
-      hipLaunchKernelGGL(bd_next_kernel, g, b, 0, st, a);
-      hipLaunchKernelGGL(bd_union_kernel, g, b, 0, st, a);
-      hipLaunchKernelGGL(bd_open_kernel, g, b, 0, st, a);
-      scan(a.scan_c, nullptr);
-      hipLaunchKernelGGL(bd_rank_init_kernel, g, b, 0, st, a);
-      for (int r = 0; r < rounds; r++) hipLaunchKernelGGL(bd_jump_kernel, g, b, 0, st, a, r & 1); // rounds are separated by launches
-      hipLaunchKernelGGL(bd_flag_kernel, g, b, 0, st, a);
-      scan(a.scan_n, a.cnt);
-      hipLaunchKernelGGL(bd_number_kernel, g, b, 0, st, a);
-      scan(a.lens, a.cnt + 1);
-      hipLaunchKernelGGL(bd_scatter_kernel, g, b, 0, st, a);
-    });
-  });
-}
-int ezrt_cap_rows_device(EzrtScene* s, const float* tri36, int n_tri, const int32_t* order, const int32_t* loop, const int32_t* pos,
-                         const int32_t* loop_offsets, const uint8_t* lflags, const int64_t* summary, float* cap, uint8_t* cap_valid,
-                         void* stream) {
-  return ezi::guarded("ezrt_cap_rows_device", [&]() -> int {
-    if (!s || !tri36 || !order || !loop || !pos || !loop_offsets || !lflags || !summary || !cap || !cap_valid)
-      return fail(EZRT_ERR_INVALID, "NULL argument");
-    if ((int64_t)n_tri != (int64_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n_tri is %d, the scene has %lld triangles", n_tri, (long long)s->n_tri);
-    if (n_tri > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 triangles");
-    if (n_tri <= 0) return 0;
-    const size_t N = (size_t)n_tri, H = 3 * N, i4 = sizeof(int32_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {order, H * i4}, {loop, H * i4}, {pos, H * i4}, {loop_offsets, (H + 1) * i4},
-                          {lflags, H}, {summary, 8 * sizeof(int64_t)}, {cap, H * 36 * sizeof(float)}, {cap_valid, H}},
-                      H, st, [&](dim3, dim3) {
-      hipLaunchKernelGGL(cap_rows_kernel, dim3((unsigned)((H + BD_BLOCK - 1) / BD_BLOCK)), dim3(BD_BLOCK), 0, st, tri36, (int32_t)n_tri, order, loop,
-                         pos, loop_offsets, lflags, (const long long*)summary, cap, cap_valid);
-    });
-  });
-}
-
-// ---- plane clipping on device memory (include/ezrt_clip.h).  Count: a memset of the summary, clip_count_kernel, and the weld's tiled
-// prefix sum (sums, loops_scan_kernel, scan) of offsets in place over the caller's `work`, the tiles' sums and their total.  Fill: one
-// launch, the staged instance where tri36 and out are 16-byte aligned, else the per-lane one (always, in the measurement variant
-// EZRT_CLIP_PER_LANE).  Checked, launched and ordered against a refit by query_call; the scene's records are not read.
-#ifndef EZRT_CLIP_PER_LANE
-#define EZRT_CLIP_PER_LANE 0
-#endif
-static uint64_t clip_tiles(int n_rows) { return ((uint64_t)n_rows + WD_TILE - 1) / WD_TILE; }
-size_t ezrt_clip_work_bytes(int n_rows) {
-  if (n_rows <= 0) return 8;
-  return (size_t)(8ull * clip_tiles(n_rows) + 8ull);
-}
-int ezrt_clip_count_device(EzrtScene* s, const float* tri36, int n_rows, const float* plane4, int64_t* offsets, int64_t* summary, void* work,
-                           size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_clip_count_device", [&]() -> int {
-    if (!s || !tri36 || !plane4 || !offsets || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
-    if (n_rows > INT32_MAX / 2) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 2 rows");
-    if (work_bytes < ezrt_clip_work_bytes(n_rows)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_clip_work_bytes(n_rows)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_rows == 0) return 0;
-    const size_t N = (size_t)n_rows, i8 = sizeof(int64_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {plane4, 4 * sizeof(float)}, {offsets, (N + 1) * i8}, {summary, 8 * i8},
-                          {work, ezrt_clip_work_bytes(n_rows)}},
-                      N, st, [&](dim3, dim3) -> int {
-      const uint64_t T = clip_tiles(n_rows);
-      long long *x = (long long*)offsets, *tiles = (long long*)work;
-      HIP_TRY(hipMemsetAsync(summary, 0, 8 * i8, st));
-      hipLaunchKernelGGL(clip_count_kernel, dim3((unsigned)((N + CL_BLOCK - 1) / CL_BLOCK)), dim3(CL_BLOCK), 0, st, tri36, (int32_t)n_rows, plane4, x,
-                         (unsigned long long*)summary);
-      // the prefix sum of the counts in place over T tiles (ezrt_vertex_kernels.h: weld_scan_kernel); the total lands in offsets[n_rows]
-      hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, (const long long*)x, tiles, (const long long*)nullptr, (long long)N);
-      hipLaunchKernelGGL(loops_scan_kernel, dim3(1), dim3(LP_SCAN), 0, st, tiles, (const long long*)nullptr, (long long)T);
-      hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)T), dim3(WD_BLOCK), 0, st, x, (const long long*)tiles, (const long long*)nullptr, (long long)N);
-      return 0;
-    });
-  });
-}
-int ezrt_clip_rows_device(EzrtScene* s, const float* tri36, int n_rows, const float* plane4, const int64_t* offsets, int64_t capacity, float* out,
-                          int32_t* src, int8_t* cut_edge, void* stream) {
-  return ezi::guarded("ezrt_clip_rows_device", [&]() -> int {
-    if (!s || !tri36 || !plane4 || !offsets) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
-    if (n_rows > INT32_MAX / 2) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 2 rows");
-    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
-    // (the byte count below must not wrap: a wrapped one would pass the buffer check and leave the kernel a capacity that is none)
-    if (capacity > (int64_t)(PTRDIFF_MAX / (36 * sizeof(float)))) return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
-    if (!out && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL out with capacity > 0");
-    if (n_rows == 0) return 0;
-    const size_t N = (size_t)n_rows, cap = (size_t)capacity, row = 36 * sizeof(float);
-    if (out && cap > 0) {
-      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + cap * row;
-      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * row}, {plane4, 4 * sizeof(float)}, {offsets, (N + 1) * sizeof(int64_t)}, {cap ? out : nullptr, cap * row},
-                          {cap ? src : nullptr, cap * sizeof(int32_t)}, {cap ? cut_edge : nullptr, cap}},
-                      N, st, [&](dim3, dim3) {
-      if (cap == 0) return; // nothing fits: nothing is written
-      ClipFillArgs a{};
-      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.plane4 = plane4, a.offsets = (const long long*)offsets, a.capacity = (long long)capacity;
-      a.out = out, a.src = src, a.cut_edge = cut_edge;
-      const dim3 g((unsigned)((N + CL_BLOCK - 1) / CL_BLOCK)), b(CL_BLOCK);
-      const bool staged = !EZRT_CLIP_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
-      if (staged) hipLaunchKernelGGL(clip_fill_kernel<true>, g, b, 0, st, a);
-      else hipLaunchKernelGGL(clip_fill_kernel<false>, g, b, 0, st, a);
-    });
-  });
-}
-
-// ---- subdivision on device memory (include/ezrt_subdivide.h): a memset of the summary, in Loop mode subdiv_vertex_kernel over the
-// caller's `work` (four words per possible vertex), and one fill launch, the staged instance where tri36 and out are 16-byte aligned,
-// else the per-lane one (always, in the measurement variant EZRT_SUBDIV_PER_LANE).  The output's size is known, so there is no count.
-// Checked, launched and ordered against a refit by query_call; the scene's records are not read.
-#ifndef EZRT_SUBDIV_PER_LANE
-#define EZRT_SUBDIV_PER_LANE 0
-#endif
-#ifndef EZRT_SUBDIV_SKIP_VERTEX // measurement variant: Loop mode without its vertex pass, for timing the fill alone (the slots are whatever `work` held)
-#define EZRT_SUBDIV_SKIP_VERTEX 0
-#endif
-size_t ezrt_subdivide_work_bytes(int n_rows, int mode) {
-  if (n_rows <= 0 || mode != EZRT_SUBDIVIDE_LOOP) return 8;
-  return (size_t)(48ull * (uint64_t)n_rows + 8ull);
-}
-int ezrt_subdivide_rows_device(EzrtScene* s, const float* tri36, int n_rows, int mode, const int32_t* twin, const uint8_t* edge_class,
-                               const int32_t* vertex, const int32_t* star_offsets, const int32_t* star, const uint8_t* vert_flags, float* out,
-                               int64_t* summary, void* work, size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_subdivide_rows_device", [&]() -> int {
-    if (!s || !tri36 || !out || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
-    if (n_rows > INT32_MAX / 12) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 12 rows");
-    if (mode != EZRT_SUBDIVIDE_MIDPOINT && mode != EZRT_SUBDIVIDE_LOOP) return fail(EZRT_ERR_INVALID, "mode %d is neither MIDPOINT nor LOOP", mode);
-    const int given = !!twin + !!edge_class + !!vertex + !!star_offsets + !!star + !!vert_flags;
-    if (given != 0 && given != 6)
-      return fail(EZRT_ERR_INVALID, "twin, edge_class, vertex, star_offsets, star and vert_flags are given together or not at all");
-    if (mode == EZRT_SUBDIVIDE_MIDPOINT && given) return fail(EZRT_ERR_INVALID, "the topology and weld arrays must be NULL in MIDPOINT mode");
-    if (mode == EZRT_SUBDIVIDE_LOOP && !given) return fail(EZRT_ERR_INVALID, "LOOP mode needs the topology and weld arrays");
-    if (work_bytes < ezrt_subdivide_work_bytes(n_rows, mode))
-      return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_subdivide_work_bytes(n_rows, mode)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_rows == 0) return 0;
-    const size_t N = (size_t)n_rows, H = 3 * N, row = 36 * sizeof(float), i4 = sizeof(int32_t);
-    {
-      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + 4 * N * row;
-      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * row}, {out, 4 * N * row}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_subdivide_work_bytes(n_rows, mode)},
-                          {twin, H * i4}, {edge_class, H}, {vertex, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4}, {vert_flags, H}},
-                      N, st, [&](dim3, dim3) -> int {
-      SubdivArgs a{};
-      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.mode = (int32_t)mode;
-      a.twin = twin, a.edge_class = edge_class, a.vertex = vertex, a.star_offsets = star_offsets, a.star = star, a.vert_flags = vert_flags;
-      a.out = out, a.summary = (unsigned long long*)summary, a.slot = (uint32_t*)work;
-      HIP_TRY(hipMemsetAsync(summary, 0, 8 * sizeof(int64_t), st));
-      const dim3 b(SD_BLOCK);
-      if (mode == EZRT_SUBDIVIDE_LOOP && !EZRT_SUBDIV_SKIP_VERTEX) hipLaunchKernelGGL(subdiv_vertex_kernel, dim3((unsigned)((H + SD_BLOCK - 1) / SD_BLOCK)), b, 0, st, a);
-      const bool staged = !EZRT_SUBDIV_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
-      if (staged) hipLaunchKernelGGL(subdiv_fill_kernel<true>, dim3((unsigned)std::min<uint64_t>((N + SD_TILE - 1) / SD_TILE, SD_GRID_MAX)), b, 0, st, a);
-      else hipLaunchKernelGGL(subdiv_fill_kernel<false>, dim3((unsigned)((N + SD_BLOCK - 1) / SD_BLOCK)), b, 0, st, a);
-      return 0;
-    });
-  });
-}
-
-// ---- decimation on device memory (include/ezrt_decimate.h).  Count: init, insert, flag, the weld's tiled prefix sum (sums,
-// loops_scan_kernel, scan) over the corners, cells, with EZRT_DECIMATE_DEDUP classify, keep, and the prefix sum again over the rows,
-// in place in offsets -- up to twelve launches over the caller's `work`: ids (3 n_rows + 1 int64), tiles (one int64 per 2048 corners,
-// and one), key (T int64, T the topology's power of two >= 6 n_rows), sum (3 T int64), cnt, low (T ints each), mn, mx (3 T ints each),
-// slot (3 n_rows ints), rep2 (T2 ints, T2 the power of two >= 2 n_rows), slot2 (n_rows ints).  Fill: one launch, the staged instance
-// where tri36 and out are 16-byte aligned, else the per-lane one (always, in the measurement variant EZRT_DECIMATE_PER_LANE).
-// Checked, launched and ordered against a refit by query_call; the scene's records are not read.
-#ifndef EZRT_DECIMATE_PER_LANE
-#define EZRT_DECIMATE_PER_LANE 0
-#endif
-static uint64_t dec_slots2(int n_rows) {
-  uint64_t T = 8;
-  while (T < 2ull * (uint64_t)n_rows) T <<= 1;
-  return T;
-}
-size_t ezrt_decimate_work_bytes(int n_rows) {
-  if (n_rows <= 0) return 8;
-  const uint64_t n = (uint64_t)n_rows;
-  return (size_t)(40ull * n + 8ull * weld_tiles(n_rows) + 64ull * topo_slots(n_rows) + 4ull * dec_slots2(n_rows) + 16ull);
-}
-int ezrt_decimate_count_device(EzrtScene* s, const float* tri36, int n_rows, const float* grid4, int flags, int32_t* cell, int32_t* cell_corner,
-                               float* cell_point, int64_t* offsets, int64_t* summary, void* work, size_t work_bytes, void* stream) {
-  return ezi::guarded("ezrt_decimate_count_device", [&]() -> int {
-    if (!s || !tri36 || !grid4 || !cell || !cell_corner || !cell_point || !offsets || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
-    if (n_rows > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 rows");
-    if (flags & ~EZRT_DECIMATE_DEDUP) return fail(EZRT_ERR_INVALID, "flags %d has a bit that is not EZRT_DECIMATE_DEDUP", flags);
-    if (work_bytes < ezrt_decimate_work_bytes(n_rows)) return fail(EZRT_ERR_INVALID, "work_bytes is below ezrt_decimate_work_bytes(n_rows)");
-    if ((uintptr_t)work % sizeof(int64_t)) return fail(EZRT_ERR_INVALID, "work is not 8-byte aligned");
-    if (n_rows == 0) return 0;
-    const size_t N = (size_t)n_rows, H = 3 * N, i4 = sizeof(int32_t), i8 = sizeof(int64_t);
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * 36 * sizeof(float)}, {grid4, 4 * sizeof(float)}, {cell, H * i4}, {cell_corner, H * i4},
-                          {cell_point, H * 3 * sizeof(float)}, {offsets, (N + 1) * i8}, {summary, 8 * i8}, {work, ezrt_decimate_work_bytes(n_rows)}},
-                      H, st, [&](dim3, dim3) {
-      DecArgs a{};
-      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.grid4 = grid4, a.flags = (int32_t)flags;
-      a.T = topo_slots(n_rows), a.T2 = dec_slots2(n_rows);
-      const uint64_t B = weld_tiles(n_rows), R = clip_tiles(n_rows);
-      a.ids = (long long*)work;
-      a.tiles = a.ids + H + 1;
-      a.key = (unsigned long long*)(a.tiles + B + 1);
-      a.sum = a.key + a.T;
-      a.cnt = (uint32_t*)(a.sum + 3 * a.T);
-      a.low = (int32_t*)(a.cnt + a.T);
-      a.mn = (uint32_t*)(a.low + a.T);
-      a.mx = a.mn + 3 * a.T;
-      a.slot = a.mx + 3 * a.T;
-      a.rep2 = (int32_t*)(a.slot + H);
-      a.slot2 = (uint32_t*)(a.rep2 + a.T2);
-      a.cell = cell, a.cell_corner = cell_corner, a.cell_point = cell_point, a.offsets = (long long*)offsets;
-      a.summary = (unsigned long long*)summary;
-      const auto grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + DC_BLOCK - 1) / DC_BLOCK, DC_GRID_MAX)); };
-      const dim3 b(DC_BLOCK), gh = grid(H), scan(LP_SCAN), wb(WD_BLOCK);
-      // a prefix sum of x[0 .. n) in place over `tl` tiles (ezrt_vertex_kernels.h: weld_scan_kernel); the total lands in x[n]
-      const auto prefix = [&](long long* x, uint64_t n, uint64_t tl) {
-        hipLaunchKernelGGL(weld_sums_kernel, dim3((unsigned)tl), wb, 0, st, (const long long*)x, a.tiles, (const long long*)nullptr, (long long)n);
-        hipLaunchKernelGGL(loops_scan_kernel, dim3(1), scan, 0, st, a.tiles, (const long long*)nullptr, (long long)tl);
-        hipLaunchKernelGGL(weld_scan_kernel, dim3((unsigned)tl), wb, 0, st, x, (const long long*)a.tiles, (const long long*)nullptr, (long long)n);
-      };
-      hipLaunchKernelGGL(dec_init_kernel, grid(3 * a.T), b, 0, st, a);
-      hipLaunchKernelGGL(dec_insert_kernel, gh, b, 0, st, a);
-      hipLaunchKernelGGL(dec_flag_kernel, gh, b, 0, st, a);
-      prefix(a.ids, H, B);
-      hipLaunchKernelGGL(dec_cells_kernel, gh, b, 0, st, a);
-      if (flags & EZRT_DECIMATE_DEDUP) hipLaunchKernelGGL(dec_classify_kernel, grid(N), b, 0, st, a);
-      hipLaunchKernelGGL(dec_keep_kernel, dim3((unsigned)((N + DC_BLOCK - 1) / DC_BLOCK)), b, 0, st, a);
-      prefix(a.offsets, N, R);
-    });
-  });
-}
-int ezrt_decimate_rows_device(EzrtScene* s, const float* tri36, int n_rows, const int32_t* cell, const float* cell_point, const int64_t* offsets,
-                              int64_t capacity, float* out, int32_t* src, void* stream) {
-  return ezi::guarded("ezrt_decimate_rows_device", [&]() -> int {
-    if (!s || !tri36 || !cell || !cell_point || !offsets) return fail(EZRT_ERR_INVALID, "NULL argument");
-    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
-    if (n_rows > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 rows");
-    if (capacity < 0) return fail(EZRT_ERR_INVALID, "capacity < 0");
-    // (the byte count below must not wrap: a wrapped one would pass the buffer check and leave the kernel a capacity that is none)
-    if (capacity > (int64_t)(PTRDIFF_MAX / (36 * sizeof(float)))) return fail(EZRT_ERR_INVALID, "capacity exceeds what an array can hold");
-    if (!out && capacity > 0) return fail(EZRT_ERR_INVALID, "NULL out with capacity > 0");
-    if (n_rows == 0) return 0;
-    const size_t N = (size_t)n_rows, H = 3 * N, cap = (size_t)capacity, row = 36 * sizeof(float);
-    if (out && cap > 0) {
-      const uintptr_t i0 = (uintptr_t)tri36, i1 = i0 + N * row, o0 = (uintptr_t)out, o1 = o0 + cap * row;
-      if (i0 < o1 && o0 < i1) return fail(EZRT_ERR_INVALID, "out overlaps tri36");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tri36, N * row}, {cell, H * sizeof(int32_t)}, {cell_point, H * 3 * sizeof(float)}, {offsets, (N + 1) * sizeof(int64_t)},
-                          {cap ? out : nullptr, cap * row}, {cap ? src : nullptr, cap * sizeof(int32_t)}},
-                      N, st, [&](dim3, dim3) {
-      if (cap == 0) return; // nothing fits: nothing is written
-      DecFillArgs a{};
-      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.cell = cell, a.cell_point = cell_point, a.offsets = (const long long*)offsets;
-      a.capacity = (long long)capacity, a.out = out, a.src = src;
-      const dim3 g((unsigned)((N + DC_BLOCK - 1) / DC_BLOCK)), b(DC_BLOCK);
-      const bool staged = !EZRT_DECIMATE_PER_LANE && ((uintptr_t)tri36 | (uintptr_t)out) % 16 == 0;
-      if (staged) hipLaunchKernelGGL(dec_fill_kernel<true>, g, b, 0, st, a);
-      else hipLaunchKernelGGL(dec_fill_kernel<false>, g, b, 0, st, a);
     });
   });
 }

@@ -1,5 +1,5 @@
 // ezrt_subdiv_kernels.h -- the kernels of the subdivision (include/ezrt_subdivide.h, rules S1 to S9): four rows per caller's row, by
-// midpoints or by Loop's scheme.  Included by ezrt_queries.hip, after ezrt_clip_kernels.h (it uses topo_bits of ezrt_topology_kernels.h
+// midpoints or by Loop's scheme.  Included by ezrt_mesh.hip, after ezrt_clip_kernels.h (it uses topo_bits of ezrt_topology_kernels.h
 // and ezi::tri_normal, the N1 of ezrt_vertices.h).
 //
 //   subdiv_vertex_kernel   S4 .. S7, Loop mode: one lane per corner; the lane that is the FIRST corner of its vertex's star walks the

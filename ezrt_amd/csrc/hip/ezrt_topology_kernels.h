@@ -1,12 +1,12 @@
 // ezrt_topology_kernels.h -- the kernels of the mesh topology (include/ezrt_topology.h, rules M1 to M7): edge twins, edge classes and
-// edge-connected components of the whole mesh, on bits alone.  Included by ezrt_queries.hip, after ezrt_point_queries.h (it uses
-// loops_hash and loops_scan_kernel of the plane loops).
+// edge-connected components of the whole mesh, on bits alone.  Included by ezrt_mesh.hip, after ezrt_scan_kernels.h (it uses
+// loops_hash; the host numbers the components with scan_small).
 //
 //   topo_init_kernel      the table, the union-find, the accumulators and the summary, whatever `work` held
 //   topo_join_kernel      M3: one lane per half-edge; claims or finds the slot of its undirected edge, pushes itself onto the slot's list
 //   topo_rank_kernel      M4, M5, M7: one lane per half-edge; walks its slot's list: m, its direction group, its rank; twin, class, mult
 //   topo_unite_kernel     M6: one lane per half-edge; unites its triangle with the triangle of its slot's representative
-//   topo_flatten_kernel   M6: one lane per triangle; its root, the root's size and flags, the flag that loops_scan_kernel numbers
+//   topo_flatten_kernel   M6: one lane per triangle; its root, the root's size and flags, the flag that scan_block_kernel numbers
 //   topo_scatter_kernel   M6: one lane per triangle; component, and comp_root / comp_size / comp_flags of a root; summary[6]
 //   topo_at_kernel        the same rule for pairs already held: one lane per pair, no table
 //
@@ -32,7 +32,6 @@
 #pragma once
 
 constexpr int TP_BLOCK = 256;
-constexpr unsigned TP_GRID_MAX = 4096;       // workgroups of a grid-stride launch: 16 per CU
 constexpr uint32_t TP_END = 0xFFFFFFFFu;   // the end of a slot's list, an empty head
 constexpr uint32_t TP_DEAD = 0xFFFFFFFEu;  // link[h] of a half-edge whose triangle is not TOPO-live (an entry is at most 0xFFFFFFFB)
 

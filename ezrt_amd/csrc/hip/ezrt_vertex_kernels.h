@@ -1,14 +1,12 @@
 // ezrt_vertex_kernels.h -- the kernels of the vertex weld and the smooth normals (include/ezrt_vertices.h, rules W1 to W7 and N1 to
 // N4): the indexed mesh of the scene's triangles, the star of every vertex, its fans and flags, and the reference's smooth normals
-// over the stars.  Included by ezrt_queries.hip, after ezrt_topology_kernels.h (it uses its keys, its union-find, loops_hash and
-// loops_scan_kernel).
+// over the stars.  Included by ezrt_mesh.hip, after ezrt_scan_kernels.h and ezrt_topology_kernels.h (it uses the topology's keys and
+// union-find, and loops_hash; its two prefix sums are scan_tiled, launched by the host).
 //
 //   weld_init_kernel     the table, the counters, the union-find, the accumulators and the summary, whatever `work` held
 //   weld_join_kernel     W1, W2: one lane per corner; claims or finds the slot of its key; atomicMin leaves the key's lowest corner
-//   weld_flag_kernel     W2: one lane per corner; 1 where the corner is the lowest of its key (loops_scan_kernel numbers them); L
-//   weld_sums_kernel, weld_scan_kernel   the prefix sums of W2 and W3 over many workgroups: a tile's sum, loops_scan_kernel over the
-//                        tiles' sums, then the tile's own scan on top of its offset -- loops_scan_kernel's contract, in three launches
-//   weld_id_kernel       W2, W3: one lane per corner; vertex, vert_corner, and the valence counted into cnt (loops_scan_kernel sums)
+//   weld_flag_kernel     W2: one lane per corner; 1 where the corner is the lowest of its key (scan_tiled numbers them); L
+//   weld_id_kernel       W2, W3: one lane per corner; vertex, vert_corner, and the valence counted into cnt (scan_tiled sums)
 //   weld_scatter_kernel  W3: one lane per corner; its star's entries in arrival order into tmp; star_offsets; the largest valence
 //   weld_rank_kernel     W3: one lane per corner; its rank among its star's corners: star comes out ascending whatever the order
 //   weld_link_kernel     W4, W5, W6: one lane per corner; walks its star: m of its two edges, and unites itself with lower corners
@@ -37,9 +35,6 @@
 #pragma once
 
 constexpr int WD_BLOCK = 256;
-constexpr unsigned WD_GRID_MAX = 4096; // workgroups of a grid-stride launch: 16 per CU
-constexpr int WD_SCAN_PER = 8;          // entries per lane of a scan tile
-constexpr int WD_TILE = WD_BLOCK * WD_SCAN_PER;
 
 struct WeldArgs {
   const float4* tri_geom;
@@ -48,7 +43,7 @@ struct WeldArgs {
   // work
   long long* ids;    // 3 n_tri + 1: 1 at the lowest corner of a key, then its exclusive prefix sum; [3 n_tri] = V
   long long* cnt;    // 3 n_tri + 1: the valence of vertex v, then its exclusive prefix sum; [V] = L
-  long long* tiles;  // ceil(3 n_tri / WD_TILE) + 1: the sums of a scan's tiles, then their exclusive prefix sum
+  long long* tiles;  // ceil(3 n_tri / SCAN_TILE) + 1: the sums of a scan's tiles, then their exclusive prefix sum
   int32_t* rep;      // T: a corner of the slot's key, in the end the lowest; -1 empty
   uint32_t* slot;    // 3 n_tri
   int32_t* cur;      // 3 n_tri: the entries of star v scattered so far
@@ -150,60 +145,8 @@ __global__ __launch_bounds__(WD_BLOCK) void weld_flag_kernel(WeldArgs a) {
   }
 }
 
-// x[0 .. n) -> its exclusive prefix sum IN PLACE, the total in x[n]; n = min(*n_dev, n_max) where n_dev is given, else n_max:
-// loops_scan_kernel's contract, but over ceil(n_max / WD_TILE) workgroups (one workgroup took 5.3 of the weld's 6.2 ms per 10^6
-// corners).  weld_sums_kernel: tile b's sum into tiles[b] (0 behind n); loops_scan_kernel over tiles; weld_scan_kernel: the tile's
-// own exclusive scan plus tiles[b].  A tile is WD_BLOCK lanes of WD_SCAN_PER consecutive entries; tiles cross launch boundaries.
-__device__ inline unsigned long long weld_scan_n(const long long* n_dev, long long n_max) {
-  long long nn = n_dev ? *n_dev : n_max;
-  nn = nn < 0 ? 0 : (nn > n_max ? n_max : nn);
-  return (unsigned long long)nn;
-}
-__global__ __launch_bounds__(WD_BLOCK) void weld_sums_kernel(const long long* x, long long* tiles, const long long* n_dev, long long n_max) {
-  __shared__ long long part[WD_BLOCK / 64];
-  const unsigned long long n = weld_scan_n(n_dev, n_max), base = (unsigned long long)blockIdx.x * WD_TILE;
-  long long s = 0;
-#pragma unroll
-  for (int j = 0; j < WD_SCAN_PER; j++) { // coalesced: the order of an integer sum does not matter
-    const unsigned long long i = base + (unsigned long long)j * WD_BLOCK + threadIdx.x;
-    s += i < n ? x[i] : 0;
-  }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long long t = 0;
-    for (int w = 0; w < WD_BLOCK / 64; w++) t += part[w];
-    tiles[blockIdx.x] = t;
-  }
-}
-__global__ __launch_bounds__(WD_BLOCK) void weld_scan_kernel(long long* x, const long long* tiles, const long long* n_dev, long long n_max) {
-  __shared__ long long sums[WD_BLOCK];
-  const unsigned long long n = weld_scan_n(n_dev, n_max), lo = (unsigned long long)blockIdx.x * WD_TILE + (unsigned long long)threadIdx.x * WD_SCAN_PER;
-  const uint32_t t = threadIdx.x;
-  long long v[WD_SCAN_PER], s = 0;
-#pragma unroll
-  for (int j = 0; j < WD_SCAN_PER; j++) {
-    v[j] = lo + j < n ? x[lo + j] : 0;
-    s += v[j];
-  }
-  sums[t] = s;
-  __syncthreads();
-  for (uint32_t o = 1; o < WD_BLOCK; o <<= 1) {
-    const long long add = t >= o ? sums[t - o] : 0;
-    __syncthreads();
-    sums[t] += add;
-    __syncthreads();
-  }
-  long long run = tiles[blockIdx.x] + sums[t] - s;
-#pragma unroll
-  for (int j = 0; j < WD_SCAN_PER; j++) {
-    if (lo + j < n) x[lo + j] = run;
-    run += v[j];
-  }
-  if (blockIdx.x == 0 && t == 0) x[n] = tiles[gridDim.x]; // the total: loops_scan_kernel left it behind the tiles' sums
-}
-
+// (the prefix sums of W2 and W3 run between these launches: scan_tiled of ezrt_scan_kernels.h, over many workgroups -- one workgroup
+// took 5.3 of the weld's 6.2 ms per 10^6 corners)
 __global__ __launch_bounds__(WD_BLOCK) void weld_id_kernel(WeldArgs a) {
   const uint64_t H = 3ull * (uint64_t)a.n_tri, stride = (uint64_t)gridDim.x * WD_BLOCK;
   for (uint64_t c = (uint64_t)blockIdx.x * WD_BLOCK + threadIdx.x; c < H; c += stride) {

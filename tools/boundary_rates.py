@@ -35,8 +35,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 P = C.c_void_p
-KERNELS = ("bd_init", "bd_next", "bd_union", "bd_open", "bd_rank_init", "bd_jump", "bd_flag", "bd_number", "bd_scatter", "cap_rows", "weld_sums",
-           "loops_scan", "weld_scan", "topo_init", "topo_join", "topo_rank")
+KERNELS = ("bd_init", "bd_next", "bd_union", "bd_open", "bd_rank_init", "bd_jump", "bd_flag", "bd_number", "bd_scatter", "cap_rows", "scan_tile_sums",
+           "scan_block", "scan_tiles", "topo_init", "topo_join", "topo_rank")
 
 
 def mesh(name, hip):

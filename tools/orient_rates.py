@@ -39,7 +39,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 P = C.c_void_p
 OUTS = ("flip", "patch_root", "patch", "proot", "psize", "pflags", "vol6")
-KERNELS = ("orient_init", "orient_union", "orient_flatten", "orient_check", "weld_sums", "loops_scan", "weld_scan", "orient_volume", "orient_finish",
+KERNELS = ("orient_init", "orient_union", "orient_flatten", "orient_check", "scan_tile_sums", "scan_block", "scan_tiles", "orient_volume", "orient_finish",
            "rewind")
 
 

@@ -95,7 +95,7 @@ def kernel_stats(path):
     for f in glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row.get("Name", "")
-            for k in ("topo_init", "topo_join", "topo_rank", "topo_unite", "topo_flatten", "topo_scatter", "loops_scan"):
+            for k in ("topo_init", "topo_join", "topo_rank", "topo_unite", "topo_flatten", "topo_scatter", "scan_block"):
                 if (k + "_kernel(") in name and row.get("AverageNs"):
                     out[k] = round(float(row["AverageNs"]) / 1e3, 1)
     return out
@@ -189,7 +189,7 @@ def report(a, res):
                     ks = r["kernels_us"]
                     f.write("%s: kernel trace, average microseconds per launch: %s\n" % (name, ", ".join("%s %.1f" % kv for kv in ks.items())))
                     parts = {"join": ks.get("topo_join"), "rank": ks.get("topo_rank"),
-                             "components": sum(ks.get(k, 0) for k in ("topo_unite", "topo_flatten", "loops_scan", "topo_scatter")) or None}
+                             "components": sum(ks.get(k, 0) for k in ("topo_unite", "topo_flatten", "scan_block", "topo_scatter")) or None}
                     f.write("%s: Mtri/s by phase: %s\n" % (name, ", ".join("%s %.0f" % (k, r["n_tri"] / v) for k, v in parts.items() if v)))
 
 
