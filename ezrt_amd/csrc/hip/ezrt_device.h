@@ -97,6 +97,8 @@ struct DevScene {
   const float4* hdr;   // RGBA texels, row 0 = top
   const uint32_t* hdr_rgbe; // the same map as R | G << 8 | B << 16 | E << 24 when EVERY texel is exactly (m / 256) 2^(E - 128)
                             // per channel -- true by construction for maps HDRLoader decoded (hdrloader.cpp:97-114) -- else NULL
+  const uint2* hdr_pairs;   // hdr_rgbe's rows in pairs (or NULL): (H + 1) x W entries, [j][x] = (texel(max(j - 1, 0), x), texel(min(j, H - 1), x)),
+                            // so the 2x2 footprint of a bilinear lookup is ONE 16-byte load (tex_fetch_rgbe; knob env_pairs; W >= 2)
   const float4* cache; // (x/w, y/h, pdf, 0)
   const float2* cache_xy; // the same cache as two planes (or NULL): (x/w, y/h) for SampleHdr, pdf for hdrPdf -- the two
   const float* cache_pdf; // texels a bilinear lookup takes from a row are then ONE 16- or 8-byte load (tex_fetch_xy / _pdf)
@@ -1543,7 +1545,7 @@ EZD f3 rgbe_texel(uint32_t p) {
   return mk(__builtin_amdgcn_ldexpf((float)(p & 255u), e), __builtin_amdgcn_ldexpf((float)((p >> 8) & 255u), e),
             __builtin_amdgcn_ldexpf((float)((p >> 16) & 255u), e));
 }
-EZD f3 tex_fetch_rgbe(const uint32_t* __restrict__ img, int W, int H, int filter, float u, float v) {
+EZD f3 tex_fetch_rgbe(const uint32_t* __restrict__ img, const uint2* __restrict__ pairs, int W, int H, int filter, float u, float v) {
   u = sane01(u);
   v = sane01(v);
   if (filter == EZRT_FILTER_NEAREST) {
@@ -1567,7 +1569,20 @@ EZD f3 tex_fetch_rgbe(const uint32_t* __restrict__ img, int W, int H, int filter
     uint32_t a, b;
   };
   uint32_t q00, q10, q01, q11;
-  if (W >= 2) {
+  if (pairs) {
+    // The row-pair plane (DevScene::hdr_pairs): entry row j = (int)y0 + 1 holds the texels of rows (iy0, iy1) as clamped above, the
+    // map's top and bottom edges included (j = 0: rows (0, 0); j = H: rows (H - 1, H - 1)), so the footprint's two rows are one
+    // request to one line instead of two to two.  (8-byte aligned: the struct says so.)
+    struct __attribute__((packed, aligned(8))) PairPair {
+      uint32_t a_top, a_bot, b_top, b_bot; // entries bx and bx + 1
+    };
+    const int bx = ix0 < W - 2 ? ix0 : W - 2;
+    const PairPair r = *reinterpret_cast<const PairPair*>(pairs + (size_t)((int)y0 + 1) * W + bx);
+    q00 = ix0 == bx ? r.a_top : r.b_top;
+    q10 = ix1 == bx ? r.a_top : r.b_top;
+    q01 = ix0 == bx ? r.a_bot : r.b_bot;
+    q11 = ix1 == bx ? r.a_bot : r.b_bot;
+  } else if (W >= 2) {
     int bx = ix0 < W - 2 ? ix0 : W - 2;
     const TexelPair r0 = *reinterpret_cast<const TexelPair*>(img + (size_t)iy0 * W + bx);
     const TexelPair r1 = *reinterpret_cast<const TexelPair*>(img + (size_t)iy1 * W + bx);
@@ -1645,7 +1660,7 @@ EZD f3 hdr_color(const DevScene& sc, f3 L, float env_clamp, Counters& ctr) {
   if (!sc.hdr) return mk(0, 0, 0);
   float u, v;
   to_spherical(normalize(L), u, v);
-  f3 c = sc.hdr_rgbe ? tex_fetch_rgbe(sc.hdr_rgbe, sc.env_w, sc.env_h, sc.env_filter, u, v)
+  f3 c = sc.hdr_rgbe ? tex_fetch_rgbe(sc.hdr_rgbe, sc.hdr_pairs, sc.env_w, sc.env_h, sc.env_filter, u, v)
                      : tex_fetch(sc.hdr, sc.env_w, sc.env_h, sc.env_filter, u, v);
   if (env_clamp > 0.0f) c = mk(ez_min(c.x, env_clamp), ez_min(c.y, env_clamp), ez_min(c.z, env_clamp));
   return c;
@@ -1698,7 +1713,7 @@ EZD void hdr_color_pdf(const DevScene& sc, f3 L, float env_clamp, Counters& ctr,
   if (!sc.hdr) {
     color = mk(0, 0, 0);
   } else {
-    f3 c = sc.hdr_rgbe ? tex_fetch_rgbe(sc.hdr_rgbe, sc.env_w, sc.env_h, sc.env_filter, u, v)
+    f3 c = sc.hdr_rgbe ? tex_fetch_rgbe(sc.hdr_rgbe, sc.hdr_pairs, sc.env_w, sc.env_h, sc.env_filter, u, v)
                        : tex_fetch(sc.hdr, sc.env_w, sc.env_h, sc.env_filter, u, v);
     if (env_clamp > 0.0f) c = mk(ez_min(c.x, env_clamp), ez_min(c.y, env_clamp), ez_min(c.z, env_clamp));
     color = c;

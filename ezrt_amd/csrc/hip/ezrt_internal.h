@@ -206,6 +206,7 @@ struct Tuning {
                            // record costs the stream ~5 us: -1.2 % on C2); 0: only the call's begin / end events
   int env_planes = 1;      // the env cache as an (x, y) plane and a pdf plane for bilinear lookups (one load per row)
   int env_rgbe = 1;        // environment lookups through the 4-byte RGBE form of the map when it has an exact one (set_env)
+  int env_pairs = 1;       // ... and its bilinear lookups through the row-pair plane of that form: one 16-byte load per lookup (DevScene::hdr_pairs)
   int min_staged = 16;      // a trace launch gives up workgroups per CU (down to 4) until this many top-of-tree records fit in LDS
   int rel_min_records = 4;  // the primary stage runs at trace_wps_rel waves per SIMD only while that leaves this many top-of-tree records in LDS
                             // (24 until round 4; C2 and C4 -- 16 stack rows, 6 records left at 7 workgroups per CU -- gain 0.6-1.1 % at 7)
@@ -278,6 +279,7 @@ const TuningName kTuning[] = {{"megakernel", &Tuning::megakernel, 0, 1},
                               {"debug_stages", &Tuning::debug_stages, 0, 2},
                               {"env_rgbe", &Tuning::env_rgbe, 0, 1},
                               {"env_planes", &Tuning::env_planes, 0, 1},
+                              {"env_pairs", &Tuning::env_pairs, 0, 1},
                               {"launch_events", &Tuning::launch_events, 0, 1},
                               {"shade_wgs", &Tuning::shade_wgs, 0, 4096},
                               {"chunk_log2", &Tuning::chunk_log2, 12, 28},
@@ -417,6 +419,8 @@ struct EzrtScene {
   DevBuf<float> cache_pdf;
   DevBuf<uint32_t> hdr_rgbe; // RGBE form of hdr (has_rgbe)
   bool has_rgbe = false;
+  DevBuf<uint2> hdr_pairs;   // hdr_rgbe's rows in pairs, (env_h + 1) x env_w entries (has_pairs: has_rgbe and env_w >= 2)
+  bool has_pairs = false;
   uint32_t root_ref = 0;
   int env_w = 0, env_h = 0, env_filter = 0;
   bool has_cache = false;
@@ -465,6 +469,7 @@ struct EzrtScene {
     d.n_tri = n_tri;
     d.hdr = hdr.p;
     d.hdr_rgbe = (has_rgbe && tune.env_rgbe) ? hdr_rgbe.p : nullptr;
+    d.hdr_pairs = (has_pairs && tune.env_rgbe && tune.env_pairs) ? hdr_pairs.p : nullptr;
     d.cache = has_cache ? cache.p : nullptr;
     d.cache_xy = (has_cache && tune.env_planes && env_w >= 2) ? cache_xy.p : nullptr;
     d.cache_pdf = (has_cache && tune.env_planes && env_w >= 2) ? cache_pdf.p : nullptr;

@@ -112,8 +112,9 @@ struct GenWhole {
   uint32_t sh_sub, sh_bw;  // POW2: their base-2 logarithms
   uint32_t scatter, scatter_shift, frame_first;
 };
+// sslot: the sample slot of the queue position (what queue_to_sample returns: [frame of the chunk][sample slot within the frame])
 template <bool POW2>
-EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, uint32_t& frame) {
+EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, uint32_t& frame, uint32_t& sslot) {
   const uint32_t sh = g.scatter_shift;
   const uint32_t q = qslot >> sh;
   uint32_t fk, r2; // frame of the chunk; granule within the frame after the scatter (queue_to_sample)
@@ -141,6 +142,12 @@ EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, 
   x = (int)(bx * 16u + (wave & 1u) * 8u + (lane & 7u));
   y = (int)(by * 16u + (wave >> 1) * 8u + (lane >> 3));
   frame = g.frame_first + fk;
+  sslot = ((POW2 ? fk << g.sh_sub : fk * g.div_sub.d) << sh) + s; // (r2 < granules per frame)
+}
+template <bool POW2>
+EZD void slot_to_pixel_whole(const GenWhole& g, uint32_t qslot, int& x, int& y, uint32_t& frame) {
+  uint32_t sslot;
+  slot_to_pixel_whole<POW2>(g, qslot, x, y, frame, sslot);
 }
 // seed: the RNG state after the two jitter draws (camera_dir_scaled), what the MIS integrators' primary stage starts from
 template <bool POW2>
@@ -148,6 +155,14 @@ EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot, uint32_t& seed) 
   int x, y;
   uint32_t frame;
   slot_to_pixel_whole<POW2>(g, qslot, x, y, frame);
+  const f3 dir = camera_dir_scaled<POW2>(g.sw, g.sh, g.rot, (uint32_t)x, (uint32_t)y, frame, seed);
+  return make_float4(dir.x, dir.y, dir.z, 1.0f);
+}
+// ... and the pixel, the frame and the sample slot the direction was made from: the primary stage's regenerating shading passes
+// (shade_body REGEN) take them from here instead of dividing the queue position again (queue_to_sample, slot_to_pixel)
+template <bool POW2>
+EZD float4 primary_dir_whole(const GenWhole& g, uint32_t qslot, uint32_t& seed, int& x, int& y, uint32_t& frame, uint32_t& sslot) {
+  slot_to_pixel_whole<POW2>(g, qslot, x, y, frame, sslot);
   const f3 dir = camera_dir_scaled<POW2>(g.sw, g.sh, g.rot, (uint32_t)x, (uint32_t)y, frame, seed);
   return make_float4(dir.x, dir.y, dir.z, 1.0f);
 }

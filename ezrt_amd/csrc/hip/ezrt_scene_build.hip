@@ -873,6 +873,7 @@ static int ezrt_scene_set_env_body(EzrtScene* s, const float* hdr, const float* 
   HIP_TRY(hipMemcpy(s->hdr.p, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice));
   // RGBE form: every texel exactly (m / 256) * 2^(E - 128) per channel with one shared E (what HDRLoader produces)
   s->has_rgbe = false;
+  s->has_pairs = false;
   {
     std::vector<uint32_t> packed(n);
     bool ok = true;
@@ -911,6 +912,18 @@ static int ezrt_scene_set_env_body(EzrtScene* s, const float* hdr, const float* 
       HIP_TRY(s->hdr_rgbe.ensure(n));
       HIP_TRY(hipMemcpy(s->hdr_rgbe.p, packed.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
       s->has_rgbe = true;
+      // the same texels as row pairs (DevScene::hdr_pairs): entry [j][x] = (row max(j - 1, 0), row min(j, h - 1)) of column x
+      if (w >= 2) {
+        std::vector<uint2> pairs((size_t)(h + 1) * w);
+        for (int j = 0; j <= h; j++) {
+          const uint32_t* top = packed.data() + (size_t)(j > 0 ? j - 1 : 0) * w;
+          const uint32_t* bot = packed.data() + (size_t)(j < h ? j : h - 1) * w;
+          for (int x = 0; x < w; x++) pairs[(size_t)j * w + x] = make_uint2(top[x], bot[x]);
+        }
+        HIP_TRY(s->hdr_pairs.ensure(pairs.size()));
+        HIP_TRY(hipMemcpy(s->hdr_pairs.p, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        s->has_pairs = true;
+      }
     }
   }
   s->has_cache = false;

@@ -193,7 +193,7 @@ EZD void chunk_prologue(const ChunkPrologue& g, uint32_t tid, uint32_t n_threads
 // LOG: the per-wave diagnostics of debug_stages=2 (a.wave_log).  A template parameter, not a run-time test: the
 // counters and time stamps are loop-carried values, and even never-executed they cost the production kernel registers
 // (one 64-bit time stamp turned 4 spills into 7: -2 %).
-// GEN (with REL): primary rays are generated in the refill block -- seed, AA jitter, camera rotation, normalize:
+// GEN (with REL): primary rays are generated in the refill block, by the lane that adopts the drawn slot -- seed, AA jitter, camera rotation, normalize:
 // primary_dir, the code raygen_kernel runs -- and stored to the queue from here (the stage's shading passes and a redo
 // launch read them there: recomputing the direction in the shading kernels cost them 30 us each on C2, more than the
 // 16-byte read -- with the general generator; the whole-frame power-of-two one is cheap enough: WHOLE == 3 below).  What goes away is raygen_kernel's launch and this kernel's read of the queue: the stores ride on a
@@ -386,6 +386,15 @@ EZD void traceq4_body(const TraceQ4Args& A) {
       if (ref == REF_NONE && nx_slot != REF_NONE) {
         const uint32_t adopted = nx_slot;
         nx_slot = REF_NONE;
+        if constexpr (GEN) {
+          // The draw kept the slot alone: its ray is generated here, by the lane that adopts it (its drawer, or after the hand-over the
+          // taker) -- a pure function of the slot and launch-uniform values, so there is no load to hide by generating at the draw, and
+          // nx_d is not live across the traversal loop (four VGPRs at a budget of 72).  The same instructions in the same wave-wide
+          // block; every drawn slot is adopted exactly once, and before any to_redo of it.
+          if (WHOLE) nx_d = primary_dir_whole<WHOLE >= 2>(A.gen_whole, adopted);
+          else nx_d = primary_dir(A.gen.p, A.gen.blocks, A.gen.div_blocks, A.gen.div_sub, A.gen.scatter, A.gen.scatter_shift, A.gen.frame_first, adopted);
+          if (WHOLE != 3) a.rq.d[adopted] = nx_d; // (for the stage's shading passes and a redo launch; w = 0: a pixel of another shard)
+        }
         if (nx_d.w != 0.0f) {
           n_counted += a.count_rays;
           slot = adopted;
@@ -452,13 +461,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           if (a.slot_map) rs = a.slot_map[idx];
           nx_slot = rs;
           if (!REL) nx_o = a.const_origin == 1u ? make_float4(a.origin[0], a.origin[1], a.origin[2], 0.0f) : a.rq.o[rs >> (a.const_origin >> 1)];
-          if (GEN) { // generate, and leave the direction in the queue for the stage's shading passes (and a redo launch)
-            if (WHOLE) nx_d = primary_dir_whole<WHOLE >= 2>(A.gen_whole, rs);
-            else nx_d = primary_dir(A.gen.p, A.gen.blocks, A.gen.div_blocks, A.gen.div_sub, A.gen.scatter, A.gen.scatter_shift, A.gen.frame_first, rs);
-            if (WHOLE != 3) a.rq.d[rs] = nx_d;
-          } else {
-            nx_d = a.rq.d[rs];
-          }
+          if constexpr (!GEN) nx_d = a.rq.d[rs]; // (GEN: nothing to fetch -- the lane that adopts the slot generates its ray)
         }
       }
     }
@@ -486,7 +489,8 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           __builtin_amdgcn_wave_barrier();
           const int src = taker ? wsrc[ir0] : lane;
           const uint32_t hs = (uint32_t)__shfl((int)nx_slot, src, 64);
-          const float hdx = __shfl(nx_d.x, src, 64), hdy = __shfl(nx_d.y, src, 64), hdz = __shfl(nx_d.z, src, 64), hdw = __shfl(nx_d.w, src, 64);
+          float hdx = 0.0f, hdy = 0.0f, hdz = 0.0f, hdw = 0.0f;
+          if constexpr (!GEN) hdx = __shfl(nx_d.x, src, 64), hdy = __shfl(nx_d.y, src, 64), hdz = __shfl(nx_d.z, src, 64), hdw = __shfl(nx_d.w, src, 64);
           float hox = 0.0f, hoy = 0.0f, hoz = 0.0f, how = 0.0f;
           if (!REL) hox = __shfl(nx_o.x, src, 64), hoy = __shfl(nx_o.y, src, 64), hoz = __shfl(nx_o.z, src, 64);
           if (OCC) how = __shfl(nx_o.w, src, 64); // (t_max)
@@ -494,7 +498,7 @@ EZD void traceq4_body(const TraceQ4Args& A) {
           if (giver) nx_slot = REF_NONE;
           if (taker) { // (adopted by the next refill, like a ray this lane had prefetched itself)
             nx_slot = hs;
-            nx_d = make_float4(hdx, hdy, hdz, hdw);
+            if constexpr (!GEN) nx_d = make_float4(hdx, hdy, hdz, hdw);
             if (!REL) nx_o = make_float4(hox, hoy, hoz, how);
           }
         }

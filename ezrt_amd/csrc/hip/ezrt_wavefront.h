@@ -198,6 +198,8 @@ struct ShadeOut {
 struct ShadeIn { // what stage b reads for one path (from the queues)
   float4 rd4, ro4, s0, s1, s2, s3, s4;
   int2 h, sh;
+  int gen_x, gen_y;               // REGEN, second pass: the pixel, the frame and the sample slot the generator made the direction from
+  uint32_t gen_frame, gen_sslot;  // (primary_dir_whole), where shade_body would divide the queue position again
 };
 // entry (PASS 2 of the split kernels, or NULL): the list entry shade_miss_kernel wrote for this path
 // REGEN (the primary stage of a whole power-of-two frame: knob regen_dir): the queue holds no directions -- the trace launch that
@@ -256,7 +258,7 @@ EZD void shade_load(const WfArgs& a, const uint32_t i, const bool live, ShadeIn&
   }
   if constexpr (REGEN && PASS == 2) { // the RNG state after the generator's two draws goes where the general state keeps a path's seed
     uint32_t seed;
-    rd4 = primary_dir_whole<true>(a.gen_whole, rslot, seed);
+    rd4 = primary_dir_whole<true>(a.gen_whole, rslot, seed, in.gen_x, in.gen_y, in.gen_frame, in.gen_sslot);
     s3.w = __uint_as_float(seed);
   }
   // Pin the loads here: left alone, the compiler sinks every one of them into the branch that first uses
@@ -322,7 +324,17 @@ EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn&
   f3 colour = mk(0, 0, 0);
   f3 rd = mk(rd4.x, rd4.y, rd4.z);
   if (B0) {
-    sslot = queue_to_sample(i, a.div_sub, a.scatter, a.scatter_shift);
+    if constexpr (REGEN) { // the generator's shifts, not queue_to_sample's two divisions: the same slot
+      if (PASS == 2) {
+        sslot = in.gen_sslot;
+      } else { // (the first pass generates inside the branch of a ray that left the scene, below: the compiler shares the shifts)
+        int gx, gy;
+        uint32_t gf;
+        slot_to_pixel_whole<true>(a.gen_whole, i, gx, gy, gf, sslot);
+      }
+    } else {
+      sslot = queue_to_sample(i, a.div_sub, a.scatter, a.scatter_shift);
+    }
     if (rd4.w == 0.0f) {
       live = false; // pixel not owned by this shard
     } else {
@@ -449,7 +461,8 @@ EZD bool shade_body(const WfArgs& a, const uint32_t i, bool live, const ShadeIn&
     // ---- start bounce b (loop body of pathTracing*, P5/fsh:767-804 / 815-887)
     int x, y;
     uint32_t frame;
-    slot_to_pixel(a.blocks, a.div_blocks, sslot, a.frame_first, x, y, frame);
+    if constexpr (REGEN && PASS == 2) x = in.gen_x, y = in.gen_y, frame = in.gen_frame; // (no division, no blocks[] load)
+    else slot_to_pixel(a.blocks, a.div_blocks, sslot, a.frame_first, x, y, frame);
     const f3 V = -hit.viewDir, N = hit.N;
     constexpr bool ANISO_IS = integ_aniso_is<INTEG>();
     f3 X = mk(0, 0, 0), Y = mk(0, 0, 0);

@@ -39,7 +39,7 @@
  *   is the same whichever outputs are requested.
  * ezrt_env_sample_device: L[3 i .. 3 i + 2] = SampleHdr(xi[2 i], xi[2 i + 1]), a direction drawn from the environment's importance
  *   cache.
- *   Both read the environment in whichever device layout the scene's options selected (env_rgbe, env_planes, the filter of
+ *   Both read the environment in whichever device layout the scene's options selected (env_rgbe, env_pairs, env_planes, the filter of
  *   ezrt_scene_set_env).
  *
  * Memory, streams, ordering and errors are those of ezrt_query.h: every non-NULL pointer is device memory of the scene's device,

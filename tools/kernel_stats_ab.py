@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/kernel_stats_ab.py PARENT_DIR LABEL=DIR [LABEL=DIR ...]: per-kernel comparison of rocprofv3 --kernel-trace --stats runs, the
-layout of profiles/r30/lean_kernel_stats.txt.  Every DIR holds one run's *kernel_stats.csv (searched recursively).  Per kernel:
+layout of profiles/r30/lean_kernel_stats.txt.  Every DIR holds one run's *kernel_stats.csv (searched recursively), or those of several
+runs of one library, which are pooled.  Per kernel:
 launches, the parent's average (standard deviation) over the launches in microseconds, the other run's, the difference, the margin
 3 x (parent's StdDev) / sqrt(launches), the verdict.  Kernels below --min-share (default 0.002) of the parent run's kernel time are
 left out.
@@ -15,10 +16,18 @@ def load(d):
     f = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
     if not f:
         sys.exit("no *kernel_stats.csv under " + d)
+    # several runs under one DIR are pooled: launches and totals add up, the deviation is that of all launches about their common mean
+    runs = {}
+    for path in sorted(f):
+        for r in csv.DictReader(open(path)):
+            name = re.sub(r"^void ", "", r["Name"]).replace("ezd::", "")
+            runs.setdefault(name, []).append((int(r["Calls"]), float(r["AverageNs"]) / 1e3, float(r["StdDev"]) / 1e3, float(r["TotalDurationNs"]) / 1e3))
     out = {}
-    for r in csv.DictReader(open(sorted(f)[0])):
-        name = re.sub(r"^void ", "", r["Name"]).replace("ezd::", "")
-        out[name] = (int(r["Calls"]), float(r["AverageNs"]) / 1e3, float(r["StdDev"]) / 1e3, float(r["TotalDurationNs"]) / 1e3)
+    for name, rs in runs.items():
+        n = sum(r[0] for r in rs)
+        mean = sum(r[0] * r[1] for r in rs) / n
+        ss = sum((r[0] - 1) * r[2] ** 2 + r[0] * (r[1] - mean) ** 2 for r in rs)
+        out[name] = (n, mean, math.sqrt(ss / (n - 1)) if n > 1 else 0.0, sum(r[3] for r in rs))
     return out
 
 
@@ -47,7 +56,7 @@ def main():
         other = load(d)
         print("## " + label)
         for name, (calls, avg, sd, total) in sorted(other.items(), key=lambda kv: -kv[1][3]):
-            pname = replaced(name)
+            pname = name if name in parent else replaced(name)  # (a parent from round 31 on has the regenerating instances itself)
             if pname not in parent or parent[pname][3] < min_share * run_total:
                 continue
             pc, pavg, psd, _ = parent[pname]
