@@ -75,7 +75,7 @@ negctl:
 OL_VARIANTS = i16_t4096 i64_t4096 i0_t2048 i0_t8192 nosort
 # The measurement variants of the mesh processing recompile ezrt_mesh.hip instead: the one unit a variant compiles again is
 # VARIANT_UNIT_<name>, ezrt_queries where none is named.
-MESH_VARIANTS = orient_lane_atomics clip_per_lane subdiv_per_lane subdiv_no_vertex decimate_per_lane
+MESH_VARIANTS = orient_lane_atomics clip_per_lane subdiv_per_lane subdiv_no_vertex decimate_per_lane iso_per_lane
 $(foreach v,$(MESH_VARIANTS),$(eval VARIANT_UNIT_$(v) = ezrt_mesh))
 # (the mesh orientation, ezrt_orient_kernels.h: one atomic per lane in the volume launch; EZRT_HIP_LIB selects it for a run of
 # tools/orient_rates.py)
@@ -91,6 +91,9 @@ OL_FLAGS_subdiv_no_vertex = -DEZRT_SUBDIV_SKIP_VERTEX=1
 # (and that of the decimation, ezrt_decimate_kernels.h: the fill with every lane writing its own row, whatever the alignment;
 # EZRT_HIP_LIB selects it for a run of tools/decimate_rates.py)
 OL_FLAGS_decimate_per_lane = -DEZRT_DECIMATE_PER_LANE=1
+# (and that of the isosurface extraction, ezrt_iso_kernels.h: the fill with every lane writing its own rows, whatever the alignment;
+# EZRT_HIP_LIB selects it for a run of tools/iso_rates.py)
+OL_FLAGS_iso_per_lane = -DEZRT_ISO_PER_LANE=1
 OL_FLAGS_i16_t4096 = -DEZRT_OL_INSERT_MAX=16
 OL_FLAGS_i64_t4096 = -DEZRT_OL_INSERT_MAX=64
 OL_FLAGS_i0_t2048 = -DEZRT_OL_TILE_MAX=2048

@@ -412,6 +412,23 @@ DECIMATE_ABI = {
 DECIMATE_DEDUP = 1
 
 
+# stream-ordered isosurface extraction on device memory, libezrt_hip.so only (include/ezrt_isosurface.h); pointers are device addresses
+ISO_ABI = {
+    # s, values, nx, ny, nz, grid8, offsets, summary, work, work_bytes, stream
+    "ezrt_iso_count_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    # s, values, nx, ny, nz, grid8, material18, offsets, capacity, out, cell (or None), stream
+    "ezrt_iso_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
+}
+# the header's third entry point, in a table of its own: the *_work_bytes of the *_ABI tables are functions of a row count, which
+# tests/test_mesh_work_bytes.py holds to their formulas over one list of counts; this one takes the grid's three dimensions
+# (tests/test_iso_abi.py holds it to its formula)
+ISO_SIZES = {
+    # nx, ny, nz: the bytes of `work` (no device work)
+    "ezrt_iso_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+}
+ISO_BLOCK = 256  # EZRT_ISO_BLOCK: cells per entry of offsets
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -510,7 +527,7 @@ def load_hip():
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
                       OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, BOUNDARY_ABI,
-                      CLIP_ABI, SUBDIVIDE_ABI, DECIMATE_ABI, OVERLAP_LIST_ABI,
+                      CLIP_ABI, SUBDIVIDE_ABI, DECIMATE_ABI, ISO_ABI, ISO_SIZES, OVERLAP_LIST_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

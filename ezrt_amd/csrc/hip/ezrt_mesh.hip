@@ -2,7 +2,8 @@
 // `work` buffer the caller brings.  Mesh topology (include/ezrt_topology.h, kernels in ezrt_topology_kernels.h), vertex weld and smooth
 // normals (ezrt_vertices.h, ezrt_vertex_kernels.h), mesh orientation and rewind (ezrt_orient.h, ezrt_orient_kernels.h), boundary loops
 // and caps (ezrt_boundary.h, ezrt_boundary_kernels.h), plane clipping (ezrt_clip.h, ezrt_clip_kernels.h), subdivision
-// (ezrt_subdivide.h, ezrt_subdiv_kernels.h) and decimation (ezrt_decimate.h, ezrt_decimate_kernels.h).  What the families share is
+// (ezrt_subdivide.h, ezrt_subdiv_kernels.h), decimation (ezrt_decimate.h, ezrt_decimate_kernels.h) and isosurface extraction
+// (ezrt_isosurface.h, ezrt_iso_kernels.h).  What the families share is
 // stated once: the prefix sums are scan_small and scan_tiled (ezrt_scan_kernels.h); a `work` buffer is described by ONE layout function
 // over a WorkCarver (ezrt_work_carver.h), which ezrt_*_work_bytes runs over a null pointer and the call over the caller's; the argument
 // checks and the grids are the helpers below.  A translation unit of its own, as ezrt_queries.hip is: none of its kernels is compiled
@@ -15,6 +16,7 @@
 #include "ezrt_clip.h"
 #include "ezrt_subdivide.h"
 #include "ezrt_decimate.h"
+#include "ezrt_isosurface.h"
 #include "ezrt_work_carver.h"
 #define EZRT_SCAN_TILED 1 // this unit launches the tiled prefix sum too
 #include "ezrt_scan_kernels.h"
@@ -25,6 +27,7 @@
 #include "ezrt_clip_kernels.h"
 #include "ezrt_subdiv_kernels.h"
 #include "ezrt_decimate_kernels.h"
+#include "ezrt_iso_kernels.h"
 
 using ezi::WorkCarver;
 
@@ -585,6 +588,84 @@ int ezrt_decimate_rows_device(EzrtScene* s, const float* tri36, int n_rows, cons
       const dim3 g = mesh_blocks(N, DC_BLOCK), b(DC_BLOCK);
       if (fill_staged(EZRT_DECIMATE_PER_LANE, tri36, out)) hipLaunchKernelGGL(dec_fill_kernel<true>, g, b, 0, st, a);
       else hipLaunchKernelGGL(dec_fill_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+
+// ---- isosurface extraction on device memory (include/ezrt_isosurface.h).  Count: a memset of the summary, iso_count_kernel with a
+// workgroup per block of 256 cells, and the tiled prefix sum (scan_tiled) of offsets in place over the caller's `work`, the tiles'
+// sums and their total.  Fill: one launch with a workgroup per block, the staged instance where out is 16-byte aligned, else the
+// per-lane one (always, in the measurement variant EZRT_ISO_PER_LANE).  Checked, launched and ordered against a refit by query_call;
+// the scene's records are not read.
+#ifndef EZRT_ISO_PER_LANE
+#define EZRT_ISO_PER_LANE 0
+#endif
+// the cells of a grid whose dimensions are >= 1 and whose vertices are at most INT32_MAX
+static uint64_t iso_cells(int nx, int ny, int nz) { return (uint64_t)(nx - 1) * (uint64_t)(ny - 1) * (uint64_t)(nz - 1); }
+static uint64_t iso_blocks(uint64_t n_cells) { return (n_cells + ISO_BLOCK - 1) / ISO_BLOCK; }
+// what both calls reject in the dimensions
+static int iso_dims_check(int nx, int ny, int nz) {
+  if (nx < 1 || ny < 1 || nz < 1) return fail(EZRT_ERR_INVALID, "a dimension < 1");
+  if ((uint64_t)nx * (uint64_t)ny * (uint64_t)nz > (uint64_t)INT32_MAX) return fail(EZRT_ERR_INVALID, "nx ny nz exceeds INT32_MAX");
+  return 0;
+}
+static size_t iso_layout(void* work, uint64_t n_blocks, long long*& tiles) {
+  WorkCarver w(work);
+  tiles = w.take<long long>(scan_tile_count(n_blocks) + 1);
+  return w.bytes();
+}
+size_t ezrt_iso_work_bytes(int nx, int ny, int nz) {
+  long long* tiles;
+  if (nx < 2 || ny < 2 || nz < 2) return 8;
+  // (a grid the calls reject for its size counts as the largest they take: the function stays monotone and never wraps)
+  const unsigned __int128 cells = (unsigned __int128)iso_cells(nx, ny, 2) * (unsigned __int128)(nz - 1);
+  return iso_layout(nullptr, iso_blocks(cells > (unsigned __int128)INT32_MAX ? (uint64_t)INT32_MAX : (uint64_t)cells), tiles);
+}
+int ezrt_iso_count_device(EzrtScene* s, const float* values, int nx, int ny, int nz, const float* grid8, int64_t* offsets, int64_t* summary,
+                          void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_iso_count_device", [&]() -> int {
+    if (!s || !values || !grid8 || !offsets || !summary || !work) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (int rc = iso_dims_check(nx, ny, nz)) return rc;
+    if (int rc = work_check(work, work_bytes, ezrt_iso_work_bytes(nx, ny, nz), "ezrt_iso_work_bytes(nx, ny, nz)")) return rc;
+    const uint64_t n_cells = iso_cells(nx, ny, nz), B = iso_blocks(n_cells);
+    if (n_cells == 0) return 0;
+    const size_t n_values = (size_t)nx * (size_t)ny * (size_t)nz, i8 = sizeof(int64_t);
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{values, n_values * sizeof(float)}, {grid8, 8 * sizeof(float)}, {offsets, (B + 1) * i8}, {summary, 8 * i8},
+                          {work, ezrt_iso_work_bytes(nx, ny, nz)}},
+                      n_cells, st, [&](dim3, dim3) -> int {
+      long long *x = (long long*)offsets, *tiles;
+      iso_layout(work, B, tiles);
+      HIP_TRY(hipMemsetAsync(summary, 0, 8 * i8, st));
+      hipLaunchKernelGGL(iso_count_kernel, dim3((unsigned)B), dim3(ISO_BLOCK), 0, st, values, nx, ny, (uint32_t)n_cells, grid8, x,
+                         (unsigned long long*)summary);
+      scan_tiled(st, x, tiles, scan_tile_count(B), nullptr, (long long)B); // the blocks' counts, in place; the total lands in offsets[n_blocks]
+      return 0;
+    });
+  });
+}
+int ezrt_iso_rows_device(EzrtScene* s, const float* values, int nx, int ny, int nz, const float* grid8, const float* material18,
+                         const int64_t* offsets, int64_t capacity, float* out, int32_t* cell, void* stream) {
+  return ezi::guarded("ezrt_iso_rows_device", [&]() -> int {
+    if (!s || !values || !grid8 || !material18 || !offsets) return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (int rc = iso_dims_check(nx, ny, nz)) return rc;
+    if (int rc = capacity_check(capacity, out)) return rc;
+    const uint64_t n_cells = iso_cells(nx, ny, nz), B = iso_blocks(n_cells);
+    if (n_cells == 0) return 0;
+    const size_t n_values = (size_t)nx * (size_t)ny * (size_t)nz, cap = (size_t)capacity;
+    const uintptr_t v0 = (uintptr_t)values, v1 = v0 + n_values * sizeof(float), o0 = (uintptr_t)out, o1 = o0 + cap * ROW_BYTES;
+    if (out && cap > 0 && v0 < o1 && o0 < v1) return fail(EZRT_ERR_INVALID, "out overlaps values");
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{values, n_values * sizeof(float)}, {grid8, 8 * sizeof(float)}, {material18, 18 * sizeof(float)},
+                          {offsets, (B + 1) * sizeof(int64_t)}, {cap ? out : nullptr, cap * ROW_BYTES}, {cap ? cell : nullptr, cap * sizeof(int32_t)}},
+                      n_cells, st, [&](dim3, dim3) {
+      if (cap == 0) return; // nothing fits: nothing is written
+      IsoFillArgs a{};
+      a.values = values, a.nx = (int32_t)nx, a.ny = (int32_t)ny, a.n_cells = (uint32_t)n_cells, a.grid8 = grid8, a.material18 = material18;
+      a.offsets = (const long long*)offsets, a.capacity = (long long)capacity, a.out = out, a.cell = cell;
+      const dim3 g((unsigned)B), b(ISO_BLOCK);
+      if (fill_staged(EZRT_ISO_PER_LANE, out, out)) hipLaunchKernelGGL(iso_fill_kernel<true>, g, b, 0, st, a);
+      else hipLaunchKernelGGL(iso_fill_kernel<false>, g, b, 0, st, a);
     });
   });
 }

@@ -108,6 +108,7 @@ MeshBoundary = collections.namedtuple("MeshBoundary", "next loop pos order loop_
 ClipRows = collections.namedtuple("ClipRows", "rows src cut_edge summary n_rows")
 SubdivRows = collections.namedtuple("SubdivRows", "rows summary n_rows")
 DecimatedRows = collections.namedtuple("DecimatedRows", "rows src cell cell_point summary n_rows")
+IsoRows = collections.namedtuple("IsoRows", "rows cell summary shape")
 
 
 def _scene_lib(scene, abi):
@@ -1805,6 +1806,111 @@ def decimate_rows(scene, tri36, cell_size, origin=(0, 0, 0), dedup=True, src=Tru
         _call(scene, lib.ezrt_decimate_rows_device(scene._h, ptr(tri36), n, ptr(cell), ptr(point), ptr(offsets), T, ptr(rows), ptr(srcs), P(h)))
     _keep((rows, srcs), ts, tri36)
     return DecimatedRows(rows, srcs, cell, point[:n_cells], summary, n)
+
+
+def _grid_numbers(origin, spacing):
+    """(origin, spacing) as three floats each; spacing may be one number"""
+    o = [float(x) for x in origin]
+    if len(o) != 3:
+        raise ValueError("origin must have three entries, not %d" % len(o))
+    try:
+        h = [float(x) for x in spacing]
+    except TypeError:
+        h = [float(spacing)] * 3
+    if len(h) != 3:
+        raise ValueError("spacing must be a number or have three entries, not %d" % len(h))
+    return o, h
+
+
+def _grid_shape(shape):
+    d = tuple(int(x) for x in shape)
+    if len(d) != 3 or min(d) < 1:
+        raise ValueError("shape must be (nz, ny, nx) with every dimension >= 1, not %s" % (tuple(shape),))
+    if d[0] * d[1] * d[2] > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 grid vertices per call")
+    return d
+
+
+def grid_points(shape, origin=(0, 0, 0), spacing=1.0, device=None):
+    """float32 [nz ny nx, 3]: the positions of the vertices of the regular grid of `shape` = (nz, ny, nx), x fastest -- row
+    (k ny + j) nx + i is (ox + i hx, oy + j hy, oz + k hz), every coordinate computed in float64 from the float32 values of `origin`
+    (three numbers) and `spacing` (a number or three) with one multiply and one add, then rounded to float32: exactly the positions
+    isosurface_rows gives the vertices of a grid with the same origin and spacing (G2 of include/ezrt_isosurface.h).  A field sampled
+    at these points and reshaped to `shape` is what isosurface_rows takes; the offset surface of a scene at distance r is
+        pts = query.grid_points(shape, origin, spacing, device)
+        sd = query.signed_distance(scene, pts)
+        off = query.isosurface_rows(scene, sd.dist.reshape(shape), r, origin, spacing)
+    On torch's current stream of `device`."""
+    nz, ny, nx = _grid_shape(shape)
+    o, h = _grid_numbers(origin, spacing)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    g = torch.tensor(o + h, dtype=torch.float64).to(torch.float32).to(torch.float64).to(dev)
+    axis = lambda n, a: (torch.arange(n, dtype=torch.float64, device=dev) * g[3 + a] + g[a]).to(torch.float32)
+    x, y, z = axis(nx, 0), axis(ny, 1), axis(nz, 2)
+    out = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=dev)
+    out[..., 0], out[..., 1], out[..., 2] = x[None, None, :], y[None, :, None], z[:, None, None]
+    return out.reshape(-1, 3)
+
+
+def isosurface_rows(scene, values, iso, origin=(0, 0, 0), spacing=1.0, material=None, cell=True, stream=None):
+    """IsoRows(rows float32 [T, 36], cell int32 [T] or None, summary int64 [8], shape (nz, ny, nx)): the surface on which the field
+    `values` (a contiguous float32 [nz, ny, nx] GPU tensor, x fastest, sampled at grid_points(shape, origin, spacing)) crosses the
+    level `iso`, as triangle rows -- the rows a scene is made of: p1 p2 p3, the face normal at all three corners, and `material`
+    (None: 18 zeros, or 18 numbers) in floats 18-35.  A vertex with a value below `iso` is inside, as with signed_distance, and the
+    normals face the outside.  The method is marching tetrahedra on the Kuhn split of every cell: away from the border of the grid
+    and from non-finite values the rows are a closed, consistently wound 2-manifold by value (mesh_topology of a scene of them says
+    closed and oriented); where the surface meets the border it is open -- pad the field with one layer of values >= iso to close it.
+    rows are in ascending cell, and with cell=True cell[r] is the cell (k (ny - 1) + j) (nx - 1) + i of row r.  summary is [T, cells
+    that emit, finite cells that emit nothing, cells with a non-finite value (a hole), blocks of 256 cells that emit, n_cells, grid
+    live, 0].  A non-finite iso, origin or spacing, or a spacing that is not above zero, emits nothing.  A grid with a dimension of 1
+    has no cells: the library launches nothing and writes no summary then, so this wrapper fills in `grid live` itself, by G1's rule
+    restated on the float32 values (the one place outside the library that states it).  Smooth normals: a scene of
+    the rows, mesh_weld, vertex_normals.  With values = signed_distance(scene, grid_points(shape, origin, spacing, dev)).dist
+    .reshape(shape) and iso = r this is the offset surface of the scene at distance r; with winding_number at iso 0.5 (negated: inside
+    is below) a watertight remesh; with torch.minimum / maximum of two fields the union / intersection of two parts.  `scene`
+    supplies the library and the device only.  Synchronises the stream once, to read T; rows and cell are allocated to exactly T
+    rows.  MEMORY besides the result: 8 B per 256 cells of offsets and the library's scratch, ezrt_iso_work_bytes(nx, ny, nz) -- 8 B
+    per 2048 * 256 cells -- freed to torch's allocator when the stream is done with them.  The definition:
+    include/ezrt_isosurface.h."""
+    if not isinstance(cell, bool):
+        raise ValueError("cell must be a bool")
+    lib = _scene_lib(scene, {**_abi.ISO_ABI, **_abi.ISO_SIZES})
+    _tensor("values", values, torch.float32)
+    if values.dim() != 3:
+        raise ValueError("values must have shape [nz, ny, nx], not %s" % (tuple(values.shape),))
+    nz, ny, nx = _grid_shape(values.shape)
+    o, hh = _grid_numbers(origin, spacing)
+    mat = [0.0] * 18 if material is None else [float(x) for x in material]
+    if len(mat) != 18:
+        raise ValueError("material must have 18 entries, not %d" % len(mat))
+    dev = values.device
+    h, ts = _stream(values, stream)
+    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    n_cells = (nx - 1) * (ny - 1) * (nz - 1)
+    n_blocks = (n_cells + _abi.ISO_BLOCK - 1) // _abi.ISO_BLOCK
+    work_bytes = int(lib.ezrt_iso_work_bytes(nx, ny, nz))
+    grid_host = torch.tensor(o + hh + [float(iso), 0.0], dtype=torch.float64).to(torch.float32)
+    with torch.cuda.stream(own):
+        grid = grid_host.to(dev)
+        mat18 = torch.tensor(mat, dtype=torch.float64).to(torch.float32).to(dev)
+        offsets = torch.zeros((n_blocks + 1,), dtype=torch.int64, device=dev)
+        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
+        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+        if n_cells == 0:                                             # the C call writes nothing then: G1's LIVE, restated (see the docstring)
+            summary[6] = int(bool(torch.isfinite(grid_host[:7]).all()) and bool((grid_host[3:6] > 0).all()))
+    P = C.c_void_p
+    ptr = lambda x: P(x.data_ptr()) if x is not None else None
+    if n_cells > 0:
+        _call(scene, lib.ezrt_iso_count_device(scene._h, ptr(values), nx, ny, nz, ptr(grid), ptr(offsets), ptr(summary), ptr(work), work_bytes, P(h)))
+    _keep((values, grid, mat18, offsets, summary, work), ts, values)
+    with torch.cuda.stream(own):
+        T = int(offsets[n_blocks].item())                            # the one synchronisation, of the query's stream
+        rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
+        cells = torch.empty((T,), dtype=torch.int32, device=dev) if cell else None
+    if n_cells > 0 and T > 0:
+        _call(scene, lib.ezrt_iso_rows_device(scene._h, ptr(values), nx, ny, nz, ptr(grid), ptr(mat18), ptr(offsets), T, ptr(rows), ptr(cells), P(h)))
+    _keep((rows, cells), ts, values)
+    return IsoRows(rows, cells, summary, (nz, ny, nx))
 
 
 def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
