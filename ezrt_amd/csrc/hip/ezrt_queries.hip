@@ -116,6 +116,37 @@ static int overlap_list_call(const char* name, EzrtScene* s, bool inputs, ezi::D
   });
 }
 
+// ---- the lowest max_k overlapping triangles per query, on device memory (include/ezrt_box_overlap.h, ezrt_obb_overlap.h,
+// ezrt_tri_overlap.h, ezrt_self_overlap.h, ezrt_segment.h): the call that the five max_k entry points share, overlap_list_call's
+// sibling with the same in0, in1, set, walk, sweep and lds_div.  `max` is the query's EZRT_*_OVERLAP_MAX.  One routed kernel on `st`,
+// no scratch (a query's list is kept in its own output row); checked, launched and ordered against a refit by query_call.
+template <class Args, class Set>
+static int overlap_rows_call(const char* name, EzrtScene* s, bool inputs, ezi::DeviceBuf in0, ezi::DeviceBuf in1, int n, int max_k, int max,
+                             int32_t* tri_id, int32_t* n_overlap, void* stream, void (*walk)(Args), void (*sweep)(Args), size_t lds_div,
+                             Set set) {
+  return ezi::guarded(name, [&]() -> int {
+    if (!s || !inputs || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
+    if (max_k < 0 || max_k > max) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", max);
+    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
+    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
+    if (n == 0) return 0;
+    const size_t N = (size_t)n, K = (size_t)max_k;
+    if (max_k == 0) tri_id = nullptr; // ignored
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {in0, in1, {tri_id, N * K * sizeof(int32_t)}, {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
+      Args a;
+      const PointRoute r = point_scene(s, a.sc);
+      a.n = (uint32_t)n;
+      a.K = max_k;
+      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
+      a.tri = tri_id;
+      a.n_overlap = n_overlap;
+      set(a);
+      launch_routed(walk, sweep, r, r.lds / lds_div, N, st, a);
+    });
+  });
+}
+
 extern "C" {
 // ---- shading queries on device memory (include/ezrt_shade.h)
 int ezrt_query_material_device(EzrtScene* s, const int32_t* tri_id, int n, float* mat18, void* stream) {
@@ -411,30 +442,11 @@ int ezrt_query_signed_distance_device(EzrtScene* s, const float* points3, const 
 // its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
 int ezrt_query_box_overlap_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, int n, int max_k, int32_t* tri_id,
                                   int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_box_overlap_device", [&]() -> int {
-    if (!s || !box_lo3 || !box_hi3 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 0 || max_k > EZRT_BOX_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_BOX_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{box_lo3, N * 3 * sizeof(float)}, {box_hi3, N * 3 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      BoxOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.lo = box_lo3;
-      a.hi = box_hi3;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      // this walk's entries are bare references, one row each: half of the column that decides the route
-      launch_routed(box_overlap_kernel<true>, box_overlap_kernel<false>, r, r.lds / 2, N, st, a);
-    });
-  });
+  const size_t b3 = (size_t)n * 3 * sizeof(float);
+  // this walk's entries are bare references, one row each: half of the column that decides the route
+  return overlap_rows_call<BoxOverlapArgs>("ezrt_query_box_overlap_device", s, box_lo3 && box_hi3, {box_lo3, b3}, {box_hi3, b3}, n, max_k,
+                                           EZRT_BOX_OVERLAP_MAX, tri_id, n_overlap, stream, box_overlap_kernel<true>, box_overlap_kernel<false>, 2,
+                                           [&](BoxOverlapArgs& a) { a.lo = box_lo3, a.hi = box_hi3; });
 }
 int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* box_hi3, const int32_t* tri_id, int n, uint8_t* overlaps,
                                void* stream) {
@@ -454,30 +466,11 @@ int ezrt_box_overlap_at_device(EzrtScene* s, const float* box_lo3, const float* 
 // its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by point_scene.
 int ezrt_query_obb_overlap_device(EzrtScene* s, const float* centre3, const float* axes9, int n, int max_k, int32_t* tri_id,
                                   int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_obb_overlap_device", [&]() -> int {
-    if (!s || !centre3 || !axes9 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 0 || max_k > EZRT_OBB_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_OBB_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{centre3, N * 3 * sizeof(float)}, {axes9, N * 9 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      ObbOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.centre = centre3;
-      a.axes = axes9;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      // slot_walk's entries are bare references, one row each: half of the column that decides the route (stack_need_cp + 1 rows)
-      launch_routed(obb_overlap_kernel<true>, obb_overlap_kernel<false>, r, r.lds / 2, N, st, a);
-    });
-  });
+  const size_t b3 = (size_t)n * 3 * sizeof(float);
+  // slot_walk's entries are bare references, one row each: half of the column that decides the route (stack_need_cp + 1 rows)
+  return overlap_rows_call<ObbOverlapArgs>("ezrt_query_obb_overlap_device", s, centre3 && axes9, {centre3, b3}, {axes9, 3 * b3}, n, max_k,
+                                           EZRT_OBB_OVERLAP_MAX, tri_id, n_overlap, stream, obb_overlap_kernel<true>, obb_overlap_kernel<false>, 2,
+                                           [&](ObbOverlapArgs& a) { a.centre = centre3, a.axes = axes9; });
 }
 int ezrt_obb_overlap_at_device(EzrtScene* s, const float* centre3, const float* axes9, const int32_t* tri_id, int n, uint8_t* overlaps,
                                void* stream) {
@@ -727,29 +720,10 @@ int ezrt_plane_loops_device(EzrtScene* s, const int64_t* offsets, int n, const f
 // kept in its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by
 // point_scene.
 int ezrt_query_tri_overlap_device(EzrtScene* s, const float* tris9, int n, int max_k, int32_t* tri_id, int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_tri_overlap_device", [&]() -> int {
-    if (!s || !tris9 || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 0 || max_k > EZRT_TRI_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_TRI_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{tris9, N * 9 * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)}, {n_overlap, N * sizeof(int32_t)}}, N, st,
-                      [&](dim3, dim3) {
-      TriOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.tris = tris9;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      // this walk's entries are bare references, one row each: half of the column that decides the route
-      launch_routed(tri_overlap_kernel<true>, tri_overlap_kernel<false>, r, r.lds / 2, N, st, a);
-    });
-  });
+  // this walk's entries are bare references, one row each: half of the column that decides the route
+  return overlap_rows_call<TriOverlapArgs>("ezrt_query_tri_overlap_device", s, tris9 != nullptr, {tris9, (size_t)n * 9 * sizeof(float)}, {nullptr, 0},
+                                           n, max_k, EZRT_TRI_OVERLAP_MAX, tri_id, n_overlap, stream, tri_overlap_kernel<true>,
+                                           tri_overlap_kernel<false>, 2, [&](TriOverlapArgs& a) { a.tris = tris9; });
 }
 int ezrt_tri_overlap_at_device(EzrtScene* s, const float* tris9, const int32_t* tri_id, int n, uint8_t* overlaps, void* stream) {
   return ezi::guarded("ezrt_tri_overlap_at_device", [&]() -> int {
@@ -767,30 +741,13 @@ int ezrt_tri_overlap_at_device(EzrtScene* s, const float* tris9, const int32_t* 
 // kept in its own output row); checked, launched and ordered against a refit by query_call.  The route is chosen per call, by
 // point_scene.
 int ezrt_query_self_overlap_device(EzrtScene* s, const int32_t* ids, int n, int max_k, int32_t* tri_id, int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_self_overlap_device", [&]() -> int {
-    if (!s || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (!ids && (size_t)n > (size_t)s->n_tri) return fail(EZRT_ERR_INVALID, "n exceeds the scene's %d triangles (ids is NULL)", (int)s->n_tri);
-    if (max_k < 0 || max_k > EZRT_SELF_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_SELF_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{ids, N * sizeof(int32_t)}, {tri_id, N * K * sizeof(int32_t)}, {n_overlap, N * sizeof(int32_t)}}, N, st,
-                      [&](dim3, dim3) {
-      SelfOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.ids = ids;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      // this walk's entries are bare references, one row each: half of the column that decides the route
-      launch_routed(self_overlap_kernel<true>, self_overlap_kernel<false>, r, r.lds / 2, N, st, a);
-    });
-  });
+  // (between the shared call's first and second test, which a scene and an n >= 0 pass)
+  if (s && !ids && n > 0 && (size_t)n > (size_t)s->n_tri)
+    return fail(EZRT_ERR_INVALID, "n exceeds the scene's %d triangles (ids is NULL)", (int)s->n_tri);
+  // this walk's entries are bare references, one row each: half of the column that decides the route
+  return overlap_rows_call<SelfOverlapArgs>("ezrt_query_self_overlap_device", s, true, {ids, (size_t)n * sizeof(int32_t)}, {nullptr, 0}, n, max_k,
+                                            EZRT_SELF_OVERLAP_MAX, tri_id, n_overlap, stream, self_overlap_kernel<true>,
+                                            self_overlap_kernel<false>, 2, [&](SelfOverlapArgs& a) { a.ids = ids; });
 }
 int ezrt_self_overlap_at_device(EzrtScene* s, const int32_t* tri_a, const int32_t* tri_b, int n, uint8_t* crosses, void* stream) {
   return ezi::guarded("ezrt_self_overlap_at_device", [&]() -> int {
@@ -935,30 +892,11 @@ int ezrt_segment_distance_at_device(EzrtScene* s, const float* segs6, const int3
 }
 int ezrt_query_capsule_overlap_device(EzrtScene* s, const float* segs6, const float* radius, int n, int max_k, int32_t* tri_id,
                                       int32_t* n_overlap, void* stream) {
-  return ezi::guarded("ezrt_query_capsule_overlap_device", [&]() -> int {
-    if (!s || !segs6 || !radius || n < 0) return fail(EZRT_ERR_INVALID, "NULL argument or n < 0");
-    if (max_k < 0 || max_k > EZRT_CAPSULE_OVERLAP_MAX) return fail(EZRT_ERR_INVALID, "max_k out of range [0,%d]", EZRT_CAPSULE_OVERLAP_MAX);
-    if (max_k > 0 && !tri_id) return fail(EZRT_ERR_INVALID, "tri_id is required when max_k > 0");
-    if (max_k == 0 && !n_overlap) return fail(EZRT_ERR_INVALID, "n_overlap is required when max_k == 0");
-    if (n == 0) return 0;
-    const size_t N = (size_t)n, K = (size_t)max_k;
-    if (max_k == 0) tri_id = nullptr; // ignored
-    hipStream_t st = (hipStream_t)stream;
-    return query_call(s, {{segs6, N * 6 * sizeof(float)}, {radius, N * sizeof(float)}, {tri_id, N * K * sizeof(int32_t)},
-                          {n_overlap, N * sizeof(int32_t)}}, N, st, [&](dim3, dim3) {
-      CapsuleOverlapArgs a;
-      const PointRoute r = point_scene(s, a.sc);
-      a.segs = segs6;
-      a.radius = radius;
-      a.n = (uint32_t)n;
-      a.K = max_k;
-      a.div_k = make_fastdiv((uint32_t)(max_k > 0 ? max_k : 1));
-      a.tri = tri_id;
-      a.n_overlap = n_overlap;
-      // this walk is point_walk: {lb, ref} entries, the whole column
-      launch_routed(capsule_overlap_kernel<true>, capsule_overlap_kernel<false>, r, r.lds, N, st, a);
-    });
-  });
+  // this walk is point_walk: {lb, ref} entries, the whole column
+  return overlap_rows_call<CapsuleOverlapArgs>("ezrt_query_capsule_overlap_device", s, segs6 && radius, {segs6, (size_t)n * 6 * sizeof(float)},
+                                               {radius, (size_t)n * sizeof(float)}, n, max_k, EZRT_CAPSULE_OVERLAP_MAX, tri_id, n_overlap, stream,
+                                               capsule_overlap_kernel<true>, capsule_overlap_kernel<false>, 1,
+                                               [&](CapsuleOverlapArgs& a) { a.segs = segs6, a.radius = radius; });
 }
 
 // ---- overlap lists on device memory (include/ezrt_overlap_list.h): count (the max_k == 0 calls above), offsets, fill.

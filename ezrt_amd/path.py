@@ -17,10 +17,9 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .query import _call, _keep, _scene_lib, _stream
+from .query import _OnStream, _scene_lib
 from .shade import _integrator, _tensor
 
-_P = C.c_void_p
 _XYF_DTYPES = tuple(d for d in (getattr(torch, "uint32", None), torch.int32) if d is not None)
 
 
@@ -41,11 +40,8 @@ def camera_rays(scene, params, xyf, stream=None):
     _xyf(xyf)
     rays = torch.empty(tuple(xyf.shape[:-1]) + (6,), dtype=torch.float32, device=xyf.device)
     n = xyf.numel() // 3
-    if n == 0:
-        return rays
-    h, ts = _stream(xyf, stream)
-    _call(scene, lib.ezrt_camera_rays_device(scene._h, C.byref(params), _P(xyf.data_ptr()), n, _P(rays.data_ptr()), _P(h)))
-    _keep((xyf, rays), ts, xyf)
+    if n > 0:
+        _OnStream(scene, xyf, stream).run(lib.ezrt_camera_rays_device, C.byref(params), xyf, n, rays)
     return rays
 
 
@@ -63,10 +59,6 @@ def radiance(scene, rays, xyf, integrator=_abi.INTEGRATOR_P5_MIS, max_bounce=2, 
         raise ValueError("max_bounce must not be negative")
     out = torch.empty(tuple(rays.shape[:-1]) + (3,), dtype=torch.float32, device=rays.device)
     n = rays.numel() // 6
-    if n == 0:
-        return out
-    h, ts = _stream(rays, stream)
-    _call(scene, lib.ezrt_query_radiance_device(scene._h, integrator, int(max_bounce), float(env_clamp), _P(rays.data_ptr()),
-                                                _P(xyf.data_ptr()), n, _P(out.data_ptr()), _P(h)))
-    _keep((rays, xyf, out), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_radiance_device, integrator, int(max_bounce), float(env_clamp), rays, xyf, n, out)
     return out

@@ -79,7 +79,6 @@ direction, as every `rays` above does: the segment of a ray up to t is (o, o + d
 vectors u0 u1 u2 of the box c + s0 u0 + s1 u1 + s2 u2, |s_j| <= 1; they need not be unit or orthogonal.
 """
 import collections
-import ctypes as C
 
 import torch
 
@@ -174,36 +173,92 @@ def _row_shape(tri, lead):
     return shape
 
 
-def _per_entry(x, lead, shape, h, ts):
+class _OnStream:
+    """The stream one device call of `scene` runs on, and the one path from Python into the library (shade.py and path.py use it
+    too).  `like` is a tensor of the call, or its torch.device; `stream` is None (the device's current stream), a torch.cuda.Stream
+    or a raw hipStream_t handle.  `h` is the raw handle and `stream` a torch stream object in every case.  The rule for memory, the
+    same for the three kinds of stream: a tensor the wrapper allocates and does not return is allocated inside `on()`, so its block
+    belongs to the call's stream; a tensor it returns, or was given, is allocated on the current stream and recorded by `done`."""
+    __slots__ = ("scene", "h", "stream", "side", "kept")
+
+    def __init__(self, scene, like, stream):
+        dev = like if isinstance(like, torch.device) else like.device
+        cur = torch.cuda.current_stream(dev)
+        if stream is None:
+            own, h = cur, cur.cuda_stream
+        elif isinstance(stream, torch.cuda.Stream):
+            own, h = stream, stream.cuda_stream
+        else:
+            h = int(stream)
+            own = torch.cuda.ExternalStream(h, device=dev)
+        self.scene, self.h, self.stream, self.side, self.kept = scene, h, own, own != cur, []
+
+    def on(self):
+        """The context in which torch allocates, gathers and reads on the call's stream."""
+        return torch.cuda.stream(self.stream)
+
+    def call(self, fn, *args):
+        """fn(scene handle, *args, stream handle), a TraceError unless it returns 0.  A tensor goes in as its data_ptr() (every
+        pointer parameter of _abi.py is a c_void_p, which takes an int or None) and is remembered for `done`; all else as it is."""
+        a = []
+        for x in args:
+            if isinstance(x, torch.Tensor):
+                self.kept.append(x)
+                x = x.data_ptr()
+            a.append(x)
+        rc = fn(self.scene._h, *a, self.h)
+        if rc != 0:
+            raise trace.TraceError("%s (rc=%d)" % (self.scene._tl.lib.ezrt_last_error().decode(), rc))
+
+    def done(self, *extra):
+        """The closing step: the caching allocator must not hand out the blocks of the tensors the calls were given, nor of
+        `extra`, before the call's stream is done with them."""
+        if self.side:
+            for x in self.kept + [x for x in extra if x is not None]:
+                x.record_stream(self.stream)
+        self.kept = []
+
+    def run(self, fn, *args):
+        """A wrapper's only library call: `call`, then `done`."""
+        self.call(fn, *args)
+        self.done()
+
+    def scratch(self, dev, work_bytes, summary=True):
+        """(work, summary) of a mesh call: the library's scratch of `work_bytes` (from its own *_work_bytes) as int64 words and the
+        eight int64 of its summary, zeroed -- both on the call's stream, so the scratch goes back to torch's allocator when that
+        stream is done with it."""
+        with self.on():
+            work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
+            return work, torch.zeros((8,), dtype=torch.int64, device=dev) if summary else None
+
+
+def _per_entry(x, lead, shape, q):
     """x [lead + (w,)] as one operand per entry of tri [shape]: x itself, or where a row has entries of its own a copy that repeats
     x's row for each of them, made on the query's own stream."""
     if shape == lead:
         return x
-    with torch.cuda.stream(ts if ts is not None else torch.cuda.ExternalStream(h, device=x.device)):
+    with q.on():
         return x.unsqueeze(-2).expand(lead + (shape[-1], x.shape[-1])).contiguous()
 
 
-def _stream(rays, stream):
-    """(raw handle, torch.cuda.Stream or None): the stream the query is enqueued on."""
-    if stream is None:
-        s = torch.cuda.current_stream(rays.device)
-        return s.cuda_stream, s
-    if isinstance(stream, torch.cuda.Stream):
-        return stream.cuda_stream, stream
-    return int(stream), None
+def _pairs(scene, fn, operands, tri, outs, stream):
+    """The call of an `_at` function, fn(operands..., tri, n, outputs...): tri [lead] or [lead + (K,)] checked against the first
+    operand, every operand [lead + (w,)] expanded to one row per entry of tri, and the outputs `outs` -- (trailing shape, dtype)
+    each -- allocated with tri's shape in front."""
+    dev, lead = operands[0].device, tuple(operands[0].shape[:-1])
+    _tensor("tri", tri, torch.int32, device=dev)
+    shape = _row_shape(tri, lead)
+    n = _count(tri, 1, "elements")
+    out = [torch.empty(shape + tail, dtype=dtype, device=dev) for tail, dtype in outs]
+    if n > 0:
+        q = _OnStream(scene, dev, stream)
+        q.call(fn, *[_per_entry(x, lead, shape, q) for x in operands], tri, n, *out)
+        q.done(*operands)
+    return out
 
 
-def _keep(tensors, ts, rays):
-    # the caching allocator must not hand these blocks out again before the query's stream is done with them
-    if ts is not None and ts != torch.cuda.current_stream(rays.device):
-        for x in tensors:
-            if x is not None:
-                x.record_stream(ts)
-
-
-def _call(scene, rc):
-    if rc != 0:
-        raise trace.TraceError("%s (rc=%d)" % (scene._tl.lib.ezrt_last_error().decode(), rc))
+# (dist, point_query, point_scene, crosses) of tri_distance_at and segment_distance_at
+_DISTANCE_OUTS = (((), torch.float32), ((3,), torch.float32), ((3,), torch.float32), ((), torch.uint8))
 
 
 def closest(scene, rays, t_max=None, stream=None):
@@ -212,13 +267,8 @@ def closest(scene, rays, t_max=None, stream=None):
     lead = tuple(rays.shape[:-1])
     tri = torch.empty(lead, dtype=torch.int32, device=rays.device)
     t = torch.empty(lead, dtype=torch.float32, device=rays.device)
-    if n == 0:
-        return tri, t
-    h, ts = _stream(rays, stream)
-    _call(scene, lib.ezrt_query_closest_device(scene._h, C.c_void_p(rays.data_ptr()),
-                                               C.c_void_p(t_max.data_ptr()) if t_max is not None else None, n,
-                                               C.c_void_p(tri.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(h)))
-    _keep((rays, t_max, tri, t), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_closest_device, rays, t_max, n, tri, t)
     return tri, t
 
 
@@ -226,13 +276,8 @@ def occluded(scene, rays, t_max=None, stream=None):
     """bool of shape rays.shape[:-1]: whether the ray hits a triangle at a distance below t_max (any distance without t_max)."""
     lib, n = _check(scene, rays, t_max)
     out = torch.empty(tuple(rays.shape[:-1]), dtype=torch.uint8, device=rays.device)
-    if n == 0:
-        return out.view(torch.bool)
-    h, ts = _stream(rays, stream)
-    _call(scene, lib.ezrt_query_occluded_device(scene._h, C.c_void_p(rays.data_ptr()),
-                                                C.c_void_p(t_max.data_ptr()) if t_max is not None else None, n,
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(h)))
-    _keep((rays, t_max, out), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_occluded_device, rays, t_max, n, out)
     return out.view(torch.bool)
 
 
@@ -255,14 +300,8 @@ def surface(scene, rays, t_max=None, integrator=_abi.INTEGRATOR_P5_SOBOL, stream
     point = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
     normal = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
     inside = torch.empty(lead, dtype=torch.uint8, device=rays.device)
-    if n == 0:
-        return Surface(tri, t, point, normal, inside.view(torch.bool))
-    h, ts = _stream(rays, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_surface_device(scene._h, P(rays.data_ptr()), P(t_max.data_ptr()) if t_max is not None else None,
-                                               n, int(integrator), P(tri.data_ptr()), P(t.data_ptr()), P(point.data_ptr()),
-                                               P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
-    _keep((rays, t_max, tri, t, point, normal, inside), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_surface_device, rays, t_max, n, int(integrator), tri, t, point, normal, inside)
     return Surface(tri, t, point, normal, inside.view(torch.bool))
 
 
@@ -280,13 +319,8 @@ def all_hits(scene, rays, max_hits, t_max=None, stream=None):
     tri = torch.empty(lead + (max_hits,), dtype=torch.int32, device=rays.device)
     t = torch.empty(lead + (max_hits,), dtype=torch.float32, device=rays.device)
     count = torch.empty(lead, dtype=torch.int32, device=rays.device)
-    if n == 0:
-        return tri, t, count
-    h, ts = _stream(rays, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_all_hits_device(scene._h, P(rays.data_ptr()), P(t_max.data_ptr()) if t_max is not None else None, n,
-                                                max_hits, P(tri.data_ptr()), P(t.data_ptr()), P(count.data_ptr()), P(h)))
-    _keep((rays, t_max, tri, t, count), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_all_hits_device, rays, t_max, n, max_hits, tri, t, count)
     return tri, t, count
 
 
@@ -309,14 +343,10 @@ def surface_at(scene, rays, tri, t, integrator=_abi.INTEGRATOR_P5_SOBOL, stream=
     point = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
     normal = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
     inside = torch.empty(shape, dtype=torch.uint8, device=rays.device)
-    if n == 0:
-        return point, normal, inside.view(torch.bool)
-    h, ts = _stream(rays, stream)
-    per_hit = _per_entry(rays, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_surface_at_device(scene._h, P(per_hit.data_ptr()), P(tri.data_ptr()), P(t.data_ptr()), n, int(integrator),
-                                            P(point.data_ptr()), P(normal.data_ptr()), P(inside.data_ptr()), P(h)))
-    _keep((rays, per_hit, tri, t, point, normal, inside), ts, rays)
+    if n > 0:
+        q = _OnStream(scene, rays, stream)
+        q.call(lib.ezrt_surface_at_device, _per_entry(rays, lead, shape, q), tri, t, n, int(integrator), point, normal, inside)
+        q.done(rays)
     return point, normal, inside.view(torch.bool)
 
 
@@ -341,13 +371,8 @@ def closest_point(scene, points, d_max=None, stream=None):
     point = torch.empty(lead + (3,), dtype=torch.float32, device=points.device)
     dist = torch.empty(lead, dtype=torch.float32, device=points.device)
     bary = torch.empty(lead + (2,), dtype=torch.float32, device=points.device)
-    if n == 0:
-        return ClosestPoint(tri, point, dist, bary)
-    h, ts = _stream(points, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_closest_point_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n,
-                                                     P(tri.data_ptr()), P(point.data_ptr()), P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
-    _keep((points, d_max, tri, point, dist, bary), ts, points)
+    if n > 0:
+        _OnStream(scene, points, stream).run(lib.ezrt_query_closest_point_device, points, d_max, n, tri, point, dist, bary)
     return ClosestPoint(tri, point, dist, bary)
 
 
@@ -369,13 +394,8 @@ def nearest(scene, points, k, d_max=None, count=False, stream=None):
     tri = torch.empty(lead + (k,), dtype=torch.int32, device=points.device)
     dist = torch.empty(lead + (k,), dtype=torch.float32, device=points.device)
     within = torch.empty(lead, dtype=torch.int32, device=points.device) if count else None
-    if n == 0:
-        return Nearest(tri, dist, within)
-    h, ts = _stream(points, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_nearest_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n, k,
-                                               P(tri.data_ptr()), P(dist.data_ptr()), P(within.data_ptr()) if count else None, P(h)))
-    _keep((points, d_max, tri, dist, within), ts, points)
+    if n > 0:
+        _OnStream(scene, points, stream).run(lib.ezrt_query_nearest_device, points, d_max, n, k, tri, dist, within)
     return Nearest(tri, dist, within)
 
 
@@ -387,22 +407,8 @@ def closest_point_at(scene, points, tri, stream=None):
     non-finite distance gives (zeros, +inf, zeros).  `tri` is returned as given."""
     _check_points(points, None)
     lib = _scene_lib(scene, _abi.NEAREST_ABI)
-    lead = tuple(points.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=points.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    point = torch.empty(shape + (3,), dtype=torch.float32, device=points.device)
-    dist = torch.empty(shape, dtype=torch.float32, device=points.device)
-    bary = torch.empty(shape + (2,), dtype=torch.float32, device=points.device)
-    if n == 0:
-        return ClosestPoint(tri, point, dist, bary)
-    h, ts = _stream(points, stream)
-    per_entry = _per_entry(points, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_closest_point_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(point.data_ptr()),
-                                                  P(dist.data_ptr()), P(bary.data_ptr()), P(h)))
-    _keep((points, per_entry, tri, point, dist, bary), ts, points)
-    return ClosestPoint(tri, point, dist, bary)
+    f32 = torch.float32
+    return ClosestPoint(tri, *_pairs(scene, lib.ezrt_closest_point_at_device, (points,), tri, (((3,), f32), ((), f32), ((2,), f32)), stream))
 
 
 def _check_axis(axis):
@@ -424,11 +430,7 @@ def inside(scene, points, axis=0, crossings=False, stream=None):
     out = torch.empty(lead, dtype=torch.uint8, device=points.device)
     count = torch.empty(lead, dtype=torch.int32, device=points.device) if crossings else None
     if n > 0:
-        h, ts = _stream(points, stream)
-        P = C.c_void_p
-        _call(scene, lib.ezrt_query_inside_device(scene._h, P(points.data_ptr()), n, axis, P(out.data_ptr()),
-                                                  P(count.data_ptr()) if crossings else None, P(h)))
-        _keep((points, out, count), ts, points)
+        _OnStream(scene, points, stream).run(lib.ezrt_query_inside_device, points, n, axis, out, count)
     return (out.view(torch.bool), count) if crossings else out.view(torch.bool)
 
 
@@ -446,14 +448,8 @@ def signed_distance(scene, points, d_max=None, axis=0, stream=None):
     dist = torch.empty(lead, dtype=torch.float32, device=points.device)
     bary = torch.empty(lead + (2,), dtype=torch.float32, device=points.device)
     ins = torch.empty(lead, dtype=torch.uint8, device=points.device)
-    if n == 0:
-        return SignedDistance(tri, point, dist, bary, ins.view(torch.bool))
-    h, ts = _stream(points, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_signed_distance_device(scene._h, P(points.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None,
-                                                       n, axis, P(tri.data_ptr()), P(point.data_ptr()), P(dist.data_ptr()),
-                                                       P(bary.data_ptr()), P(ins.data_ptr()), P(h)))
-    _keep((points, d_max, tri, point, dist, bary, ins), ts, points)
+    if n > 0:
+        _OnStream(scene, points, stream).run(lib.ezrt_query_signed_distance_device, points, d_max, n, axis, tri, point, dist, bary, ins)
     return SignedDistance(tri, point, dist, bary, ins.view(torch.bool))
 
 
@@ -478,25 +474,10 @@ def box_overlap(scene, lo, hi, max_k=8, count=False, stream=None):
     some axis overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
     include/ezrt_box_overlap.h; `box_overlap_at` tests pairs.  `box_overlap_list` returns every such triangle, not the
     lowest max_k."""
-    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.BOX_OVERLAP_MAX:
-        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.BOX_OVERLAP_MAX, max_k))
-    if max_k == 0 and not count:
-        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    _check_max_k(max_k, _abi.BOX_OVERLAP_MAX, count)
     n = _check_boxes(lo, hi)
     lib = _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
-    lead = tuple(lo.shape[:-1])
-    if n * max_k > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 output slots per call")
-    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=lo.device)
-    total = torch.empty(lead, dtype=torch.int32, device=lo.device) if count else None
-    if n == 0:
-        return BoxOverlap(tri, total)
-    h, ts = _stream(lo, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_box_overlap_device(scene._h, P(lo.data_ptr()), P(hi.data_ptr()), n, max_k,
-                                                   P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
-    _keep((lo, hi, tri, total), ts, lo)
-    return BoxOverlap(tri, total)
+    return BoxOverlap(*_overlap_rows(scene, lib.ezrt_query_box_overlap_device, (lo, hi), n, lo.shape[:-1], lo.device, max_k, count, stream))
 
 
 def box_overlap_at(scene, lo, hi, tri, stream=None):
@@ -505,20 +486,7 @@ def box_overlap_at(scene, lo, hi, tri, stream=None):
     that is no triangle of the scene (an unused slot, -1) gives False."""
     _check_boxes(lo, hi)
     lib = _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
-    lead = tuple(lo.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=lo.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    out = torch.empty(shape, dtype=torch.uint8, device=lo.device)
-    if n == 0:
-        return out.view(torch.bool)
-    h, ts = _stream(lo, stream)
-    per_lo, per_hi = _per_entry(lo, lead, shape, h, ts), _per_entry(hi, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_box_overlap_at_device(scene._h, P(per_lo.data_ptr()), P(per_hi.data_ptr()), P(tri.data_ptr()), n,
-                                                P(out.data_ptr()), P(h)))
-    _keep((lo, hi, per_lo, per_hi, tri, out), ts, lo)
-    return out.view(torch.bool)
+    return _pairs(scene, lib.ezrt_box_overlap_at_device, (lo, hi), tri, (((), torch.uint8),), stream)[0].view(torch.bool)
 
 
 def _check_tris(tris):
@@ -538,25 +506,10 @@ def tri_overlap(scene, tris, max_k=8, count=False, stream=None):
     collinear or repeated vertices overlaps nothing, on either side -- unlike `box_overlap`, where a degenerate triangle overlaps as
     the segment or point it is.  The definition, on the bits: include/ezrt_tri_overlap.h; `tri_overlap_at` tests pairs.  `tri_overlap_list` returns every such triangle, not the
     lowest max_k."""
-    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.TRI_OVERLAP_MAX:
-        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.TRI_OVERLAP_MAX, max_k))
-    if max_k == 0 and not count:
-        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    _check_max_k(max_k, _abi.TRI_OVERLAP_MAX, count)
     n = _check_tris(tris)
     lib = _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
-    lead = tuple(tris.shape[:-1])
-    if n * max_k > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 output slots per call")
-    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=tris.device)
-    total = torch.empty(lead, dtype=torch.int32, device=tris.device) if count else None
-    if n == 0:
-        return TriOverlap(tri, total)
-    h, ts = _stream(tris, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_tri_overlap_device(scene._h, P(tris.data_ptr()), n, max_k, P(tri.data_ptr()) if max_k else None,
-                                                   P(total.data_ptr()) if count else None, P(h)))
-    _keep((tris, tri, total), ts, tris)
-    return TriOverlap(tri, total)
+    return TriOverlap(*_overlap_rows(scene, lib.ezrt_query_tri_overlap_device, (tris,), n, tris.shape[:-1], tris.device, max_k, count, stream))
 
 
 def tri_overlap_at(scene, tris, tri, stream=None):
@@ -565,19 +518,7 @@ def tri_overlap_at(scene, tris, tri, stream=None):
     then belongs to the row's query triangle.  An id that is no triangle of the scene (an unused slot, -1) gives False."""
     _check_tris(tris)
     lib = _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
-    lead = tuple(tris.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=tris.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    out = torch.empty(shape, dtype=torch.uint8, device=tris.device)
-    if n == 0:
-        return out.view(torch.bool)
-    h, ts = _stream(tris, stream)
-    per = _per_entry(tris, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_tri_overlap_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(out.data_ptr()), P(h)))
-    _keep((tris, per, tri, out), ts, tris)
-    return out.view(torch.bool)
+    return _pairs(scene, lib.ezrt_tri_overlap_at_device, (tris,), tri, (((), torch.uint8),), stream)[0].view(torch.bool)
 
 
 def self_overlap(scene, ids=None, max_k=8, count=False, stream=None):
@@ -593,10 +534,7 @@ def self_overlap(scene, ids=None, max_k=8, count=False, stream=None):
     True).  An id that is no triangle of the scene, or a triangle that is not live, has an empty row.  The definition, on the bits:
     include/ezrt_self_overlap.h; `self_overlap_at` tests pairs.  `self_overlap_list` returns every such triangle, not the
     lowest max_k."""
-    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.SELF_OVERLAP_MAX:
-        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.SELF_OVERLAP_MAX, max_k))
-    if max_k == 0 and not count:
-        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    _check_max_k(max_k, _abi.SELF_OVERLAP_MAX, count)
     if ids is not None:
         _tensor("ids", ids, torch.int32)
     lib = _scene_lib(scene, _abi.SELF_OVERLAP_ABI)
@@ -604,20 +542,9 @@ def self_overlap(scene, ids=None, max_k=8, count=False, stream=None):
         lead, device = (scene.stats()["n_tri"],), torch.device("cuda", torch.cuda.current_device())
         n = lead[0]
     else:
-        lead, device = tuple(ids.shape), ids.device
+        lead, device = ids.shape, ids.device
         n = _count(ids, 1, "triangle ids")
-    if n * max_k > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 output slots per call")
-    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=device)
-    total = torch.empty(lead, dtype=torch.int32, device=device) if count else None
-    if n == 0:
-        return SelfOverlap(tri, total)
-    h, ts = _stream(tri, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_self_overlap_device(scene._h, P(ids.data_ptr()) if ids is not None else None, n, max_k,
-                                                    P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
-    _keep((ids, tri, total), ts, tri)
-    return SelfOverlap(tri, total)
+    return SelfOverlap(*_overlap_rows(scene, lib.ezrt_query_self_overlap_device, (ids,), n, lead, device, max_k, count, stream))
 
 
 def self_overlap_at(scene, a, b, stream=None):
@@ -629,12 +556,8 @@ def self_overlap_at(scene, a, b, stream=None):
     _tensor("b", b, torch.int32, shape=a.shape, device=a.device)
     n = _count(a, 1, "pairs")
     out = torch.empty(tuple(a.shape), dtype=torch.uint8, device=a.device)
-    if n == 0:
-        return out.view(torch.bool)
-    h, ts = _stream(a, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_self_overlap_at_device(scene._h, P(a.data_ptr()), P(b.data_ptr()), n, P(out.data_ptr()), P(h)))
-    _keep((a, b, out), ts, a)
+    if n > 0:
+        _OnStream(scene, a, stream).run(lib.ezrt_self_overlap_at_device, a, b, n, out)
     return out.view(torch.bool)
 
 
@@ -659,14 +582,8 @@ def tri_distance(scene, tris, d_max=None, stream=None):
     point_query = torch.empty(lead + (3,), dtype=torch.float32, device=tris.device)
     point_scene = torch.empty(lead + (3,), dtype=torch.float32, device=tris.device)
     crosses = torch.empty(lead, dtype=torch.uint8, device=tris.device)
-    if n == 0:
-        return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
-    h, ts = _stream(tris, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_tri_distance_device(scene._h, P(tris.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None, n,
-                                                    P(tri.data_ptr()), P(dist.data_ptr()), P(point_query.data_ptr()),
-                                                    P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
-    _keep((tris, d_max, tri, dist, point_query, point_scene, crosses), ts, tris)
+    if n > 0:
+        _OnStream(scene, tris, stream).run(lib.ezrt_query_tri_distance_device, tris, d_max, n, tri, dist, point_query, point_scene, crosses)
     return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
 
 
@@ -678,22 +595,7 @@ def tri_distance_at(scene, tris, tri, stream=None):
     is not live on either side gives (+inf, zeros, zeros, False).  `tri` is returned as given."""
     _check_tris(tris)
     lib = _scene_lib(scene, _abi.TRI_DISTANCE_ABI)
-    lead = tuple(tris.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=tris.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    dist = torch.empty(shape, dtype=torch.float32, device=tris.device)
-    point_query = torch.empty(shape + (3,), dtype=torch.float32, device=tris.device)
-    point_scene = torch.empty(shape + (3,), dtype=torch.float32, device=tris.device)
-    crosses = torch.empty(shape, dtype=torch.uint8, device=tris.device)
-    if n == 0:
-        return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
-    h, ts = _stream(tris, stream)
-    per = _per_entry(tris, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_tri_distance_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(dist.data_ptr()),
-                                                 P(point_query.data_ptr()), P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
-    _keep((tris, per, tri, dist, point_query, point_scene, crosses), ts, tris)
+    dist, point_query, point_scene, crosses = _pairs(scene, lib.ezrt_tri_distance_at_device, (tris,), tri, _DISTANCE_OUTS, stream)
     return TriDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
 
 
@@ -719,14 +621,8 @@ def sphere_cast(scene, rays, radius, t_max=None, stream=None):
     t = torch.empty(lead, dtype=torch.float32, device=rays.device)
     point = torch.empty(lead + (3,), dtype=torch.float32, device=rays.device)
     touching = torch.empty(lead, dtype=torch.uint8, device=rays.device)
-    if n == 0:
-        return SphereCast(tri, t, point, touching.view(torch.bool))
-    h, ts = _stream(rays, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_sphere_cast_device(scene._h, P(rays.data_ptr()), P(radius.data_ptr()),
-                                                   P(t_max.data_ptr()) if t_max is not None else None, n, P(tri.data_ptr()),
-                                                   P(t.data_ptr()), P(point.data_ptr()), P(touching.data_ptr()), P(h)))
-    _keep((rays, radius, t_max, tri, t, point, touching), ts, rays)
+    if n > 0:
+        _OnStream(scene, rays, stream).run(lib.ezrt_query_sphere_cast_device, rays, radius, t_max, n, tri, t, point, touching)
     return SphereCast(tri, t, point, touching.view(torch.bool))
 
 
@@ -738,22 +634,8 @@ def sphere_cast_at(scene, rays, radius, tri, stream=None):
     `tri` is returned as given."""
     _check_spheres(rays, radius, None)
     lib = _scene_lib(scene, _abi.SPHERE_CAST_ABI)
-    lead = tuple(rays.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=rays.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    t = torch.empty(shape, dtype=torch.float32, device=rays.device)
-    point = torch.empty(shape + (3,), dtype=torch.float32, device=rays.device)
-    touching = torch.empty(shape, dtype=torch.uint8, device=rays.device)
-    if n == 0:
-        return SphereCast(tri, t, point, touching.view(torch.bool))
-    h, ts = _stream(rays, stream)
-    per = _per_entry(rays, lead, shape, h, ts)
-    per_r = _per_entry(radius.unsqueeze(-1), lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_sphere_cast_at_device(scene._h, P(per.data_ptr()), P(per_r.data_ptr()), P(tri.data_ptr()), n, P(t.data_ptr()),
-                                                P(point.data_ptr()), P(touching.data_ptr()), P(h)))
-    _keep((rays, radius, per, per_r, tri, t, point, touching), ts, rays)
+    t, point, touching = _pairs(scene, lib.ezrt_sphere_cast_at_device, (rays, radius.unsqueeze(-1)), tri,
+                                (((), torch.float32), ((3,), torch.float32), ((), torch.uint8)), stream)
     return SphereCast(tri, t, point, touching.view(torch.bool))
 
 
@@ -784,14 +666,8 @@ def segment_distance(scene, segs, d_max=None, stream=None):
     point_query = torch.empty(lead + (3,), dtype=torch.float32, device=segs.device)
     point_scene = torch.empty(lead + (3,), dtype=torch.float32, device=segs.device)
     crosses = torch.empty(lead, dtype=torch.uint8, device=segs.device)
-    if n == 0:
-        return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
-    h, ts = _stream(segs, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_segment_distance_device(scene._h, P(segs.data_ptr()), P(d_max.data_ptr()) if d_max is not None else None,
-                                                        n, P(tri.data_ptr()), P(dist.data_ptr()), P(point_query.data_ptr()),
-                                                        P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
-    _keep((segs, d_max, tri, dist, point_query, point_scene, crosses), ts, segs)
+    if n > 0:
+        _OnStream(scene, segs, stream).run(lib.ezrt_query_segment_distance_device, segs, d_max, n, tri, dist, point_query, point_scene, crosses)
     return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
 
 
@@ -804,22 +680,7 @@ def segment_distance_at(scene, segs, tri, stream=None):
     `tri` is returned as given."""
     _check_segs(segs)
     lib = _scene_lib(scene, _abi.SEGMENT_ABI)
-    lead = tuple(segs.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=segs.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    dist = torch.empty(shape, dtype=torch.float32, device=segs.device)
-    point_query = torch.empty(shape + (3,), dtype=torch.float32, device=segs.device)
-    point_scene = torch.empty(shape + (3,), dtype=torch.float32, device=segs.device)
-    crosses = torch.empty(shape, dtype=torch.uint8, device=segs.device)
-    if n == 0:
-        return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
-    h, ts = _stream(segs, stream)
-    per = _per_entry(segs, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_segment_distance_at_device(scene._h, P(per.data_ptr()), P(tri.data_ptr()), n, P(dist.data_ptr()),
-                                                     P(point_query.data_ptr()), P(point_scene.data_ptr()), P(crosses.data_ptr()), P(h)))
-    _keep((segs, per, tri, dist, point_query, point_scene, crosses), ts, segs)
+    dist, point_query, point_scene, crosses = _pairs(scene, lib.ezrt_segment_distance_at_device, (segs,), tri, _DISTANCE_OUTS, stream)
     return SegmentDistance(tri, dist, point_query, point_scene, crosses.view(torch.bool))
 
 
@@ -834,27 +695,12 @@ def capsule_overlap(scene, segs, radius, max_k=8, count=False, stream=None):
     non-finite number or a negative radius touches nothing.  `segment_distance(scene, segs, radius)` finds a triangle exactly where
     the count here is > 0.  The definition, on the bits: include/ezrt_segment.h.  `capsule_overlap_list` returns every such triangle, not the
     lowest max_k."""
-    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.CAPSULE_OVERLAP_MAX:
-        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.CAPSULE_OVERLAP_MAX, max_k))
-    if max_k == 0 and not count:
-        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    _check_max_k(max_k, _abi.CAPSULE_OVERLAP_MAX, count)
     n = _check_segs(segs)
     _tensor("radius", radius, torch.float32, segs.shape[:-1], device=segs.device)
     lib = _scene_lib(scene, _abi.SEGMENT_ABI)
-    lead = tuple(segs.shape[:-1])
-    if n * max_k > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 output slots per call")
-    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=segs.device)
-    total = torch.empty(lead, dtype=torch.int32, device=segs.device) if count else None
-    if n == 0:
-        return CapsuleOverlap(tri, total)
-    h, ts = _stream(segs, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_capsule_overlap_device(scene._h, P(segs.data_ptr()), P(radius.data_ptr()), n, max_k,
-                                                       P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None,
-                                                       P(h)))
-    _keep((segs, radius, tri, total), ts, segs)
-    return CapsuleOverlap(tri, total)
+    return CapsuleOverlap(*_overlap_rows(scene, lib.ezrt_query_capsule_overlap_device, (segs, radius), n, segs.shape[:-1], segs.device,
+                                         max_k, count, stream))
 
 
 def _check_obbs(centre, axes):
@@ -882,25 +728,11 @@ def obb_overlap(scene, centre, axes, max_k=8, count=False, stream=None):
     instead) overlaps nothing, as does a triangle with a non-finite vertex.  The definition, on the bits:
     include/ezrt_obb_overlap.h; `obb_overlap_at` tests pairs.  `obb_overlap_list` returns every such triangle, not the
     lowest max_k."""
-    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= _abi.OBB_OVERLAP_MAX:
-        raise ValueError("max_k must be an int in [0, %d], not %r" % (_abi.OBB_OVERLAP_MAX, max_k))
-    if max_k == 0 and not count:
-        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+    _check_max_k(max_k, _abi.OBB_OVERLAP_MAX, count)
     n = _check_obbs(centre, axes)
     lib = _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
-    lead = tuple(centre.shape[:-1])
-    if n * max_k > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 output slots per call")
-    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=centre.device)
-    total = torch.empty(lead, dtype=torch.int32, device=centre.device) if count else None
-    if n == 0:
-        return ObbOverlap(tri, total)
-    h, ts = _stream(centre, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_obb_overlap_device(scene._h, P(centre.data_ptr()), P(axes.data_ptr()), n, max_k,
-                                                   P(tri.data_ptr()) if max_k else None, P(total.data_ptr()) if count else None, P(h)))
-    _keep((centre, axes, tri, total), ts, centre)
-    return ObbOverlap(tri, total)
+    return ObbOverlap(*_overlap_rows(scene, lib.ezrt_query_obb_overlap_device, (centre, axes), n, centre.shape[:-1], centre.device, max_k, count,
+                                     stream))
 
 
 def obb_overlap_at(scene, centre, axes, tri, stream=None):
@@ -909,21 +741,8 @@ def obb_overlap_at(scene, centre, axes, tri, stream=None):
     row's box.  An id that is no triangle of the scene (an unused slot, -1) gives False."""
     _check_obbs(centre, axes)
     lib = _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
-    lead = tuple(centre.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=centre.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    out = torch.empty(shape, dtype=torch.uint8, device=centre.device)
-    if n == 0:
-        return out.view(torch.bool)
-    h, ts = _stream(centre, stream)
-    flat = axes.reshape(lead + (9,))
-    per_c, per_u = _per_entry(centre, lead, shape, h, ts), _per_entry(flat, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_obb_overlap_at_device(scene._h, P(per_c.data_ptr()), P(per_u.data_ptr()), P(tri.data_ptr()), n,
-                                                P(out.data_ptr()), P(h)))
-    _keep((centre, axes, per_c, per_u, tri, out), ts, centre)
-    return out.view(torch.bool)
+    flat = axes.reshape(tuple(centre.shape[:-1]) + (9,))
+    return _pairs(scene, lib.ezrt_obb_overlap_at_device, (centre, flat), tri, (((), torch.uint8),), stream)[0].view(torch.bool)
 
 
 def _check_chunks(chunks):
@@ -949,13 +768,14 @@ def winding_number(scene, points, fixed=False, chunks=None, stream=None):
     n = _check_points(points, None)
     lib = _scene_lib(scene, _abi.WINDING_ABI)
     lead = tuple(points.shape[:-1])
-    acc = torch.empty(lead, dtype=torch.int64, device=points.device)    # the call's accumulator, allocated whether returned or not
+    acc = torch.empty(lead, dtype=torch.int64, device=points.device) if fixed else None
     out = torch.empty(lead, dtype=torch.float32, device=points.device)
     if n > 0:
-        h, ts = _stream(points, stream)
-        P = C.c_void_p
-        _call(scene, lib.ezrt_query_winding_device(scene._h, P(points.data_ptr()), n, c, P(acc.data_ptr()), P(out.data_ptr()), P(h)))
-        _keep((points, acc, out), ts, points)
+        q = _OnStream(scene, points, stream)
+        if not fixed:                                                # the call's accumulator, a temporary where it is not returned
+            with q.on():
+                acc = torch.empty(lead, dtype=torch.int64, device=points.device)
+        q.run(lib.ezrt_query_winding_device, points, n, c, acc, out)
     return (out, acc) if fixed else out
 
 
@@ -966,20 +786,7 @@ def winding_number_at(scene, points, tri, stream=None):
     is `winding_number`'s."""
     _check_points(points, None)
     lib = _scene_lib(scene, _abi.WINDING_ABI)
-    lead = tuple(points.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=points.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    acc = torch.empty(shape, dtype=torch.int64, device=points.device)
-    out = torch.empty(shape, dtype=torch.float32, device=points.device)
-    if n == 0:
-        return out, acc
-    h, ts = _stream(points, stream)
-    per_entry = _per_entry(points, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_winding_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(acc.data_ptr()), P(out.data_ptr()),
-                                            P(h)))
-    _keep((points, per_entry, tri, acc, out), ts, points)
+    acc, out = _pairs(scene, lib.ezrt_winding_at_device, (points,), tri, (((), torch.int64), ((), torch.float32)), stream)
     return out, acc
 
 
@@ -996,17 +803,18 @@ def _check_planes(planes):
     return _count(planes, 4, "planes")
 
 
-def _plane_counts(scene, lib, planes, n, c, h, ts, want_offsets):
-    """(S, part int32 [n, S], n_cross int32 [n], offsets int64 [n + 1] or None), enqueued on the query's stream"""
-    S = int(lib.ezrt_plane_slices(n, scene.stats()["n_tri"], c))
+def _plane_counts(q, lib, planes, n, c, n_cross=None):
+    """(part int32 [n, S], offsets int64 [n + 1] or None), enqueued on the query's stream: the counts go into the caller's n_cross
+    (int32 [n]), or without one into a temporary, and the offsets are then made of them.  part is a temporary of the caller's."""
+    S = int(lib.ezrt_plane_slices(n, q.scene.stats()["n_tri"], c))
     dev = planes.device
-    part = torch.empty((n, S), dtype=torch.int32, device=dev)
-    n_cross = torch.empty((n,), dtype=torch.int32, device=dev)
-    offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev) if want_offsets else None
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_plane_count_device(scene._h, P(planes.data_ptr()), n, c, P(part.data_ptr()), P(n_cross.data_ptr()),
-                                                   P(offsets.data_ptr()) if want_offsets else None, P(h)))
-    return S, part, n_cross, offsets
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev) if n_cross is None else None
+    with q.on():
+        part = torch.empty((n, S), dtype=torch.int32, device=dev)
+        if n_cross is None:
+            n_cross = torch.empty((n,), dtype=torch.int32, device=dev)
+    q.call(lib.ezrt_query_plane_count_device, planes, n, c, part, n_cross, offsets)
+    return part, offsets
 
 
 def plane_count(scene, planes, slices=None, stream=None):
@@ -1019,13 +827,12 @@ def plane_count(scene, planes, slices=None, stream=None):
     c = _check_slices(slices)
     n = _check_planes(planes)
     lib = _scene_lib(scene, _abi.PLANE_ABI)
-    lead = tuple(planes.shape[:-1])
-    if n == 0:
-        return torch.empty(lead, dtype=torch.int32, device=planes.device)
-    h, ts = _stream(planes, stream)
-    _, part, n_cross, _ = _plane_counts(scene, lib, planes, n, c, h, ts, False)
-    _keep((planes, part, n_cross), ts, planes)
-    return n_cross.view(lead)
+    n_cross = torch.empty(tuple(planes.shape[:-1]), dtype=torch.int32, device=planes.device)
+    if n > 0:
+        q = _OnStream(scene, planes, stream)
+        _plane_counts(q, lib, planes, n, c, n_cross)
+        q.done()
+    return n_cross
 
 
 def plane_section(scene, planes, capacity=None, slices=None, stream=None):
@@ -1039,30 +846,21 @@ def plane_section(scene, planes, capacity=None, slices=None, stream=None):
     compare offsets[n] with the capacity.  `slices` as for plane_count.  The definition, on the bits: include/ezrt_plane.h."""
     c = _check_slices(slices)
     n = _check_planes(planes)
-    if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0):
-        raise ValueError("capacity must be None or an int >= 0, not %r" % (capacity,))
+    _check_capacity("capacity", capacity)
     lib = _scene_lib(scene, _abi.PLANE_ABI)
     dev = planes.device
-    h, ts = _stream(planes, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, planes, stream)
     if n == 0:
         rows = 0 if capacity is None else capacity
-        with torch.cuda.stream(own):
+        with q.on():
             return (torch.zeros((1,), dtype=torch.int64, device=dev), torch.full((rows,), -1, dtype=torch.int32, device=dev),
                     torch.zeros((rows, 2, 3), dtype=torch.float32, device=dev))
-    _, part, n_cross, offsets = _plane_counts(scene, lib, planes, n, c, h, ts, True)
-    if capacity is None:
-        with torch.cuda.stream(own):
-            rows = int(offsets[n].item())                          # the one synchronisation: of the query's stream
-    else:
-        rows = capacity
-    with torch.cuda.stream(own):
+    part, offsets = _plane_counts(q, lib, planes, n, c)
+    with q.on():
+        rows = int(offsets[n].item()) if capacity is None else capacity    # None: the one synchronisation, of the query's stream
         tri = torch.full((rows,), -1, dtype=torch.int32, device=dev)
         seg = torch.zeros((rows, 2, 3), dtype=torch.float32, device=dev)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_query_plane_section_device(scene._h, P(planes.data_ptr()), n, c, P(part.data_ptr()), P(offsets.data_ptr()), rows,
-                                                     P(tri.data_ptr()) if rows else None, P(seg.data_ptr()) if rows else None, P(h)))
-    _keep((planes, part, n_cross, offsets, tri, seg), ts, planes)
+    q.run(lib.ezrt_query_plane_section_device, planes, n, c, part, offsets, rows, tri if rows else None, seg if rows else None)
     return offsets, tri, seg
 
 
@@ -1075,21 +873,8 @@ def plane_section_at(scene, planes, tri, stream=None):
     is not crossed has a zero seg.  `crosses` summed over all triangles of the scene is plane_count's."""
     _check_planes(planes)
     lib = _scene_lib(scene, _abi.PLANE_ABI)
-    lead = tuple(planes.shape[:-1])
-    _tensor("tri", tri, torch.int32, device=planes.device)
-    shape = _row_shape(tri, lead)
-    n = _count(tri, 1, "elements")
-    crosses = torch.empty(shape, dtype=torch.uint8, device=planes.device)
-    side = torch.empty(shape + (3,), dtype=torch.int8, device=planes.device)
-    seg = torch.empty(shape + (2, 3), dtype=torch.float32, device=planes.device)
-    if n == 0:
-        return crosses.view(torch.bool), side, seg
-    h, ts = _stream(planes, stream)
-    per_entry = _per_entry(planes, lead, shape, h, ts)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_plane_section_at_device(scene._h, P(per_entry.data_ptr()), P(tri.data_ptr()), n, P(crosses.data_ptr()),
-                                                  P(side.data_ptr()), P(seg.data_ptr()), P(h)))
-    _keep((planes, per_entry, tri, crosses, side, seg), ts, planes)
+    crosses, side, seg = _pairs(scene, lib.ezrt_plane_section_at_device, (planes,), tri,
+                                (((), torch.uint8), ((3,), torch.int8), ((2, 3), torch.float32)), stream)
     return crosses.view(torch.bool), side, seg
 
 
@@ -1142,29 +927,25 @@ def _plane_loops_of(scene, offsets, seg, capacity, loop_capacity, want_next, til
     n = _count(offsets, 1, "planes") - 1
     lib = _scene_lib(scene, _abi.PLANE_LOOPS_ABI)
     dev = offsets.device
-    h, ts = _stream(offsets, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, offsets, stream)
     lcap = rows if loop_capacity is None else loop_capacity
     work_bytes = int(lib.ezrt_plane_loops_work_bytes(rows))
-    with torch.cuda.stream(own):
+    work = q.scratch(dev, work_bytes + 8, summary=False)[0]
+    with q.on():
         nxt = torch.full((rows,), -1, dtype=torch.int64, device=dev) if want_next else None
         order = torch.full((rows,), -1, dtype=torch.int64, device=dev)
         plane_loops = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
         loop_offsets = torch.full((lcap + 1,), -1, dtype=torch.int64, device=dev)
         closed = torch.zeros((lcap,), dtype=torch.uint8, device=dev)
-        work = torch.empty((work_bytes // 8 + 1,), dtype=torch.int64, device=dev)
         if n == 0:
             loop_offsets[0] = 0
-    P = C.c_void_p
     if n > 0:
-        _call(scene, lib.ezrt_plane_loops_device(scene._h, P(offsets.data_ptr()), n, P(seg.data_ptr()) if rows else None, rows, c,
-                                                 P(nxt.data_ptr()) if want_next and rows else None, P(order.data_ptr()) if rows else None,
-                                                 P(plane_loops.data_ptr()), lcap, P(loop_offsets.data_ptr()),
-                                                 P(closed.data_ptr()) if lcap else None, P(work.data_ptr()), work_bytes, P(h)))
-    _keep((offsets, seg, nxt, order, plane_loops, loop_offsets, closed, work), ts, offsets)
+        q.call(lib.ezrt_plane_loops_device, offsets, n, seg if rows else None, rows, c, nxt if rows else None, order if rows else None,
+               plane_loops, lcap, loop_offsets, closed if lcap else None, work, work_bytes)
+    q.done(offsets, seg, nxt, order, plane_loops, loop_offsets, closed)
     R = None
     if loop_capacity is None:
-        with torch.cuda.stream(own):                                 # the one synchronisation, of the query's stream: L, and the chained
+        with q.on():                                                 # the one synchronisation, of the query's stream: L, and the chained
             L, R = torch.stack([plane_loops[n], (order >= 0).sum()]).tolist()   # rows (the entries of order that were written)
         loop_offsets, closed = loop_offsets[:L + 1], closed[:L]
     return PlaneLoopsOf(nxt, order, plane_loops, loop_offsets, closed), R
@@ -1185,12 +966,11 @@ def plane_loops(scene, planes, slices=None, tile_rows=None, stream=None):
     _check_tile_rows(tile_rows)
     offsets, tri, seg = plane_section(scene, planes, slices=slices, stream=stream)
     lp, R = _plane_loops_of(scene, offsets, seg, None, None, False, tile_rows, stream)
-    h, ts = _stream(planes, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=planes.device)
-    with torch.cuda.stream(own):
+    q = _OnStream(scene, planes, stream)
+    with q.on():
         row = lp.order[:R]
         out = PlaneLoops(lp.plane_loops, lp.loop_offsets, lp.closed, row, tri[row], seg[row])
-    _keep(out + (tri, seg, lp.order), ts, planes)
+    q.done(tri, seg, lp.order, *out)
     return out
 
 
@@ -1238,30 +1018,23 @@ def mesh_topology(scene, components=True, mult=False, stream=None):
     lib = _scene_lib(scene, _abi.TOPOLOGY_ABI)
     n = scene.stats()["n_tri"]
     dev = torch.device("cuda", torch.cuda.current_device())
-    probe = torch.empty((0,), dtype=torch.int32, device=dev)
-    h, ts = _stream(probe, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, dev, stream)
     work_bytes = int(lib.ezrt_topology_work_bytes(n))
+    work, summary = q.scratch(dev, work_bytes)
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-    with torch.cuda.stream(own):
+    with q.on():
         twin, cls = i32(n, 3), torch.empty((n, 3), dtype=torch.uint8, device=dev)
         mu = i32(n, 3) if mult else None
         root, comp, croot, csize = (i32(n), i32(n), i32(n), i32(n)) if components else (None,) * 4
         cflags = torch.empty((n,), dtype=torch.uint8, device=dev) if components else None
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_mesh_topology_device(scene._h, ptr(twin), ptr(cls), ptr(mu), ptr(root), ptr(comp), ptr(croot), ptr(csize),
-                                                   ptr(cflags), ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((twin, cls, mu, root, comp, croot, csize, cflags, summary, work), ts, probe)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_mesh_topology_device, twin, cls, mu, root, comp, croot, csize, cflags, summary, work, work_bytes)
+    with q.on():
         nb = torch.where(twin >= 0, torch.div(twin, 3, rounding_mode="floor"), twin)
         sm = summary.tolist()                                        # the one synchronisation, of the query's stream
         if components:
             croot, csize, cflags = croot[:sm[6]], csize[:sm[6]], cflags[:sm[6]]
-    _keep((nb,), ts, probe)
+    q.done(twin, cls, mu, root, comp, croot, csize, cflags, summary, nb)
     return MeshTopology(twin, cls, nb, mu, root, comp, croot, csize, cflags, summary, sm[2] == 0 and sm[5] == 0, sm[4] == 0 and sm[5] == 0)
 
 
@@ -1278,13 +1051,8 @@ def mesh_topology_at(scene, tri_a, edge_a, tri_b, stream=None):
     n = _count(tri_a, 1, "pairs")
     shared = torch.empty(tuple(tri_a.shape), dtype=torch.int8, device=tri_a.device)
     opposite = torch.empty(tuple(tri_a.shape), dtype=torch.int8, device=tri_a.device)
-    if n == 0:
-        return shared, opposite
-    h, ts = _stream(tri_a, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_mesh_topology_at_device(scene._h, P(tri_a.data_ptr()), P(edge_a.data_ptr()), P(tri_b.data_ptr()), n,
-                                                  P(shared.data_ptr()), P(opposite.data_ptr()), P(h)))
-    _keep((tri_a, edge_a, tri_b, shared, opposite), ts, tri_a)
+    if n > 0:
+        _OnStream(scene, tri_a, stream).run(lib.ezrt_mesh_topology_at_device, tri_a, edge_a, tri_b, n, shared, opposite)
     return shared, opposite
 
 
@@ -1308,26 +1076,20 @@ def mesh_weld(scene, flags=True, stream=None):
     lib = _scene_lib(scene, _abi.WELD_ABI)
     n = scene.stats()["n_tri"]
     dev = torch.device("cuda", torch.cuda.current_device())
-    probe = torch.empty((0,), dtype=torch.int32, device=dev)
-    h, ts = _stream(probe, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, dev, stream)
     work_bytes = int(lib.ezrt_weld_work_bytes(n))
+    work, summary = q.scratch(dev, work_bytes)
     i32 = lambda k: torch.empty((k,), dtype=torch.int32, device=dev)
-    with torch.cuda.stream(own):
+    with q.on():
         vertex, corner, offsets, star = i32(3 * n).view(n, 3), i32(3 * n), i32(3 * n + 1), i32(3 * n)
         fans = i32(3 * n) if flags else None
         vflags = torch.empty((3 * n,), dtype=torch.uint8, device=dev) if flags else None
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
         if n == 0:
             offsets.zero_()
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_mesh_weld_device(scene._h, ptr(vertex), ptr(corner), ptr(offsets), ptr(star), ptr(fans), ptr(vflags),
-                                               ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((vertex, corner, offsets, star, fans, vflags, summary, work), ts, probe)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_mesh_weld_device, vertex, corner, offsets, star, fans, vflags, summary, work, work_bytes)
+    q.done(vertex, corner, offsets, star, fans, vflags, summary)
+    with q.on():
         sm = summary.tolist()                                        # the one synchronisation, of the query's stream
     L, V = sm[0], sm[1]
     return MeshWeld(vertex, corner[:V], offsets[:V + 1], star[:L], fans[:V] if flags else None, vflags[:V] if flags else None, summary, V,
@@ -1343,22 +1105,18 @@ def mesh_weld_at(scene, corner_a, corner_b, stream=None):
     lib = _scene_lib(scene, _abi.WELD_ABI)
     n = _count(corner_a, 1, "pairs")
     same = torch.empty(tuple(corner_a.shape), dtype=torch.int8, device=corner_a.device)
-    if n == 0:
-        return same
-    h, ts = _stream(corner_a, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_mesh_weld_at_device(scene._h, P(corner_a.data_ptr()), P(corner_b.data_ptr()), n, P(same.data_ptr()), P(h)))
-    _keep((corner_a, corner_b, same), ts, corner_a)
+    if n > 0:
+        _OnStream(scene, corner_a, stream).run(lib.ezrt_mesh_weld_at_device, corner_a, corner_b, n, same)
     return same
 
 
-def _weld_array(name, x, size, dev, own, dtype=torch.int32):
+def _weld_array(name, x, size, dev, q, dtype=torch.int32):
     """x, an int32 array of a weld (or its uint8 flags), as the `size` entries the C call may read: x itself where that much memory
     lies behind it (the trimmed views of mesh_weld), else a zero-padded copy made on the query's stream"""
     _tensor(name, x, dtype, device=dev)
     if x.numel() >= size or (x.untyped_storage().nbytes() - x.storage_offset() * x.element_size()) >= size * x.element_size():
         return x
-    with torch.cuda.stream(own):
+    with q.on():
         full = torch.zeros((size,), dtype=dtype, device=dev)
         full[:x.numel()] = x.reshape(-1)
     return full
@@ -1375,22 +1133,17 @@ def vertex_normals(scene, tri36, weld, stream=None):
     n = scene.stats()["n_tri"]
     _tensor("tri36", tri36, torch.float32, shape=(n, 36))
     dev = tri36.device
-    h, ts = _stream(tri36, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
-    vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, own)
-    offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, own)
-    star = _weld_array("weld.star", weld.star, 3 * n, dev, own)
+    q = _OnStream(scene, tri36, stream)
+    vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, q)
+    offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, q)
+    star = _weld_array("weld.star", weld.star, 3 * n, dev, q)
     if vertex.numel() != 3 * n:
         raise ValueError("weld.vertex must have 3 * n_tri = %d entries, not %d" % (3 * n, vertex.numel()))
     if n == 0:
         return tri36
     work_bytes = int(lib.ezrt_vertex_normals_work_bytes(n))
-    with torch.cuda.stream(own):
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_vertex_normals_device(scene._h, P(tri36.data_ptr()), n, P(vertex.data_ptr()), P(offsets.data_ptr()),
-                                                P(star.data_ptr()), P(work.data_ptr()), work_bytes, P(h)))
-    _keep((tri36, vertex, offsets, star, work), ts, tri36)
+    work = q.scratch(dev, work_bytes, summary=False)[0]
+    q.run(lib.ezrt_vertex_normals_device, tri36, n, vertex, offsets, star, work, work_bytes)
     return tri36
 
 
@@ -1440,23 +1193,19 @@ def mesh_orient(scene, topo=None, outward=True, stream=None):
     if twin.numel() != 3 * n or cls.numel() != 3 * n:
         raise ValueError("topo.twin and topo.edge_class must have 3 * n_tri = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
     dev = twin.device
-    h, ts = _stream(twin, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, twin, stream)
     work_bytes = int(lib.ezrt_orient_work_bytes(n))
+    work, summary = q.scratch(dev, work_bytes)
     i32 = lambda: torch.empty((n,), dtype=torch.int32, device=dev)
     u8 = lambda: torch.empty((n,), dtype=torch.uint8, device=dev)
-    with torch.cuda.stream(own):
+    with q.on():
         flip, root, patch, proot, psize, pflags = u8(), i32(), i32(), i32(), i32(), u8()
         vol6 = torch.empty((n,), dtype=torch.int64, device=dev)
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr())
     if n > 0:
-        _call(scene, lib.ezrt_mesh_orient_device(scene._h, ptr(twin), ptr(cls), 1 if outward else 0, ptr(flip), ptr(root), ptr(patch), ptr(proot),
-                                                 ptr(psize), ptr(pflags), ptr(vol6), ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((twin, cls, flip, root, patch, proot, psize, pflags, vol6, summary, work), ts, twin)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_mesh_orient_device, twin, cls, 1 if outward else 0, flip, root, patch, proot, psize, pflags, vol6, summary, work,
+               work_bytes)
+    q.done(twin, cls, flip, root, patch, proot, psize, pflags, vol6, summary)
+    with q.on():
         sm = summary.tolist()                                        # the one synchronisation, of the query's stream
     k = sm[1]
     return MeshOrient(flip, root, patch, proot[:k], psize[:k], pflags[:k], vol6[:k], summary, k, sm[2] == sm[1], sm[6])
@@ -1472,12 +1221,8 @@ def rewind(scene, tri36, orient, stream=None):
     n = scene.stats()["n_tri"]
     _tensor("tri36", tri36, torch.float32, shape=(n, 36))
     flip = _tensor("orient.flip", orient.flip, torch.uint8, shape=(n,), device=tri36.device)
-    if n == 0:
-        return tri36
-    h, ts = _stream(tri36, stream)
-    P = C.c_void_p
-    _call(scene, lib.ezrt_rewind_device(scene._h, P(tri36.data_ptr()), n, P(flip.data_ptr()), P(h)))
-    _keep((tri36, flip), ts, tri36)
+    if n > 0:
+        _OnStream(scene, tri36, stream).run(lib.ezrt_rewind_device, tri36, n, flip)
     return tri36
 
 
@@ -1517,25 +1262,20 @@ def mesh_boundary(scene, topo=None, area=True, stream=None):
     if twin.numel() != 3 * n or cls.numel() != 3 * n:
         raise ValueError("topo.twin and topo.edge_class must have 3 * n_tri = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
     dev = twin.device
-    h, ts = _stream(twin, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, twin, stream)
     work_bytes = int(lib.ezrt_boundary_work_bytes(n))
+    work, summary = q.scratch(dev, work_bytes)
     H = 3 * n
     i32 = lambda k: torch.empty((k,), dtype=torch.int32, device=dev)
-    with torch.cuda.stream(own):
+    with q.on():
         nxt, loop, pos, order, offsets = i32(H), i32(H), i32(H), i32(H), i32(H + 1)
         lflags = torch.empty((H,), dtype=torch.uint8, device=dev)
         area2 = torch.empty((H, 3), dtype=torch.int64, device=dev) if area else None
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
         offsets[:1] = 0                                                        # (a scene without triangles: L = 0, B = 0)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_mesh_boundary_device(scene._h, ptr(twin), ptr(cls), ptr(nxt), ptr(loop), ptr(pos), ptr(order), ptr(offsets),
-                                                   ptr(lflags), ptr(area2), ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((twin, cls, nxt, loop, pos, order, offsets, lflags, area2, summary, work), ts, twin)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_mesh_boundary_device, twin, cls, nxt, loop, pos, order, offsets, lflags, area2, summary, work, work_bytes)
+    q.done(twin, cls, nxt, loop, pos, order, offsets, lflags, area2, summary)
+    with q.on():
         sm = summary.tolist()                                        # the one synchronisation, of the query's stream
     B, L = sm[0], sm[1]
     return MeshBoundary(nxt, loop, pos, order[:B], offsets[:L + 1], lflags[:L], area2[:L] if area else None, summary, B, L, sm[2] == sm[1],
@@ -1587,24 +1327,19 @@ def cap_rows(scene, tri36, boundary, stream=None):
     if not 0 <= b.n_loops <= b.n_boundary <= H:
         raise ValueError("boundary is not of this scene: %d loops, %d boundary half-edges, %d half-edges" % (b.n_loops, b.n_boundary, H))
     B = b.n_boundary
-    h, ts = _stream(tri36, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
-    with torch.cuda.stream(own):
+    q = _OnStream(scene, tri36, stream)
+    with q.on():
         # the library takes arrays of the full size; order, loop_offsets and lflags were cut to what was written
         room = lambda x: x.untyped_storage().nbytes() // x.element_size() - x.storage_offset()
         pad = lambda x, k: x if x.numel() and room(x) >= k else torch.cat([x, torch.zeros((k - x.numel(),), dtype=x.dtype, device=dev)])
         order, offsets, lflags = pad(b.order, H), pad(b.loop_offsets, H + 1), pad(b.lflags, H)
         cap = torch.empty((H, 36), dtype=torch.float32, device=dev)
         valid = torch.zeros((H,), dtype=torch.uint8, device=dev)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr())
     if n > 0:
-        _call(scene, lib.ezrt_cap_rows_device(scene._h, ptr(tri36), n, ptr(order), ptr(b.loop), ptr(b.pos), ptr(offsets), ptr(lflags),
-                                              ptr(b.summary), ptr(cap), ptr(valid), P(h)))
-    _keep((tri36, order, b.loop, b.pos, offsets, lflags, b.summary, cap, valid), ts, tri36)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_cap_rows_device, tri36, n, order, b.loop, b.pos, offsets, lflags, b.summary, cap, valid)
+    with q.on():
         out = cap[:B][valid[:B] != 0]
-    _keep((out,), ts, tri36)
+    q.done(tri36, order, b.loop, b.pos, offsets, lflags, b.summary, out)
     return out
 
 
@@ -1636,34 +1371,29 @@ def clip_rows(scene, tri36, plane, src=True, stream=None):
     if n > (2**31 - 1) // 2:
         raise ValueError("at most (2^31 - 1) / 2 rows per call")
     dev = tri36.device
-    h, ts = _stream(tri36, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, tri36, stream)
     if isinstance(plane, torch.Tensor):
         _tensor("plane", plane, torch.float32, shape=(4,), device=dev)
     else:
         p = [float(x) for x in plane]
         if len(p) != 4:
             raise ValueError("plane must have four entries (a, b, c, d), not %d" % len(p))
-        with torch.cuda.stream(own):
+        with q.on():
             plane = torch.tensor(p, dtype=torch.float64).to(torch.float32).to(dev)
     work_bytes = int(lib.ezrt_clip_work_bytes(n))
-    with torch.cuda.stream(own):
+    work, summary = q.scratch(dev, work_bytes)
+    with q.on():
         offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_clip_count_device(scene._h, ptr(tri36), n, ptr(plane), ptr(offsets), ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((tri36, plane, offsets, summary, work), ts, tri36)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_clip_count_device, tri36, n, plane, offsets, summary, work, work_bytes)
+    with q.on():
         T = int(offsets[n].item())                                   # the one synchronisation, of the query's stream
         rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
         srcs = torch.empty((T,), dtype=torch.int32, device=dev) if src else None
         cut = torch.empty((T,), dtype=torch.int8, device=dev) if src else None
     if n > 0 and T > 0:
-        _call(scene, lib.ezrt_clip_rows_device(scene._h, ptr(tri36), n, ptr(plane), ptr(offsets), T, ptr(rows), ptr(srcs), ptr(cut), P(h)))
-    _keep((rows, srcs, cut), ts, tri36)
+        q.call(lib.ezrt_clip_rows_device, tri36, n, plane, offsets, T, rows, srcs, cut)
+    q.done(tri36, plane, summary, rows, srcs, cut)
     return ClipRows(rows, srcs, cut, summary, n)
 
 
@@ -1708,8 +1438,7 @@ def subdivide_rows(scene, tri36, mode="midpoint", topo=None, weld=None, stream=N
     if n > (2**31 - 1) // 12:
         raise ValueError("at most (2^31 - 1) / 12 rows per call")
     dev = tri36.device
-    h, ts = _stream(tri36, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, tri36, stream)
     arrays = (None,) * 6
     if loop:
         if topo is None or weld is None or getattr(weld, "vert_flags", None) is None:
@@ -1718,29 +1447,25 @@ def subdivide_rows(scene, tri36, mode="midpoint", topo=None, weld=None, stream=N
         cls = _tensor("topo.edge_class", topo.edge_class, torch.uint8, device=dev)
         if twin.numel() != 3 * n or cls.numel() != 3 * n:
             raise ValueError("topo.twin and topo.edge_class must have 3 * n = %d entries, not %d and %d" % (3 * n, twin.numel(), cls.numel()))
-        vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, own)
+        vertex = _weld_array("weld.vertex", weld.vertex, 3 * n, dev, q)
         if vertex.numel() != 3 * n:
             raise ValueError("weld.vertex must have 3 * n = %d entries, not %d" % (3 * n, vertex.numel()))
-        offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, own)
-        star = _weld_array("weld.star", weld.star, 3 * n, dev, own)
-        vflags = _weld_array("weld.vert_flags", weld.vert_flags, 3 * n, dev, own, torch.uint8)
+        offsets = _weld_array("weld.star_offsets", weld.star_offsets, 3 * n + 1, dev, q)
+        star = _weld_array("weld.star", weld.star, 3 * n, dev, q)
+        vflags = _weld_array("weld.vert_flags", weld.vert_flags, 3 * n, dev, q, torch.uint8)
         arrays = (twin, cls, vertex, offsets, star, vflags)
     elif topo is not None or weld is not None:
         raise ValueError('mode="midpoint" takes no topo and no weld')
     code = _abi.SUBDIVIDE_LOOP if loop else _abi.SUBDIVIDE_MIDPOINT
     work_bytes = int(lib.ezrt_subdivide_work_bytes(n, code))
-    with torch.cuda.stream(own):
+    work, summary = q.scratch(dev, work_bytes)
+    with q.on():
         rows = torch.empty((4 * n, 36), dtype=torch.float32, device=dev)
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
         if n == 0:
             summary[6] = code
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_subdivide_rows_device(scene._h, ptr(tri36), n, code, *[ptr(x) for x in arrays], ptr(rows), ptr(summary),
-                                                    ptr(work), work_bytes, P(h)))
-    _keep((tri36, rows, summary, work) + arrays, ts, tri36)
+        q.call(lib.ezrt_subdivide_rows_device, tri36, n, code, *arrays, rows, summary, work, work_bytes)
+    q.done(tri36, rows, summary, *arrays)
     return SubdivRows(rows, summary, n)
 
 
@@ -1777,34 +1502,28 @@ def decimate_rows(scene, tri36, cell_size, origin=(0, 0, 0), dedup=True, src=Tru
     if len(o) != 3:
         raise ValueError("origin must have three entries, not %d" % len(o))
     dev = tri36.device
-    h, ts = _stream(tri36, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, tri36, stream)
     flags = _abi.DECIMATE_DEDUP if dedup else 0
     work_bytes = int(lib.ezrt_decimate_work_bytes(n))
-    with torch.cuda.stream(own):
+    work, summary = q.scratch(dev, work_bytes)
+    with q.on():
         grid = torch.tensor(o + [float(cell_size)], dtype=torch.float64).to(torch.float32).to(dev)
         cell = torch.full((n, 3), -1, dtype=torch.int32, device=dev)
         corner = torch.empty((3 * n,), dtype=torch.int32, device=dev)
         point = torch.empty((3 * n, 3), dtype=torch.float32, device=dev)
         offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
         if n == 0:
             summary[6] = flags
             summary[7] = int(bool(torch.isfinite(grid).all()) and float(grid[3]) > 0)
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n > 0:
-        _call(scene, lib.ezrt_decimate_count_device(scene._h, ptr(tri36), n, ptr(grid), flags, ptr(cell), ptr(corner), ptr(point), ptr(offsets),
-                                                    ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((tri36, grid, cell, corner, point, offsets, summary, work), ts, tri36)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_decimate_count_device, tri36, n, grid, flags, cell, corner, point, offsets, summary, work, work_bytes)
+    with q.on():
         T, n_cells = (int(x) for x in torch.stack([offsets[n], summary[4]]).tolist())   # the one synchronisation, of the query's stream
         rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
         srcs = torch.empty((T,), dtype=torch.int32, device=dev) if src else None
     if n > 0 and T > 0:
-        _call(scene, lib.ezrt_decimate_rows_device(scene._h, ptr(tri36), n, ptr(cell), ptr(point), ptr(offsets), T, ptr(rows), ptr(srcs), P(h)))
-    _keep((rows, srcs), ts, tri36)
+        q.call(lib.ezrt_decimate_rows_device, tri36, n, cell, point, offsets, T, rows, srcs)
+    q.done(tri36, cell, point, summary, rows, srcs)
     return DecimatedRows(rows, srcs, cell, point[:n_cells], summary, n)
 
 
@@ -1884,58 +1603,70 @@ def isosurface_rows(scene, values, iso, origin=(0, 0, 0), spacing=1.0, material=
     if len(mat) != 18:
         raise ValueError("material must have 18 entries, not %d" % len(mat))
     dev = values.device
-    h, ts = _stream(values, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, values, stream)
     n_cells = (nx - 1) * (ny - 1) * (nz - 1)
     n_blocks = (n_cells + _abi.ISO_BLOCK - 1) // _abi.ISO_BLOCK
     work_bytes = int(lib.ezrt_iso_work_bytes(nx, ny, nz))
     grid_host = torch.tensor(o + hh + [float(iso), 0.0], dtype=torch.float64).to(torch.float32)
-    with torch.cuda.stream(own):
+    work, summary = q.scratch(dev, work_bytes)
+    with q.on():
         grid = grid_host.to(dev)
         mat18 = torch.tensor(mat, dtype=torch.float64).to(torch.float32).to(dev)
         offsets = torch.zeros((n_blocks + 1,), dtype=torch.int64, device=dev)
-        summary = torch.zeros((8,), dtype=torch.int64, device=dev)
-        work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=dev)
         if n_cells == 0:                                             # the C call writes nothing then: G1's LIVE, restated (see the docstring)
             summary[6] = int(bool(torch.isfinite(grid_host[:7]).all()) and bool((grid_host[3:6] > 0).all()))
-    P = C.c_void_p
-    ptr = lambda x: P(x.data_ptr()) if x is not None else None
     if n_cells > 0:
-        _call(scene, lib.ezrt_iso_count_device(scene._h, ptr(values), nx, ny, nz, ptr(grid), ptr(offsets), ptr(summary), ptr(work), work_bytes, P(h)))
-    _keep((values, grid, mat18, offsets, summary, work), ts, values)
-    with torch.cuda.stream(own):
+        q.call(lib.ezrt_iso_count_device, values, nx, ny, nz, grid, offsets, summary, work, work_bytes)
+    with q.on():
         T = int(offsets[n_blocks].item())                            # the one synchronisation, of the query's stream
         rows = torch.empty((T, 36), dtype=torch.float32, device=dev)
         cells = torch.empty((T,), dtype=torch.int32, device=dev) if cell else None
     if n_cells > 0 and T > 0:
-        _call(scene, lib.ezrt_iso_rows_device(scene._h, ptr(values), nx, ny, nz, ptr(grid), ptr(mat18), ptr(offsets), T, ptr(rows), ptr(cells), P(h)))
-    _keep((rows, cells), ts, values)
+        q.call(lib.ezrt_iso_rows_device, values, nx, ny, nz, grid, mat18, offsets, T, rows, cells)
+    q.done(values, summary, rows, cells)
     return IsoRows(rows, cells, summary, (nz, ny, nx))
 
 
-def _overlap_list(scene, n, dev, inputs, capacity, check, stream, count, fill):
-    """The three steps of include/ezrt_overlap_list.h on the query's stream: count(lib, n_overlap, h) is the sibling's max_k == 0 call,
-    then the offsets, then fill(lib, offsets, capacity, tri, n_found, h).  `inputs` are the caller's tensors, kept alive for the stream."""
-    if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0):
-        raise ValueError("capacity must be None or an int >= 0, not %r" % (capacity,))
+def _check_max_k(max_k, most, count):
+    if not isinstance(max_k, int) or isinstance(max_k, bool) or not 0 <= max_k <= most:
+        raise ValueError("max_k must be an int in [0, %d], not %r" % (most, max_k))
+    if max_k == 0 and not count:
+        raise ValueError("max_k == 0 asks for the count alone: pass count=True")
+
+
+def _overlap_rows(scene, fn, inputs, n, lead, dev, max_k, count, stream):
+    """(tri int32 lead + (max_k,), n_overlap int32 lead or None) of a max_k call fn(inputs..., n, max_k, tri, n_overlap) for n queries,
+    after _check_max_k and the function's own checks of its `inputs`."""
+    lead = tuple(lead)
+    if n * max_k > 2**31 - 1:
+        raise ValueError("at most 2^31 - 1 output slots per call")
+    tri = torch.empty(lead + (max_k,), dtype=torch.int32, device=dev)
+    total = torch.empty(lead, dtype=torch.int32, device=dev) if count else None
+    if n > 0:
+        _OnStream(scene, dev, stream).run(fn, *inputs, n, max_k, tri if max_k else None, total)
+    return tri, total
+
+
+def _overlap_list(scene, kind, inputs, n, dev, capacity, check, stream):
+    """The three steps of include/ezrt_overlap_list.h on the query's stream for the `kind` ("box", "obb", ...) of query whose
+    `inputs` the caller has checked: the sibling's max_k == 0 call, then the offsets, then the fill."""
+    _check_capacity("capacity", capacity)
     lib = _scene_lib(scene, _abi.OVERLAP_LIST_ABI)
-    n_overlap = torch.empty((n,), dtype=torch.int32, device=dev)
-    h, ts = _stream(n_overlap, stream)
-    own = ts if ts is not None else torch.cuda.ExternalStream(h, device=dev)
+    q = _OnStream(scene, dev, stream)
     n_found = torch.empty((n,), dtype=torch.int32, device=dev) if check else None
     if n == 0:
         rows = 0 if capacity is None else capacity
-        with torch.cuda.stream(own):
+        with q.on():
             return OverlapList(torch.zeros((1,), dtype=torch.int64, device=dev), torch.full((rows,), -1, dtype=torch.int32, device=dev), n_found)
     offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-    P = C.c_void_p
-    _call(scene, count(lib, P(n_overlap.data_ptr()), P(h)))
-    _call(scene, lib.ezrt_overlap_offsets_device(scene._h, P(n_overlap.data_ptr()), n, P(offsets.data_ptr()), P(h)))
-    with torch.cuda.stream(own):
+    with q.on():
+        n_overlap = torch.empty((n,), dtype=torch.int32, device=dev)
+    q.call(getattr(lib, "ezrt_query_%s_overlap_device" % kind), *inputs, n, 0, None, n_overlap)
+    q.call(lib.ezrt_overlap_offsets_device, n_overlap, n, offsets)
+    with q.on():
         rows = int(offsets[n].item()) if capacity is None else capacity    # None: the one synchronisation, of the query's stream
         tri = torch.full((rows,), -1, dtype=torch.int32, device=dev)
-    _call(scene, fill(lib, P(offsets.data_ptr()), rows, P(tri.data_ptr()) if rows else None, P(n_found.data_ptr()) if check else None, P(h)))
-    _keep(tuple(inputs) + (n_overlap, offsets, tri, n_found), ts, n_overlap)
+    q.run(getattr(lib, "ezrt_query_%s_overlap_list_device" % kind), *inputs, n, offsets, rows, tri if rows else None, n_found)
     return OverlapList(offsets, tri, n_found)
 
 
@@ -1951,11 +1682,7 @@ def box_overlap_list(scene, lo, hi, capacity=None, check=False, stream=None):
     contract: include/ezrt_overlap_list.h."""
     n = _check_boxes(lo, hi)
     _scene_lib(scene, _abi.BOX_OVERLAP_ABI)
-    P = C.c_void_p
-    a = (scene._h, P(lo.data_ptr()), P(hi.data_ptr()), n)
-    return _overlap_list(scene, n, lo.device, (lo, hi), capacity, check, stream,
-                         lambda lib, n_overlap, h: lib.ezrt_query_box_overlap_device(*a, 0, None, n_overlap, h),
-                         lambda lib, *out: lib.ezrt_query_box_overlap_list_device(*a, *out))
+    return _overlap_list(scene, "box", (lo, hi), n, lo.device, capacity, check, stream)
 
 
 def obb_overlap_list(scene, centre, axes, capacity=None, check=False, stream=None):
@@ -1963,11 +1690,7 @@ def obb_overlap_list(scene, centre, axes, capacity=None, check=False, stream=Non
     touches each box, in ascending id, CSR.  The contract: include/ezrt_overlap_list.h."""
     n = _check_obbs(centre, axes)
     _scene_lib(scene, _abi.OBB_OVERLAP_ABI)
-    P = C.c_void_p
-    a = (scene._h, P(centre.data_ptr()), P(axes.data_ptr()), n)
-    return _overlap_list(scene, n, centre.device, (centre, axes), capacity, check, stream,
-                         lambda lib, n_overlap, h: lib.ezrt_query_obb_overlap_device(*a, 0, None, n_overlap, h),
-                         lambda lib, *out: lib.ezrt_query_obb_overlap_list_device(*a, *out))
+    return _overlap_list(scene, "obb", (centre, axes), n, centre.device, capacity, check, stream)
 
 
 def tri_overlap_list(scene, tris, capacity=None, check=False, stream=None):
@@ -1975,10 +1698,7 @@ def tri_overlap_list(scene, tris, capacity=None, check=False, stream=None):
     the scene that each one crosses or touches, in ascending id, CSR.  The contract: include/ezrt_overlap_list.h."""
     n = _check_tris(tris)
     _scene_lib(scene, _abi.TRI_OVERLAP_ABI)
-    a = (scene._h, C.c_void_p(tris.data_ptr()), n)
-    return _overlap_list(scene, n, tris.device, (tris,), capacity, check, stream,
-                         lambda lib, n_overlap, h: lib.ezrt_query_tri_overlap_device(*a, 0, None, n_overlap, h),
-                         lambda lib, *out: lib.ezrt_query_tri_overlap_list_device(*a, *out))
+    return _overlap_list(scene, "tri", (tris,), n, tris.device, capacity, check, stream)
 
 
 def self_overlap_list(scene, ids=None, capacity=None, check=False, stream=None):
@@ -1993,10 +1713,7 @@ def self_overlap_list(scene, ids=None, capacity=None, check=False, stream=None):
         n, device = scene.stats()["n_tri"], torch.device("cuda", torch.cuda.current_device())
     else:
         n, device = _count(ids, 1, "triangle ids"), ids.device
-    a = (scene._h, C.c_void_p(ids.data_ptr()) if ids is not None else None, n)
-    return _overlap_list(scene, n, device, (ids,), capacity, check, stream,
-                         lambda lib, n_overlap, h: lib.ezrt_query_self_overlap_device(*a, 0, None, n_overlap, h),
-                         lambda lib, *out: lib.ezrt_query_self_overlap_list_device(*a, *out))
+    return _overlap_list(scene, "self", (ids,), n, device, capacity, check, stream)
 
 
 def capsule_overlap_list(scene, segs, radius, capacity=None, check=False, stream=None):
@@ -2005,8 +1722,4 @@ def capsule_overlap_list(scene, segs, radius, capacity=None, check=False, stream
     n = _check_segs(segs)
     _tensor("radius", radius, torch.float32, segs.shape[:-1], device=segs.device)
     _scene_lib(scene, _abi.SEGMENT_ABI)
-    P = C.c_void_p
-    a = (scene._h, P(segs.data_ptr()), P(radius.data_ptr()), n)
-    return _overlap_list(scene, n, segs.device, (segs, radius), capacity, check, stream,
-                         lambda lib, n_overlap, h: lib.ezrt_query_capsule_overlap_device(*a, 0, None, n_overlap, h),
-                         lambda lib, *out: lib.ezrt_query_capsule_overlap_list_device(*a, *out))
+    return _overlap_list(scene, "capsule", (segs, radius), n, segs.device, capacity, check, stream)

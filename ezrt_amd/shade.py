@@ -14,16 +14,12 @@ Every value is what a render call of that integrator computes, on the bits.  The
 torch.cuda.Stream or a raw hipStream_t handle; default: the current stream of the tensors' device) and the functions return
 without waiting for it.
 """
-import ctypes as C
-
 import torch
 
 from . import _abi
 from .query import _SURFACE_INTEGRATORS as INTEGRATORS
-from .query import _call, _keep, _scene_lib, _stream
+from .query import _OnStream, _scene_lib
 from .query import _tensor as _query_tensor
-
-_P = C.c_void_p
 
 
 def _tensor(name, x, dtype, shape=None, last=None, device=None):
@@ -44,11 +40,8 @@ def material(scene, tri, stream=None):
     _tensor("tri", tri, torch.int32)
     out = torch.empty(tuple(tri.shape) + (18,), dtype=torch.float32, device=tri.device)
     n = tri.numel()
-    if n == 0:
-        return out
-    h, ts = _stream(tri, stream)
-    _call(scene, lib.ezrt_query_material_device(scene._h, _P(tri.data_ptr()), n, _P(out.data_ptr()), _P(h)))
-    _keep((tri, out), ts, tri)
+    if n > 0:
+        _OnStream(scene, tri, stream).run(lib.ezrt_query_material_device, tri, n, out)
     return out
 
 
@@ -65,12 +58,8 @@ def evaluate(scene, tri, V, N, L, integrator=_abi.INTEGRATOR_P5_MIS, want_pdf=Tr
     f_r = torch.empty(v3, dtype=torch.float32, device=tri.device)
     pdf = torch.empty(tuple(tri.shape), dtype=torch.float32, device=tri.device) if want_pdf else None
     n = tri.numel()
-    if n == 0:
-        return f_r, pdf
-    h, ts = _stream(tri, stream)
-    _call(scene, lib.ezrt_shade_eval_device(scene._h, integrator, _P(tri.data_ptr()), _P(V.data_ptr()), _P(N.data_ptr()),
-                                            _P(L.data_ptr()), n, _P(f_r.data_ptr()), _P(pdf.data_ptr()) if want_pdf else None, _P(h)))
-    _keep((tri, V, N, L, f_r, pdf), ts, tri)
+    if n > 0:
+        _OnStream(scene, tri, stream).run(lib.ezrt_shade_eval_device, integrator, tri, V, N, L, n, f_r, pdf)
     return f_r, pdf
 
 
@@ -86,12 +75,8 @@ def sample(scene, tri, xi, V, N, integrator=_abi.INTEGRATOR_P5_MIS, stream=None)
         _tensor(name, x, torch.float32, v3, device=tri.device)
     L = torch.empty(v3, dtype=torch.float32, device=tri.device)
     n = tri.numel()
-    if n == 0:
-        return L
-    h, ts = _stream(tri, stream)
-    _call(scene, lib.ezrt_shade_sample_device(scene._h, integrator, _P(tri.data_ptr()), _P(xi.data_ptr()), _P(V.data_ptr()),
-                                              _P(N.data_ptr()), n, _P(L.data_ptr()), _P(h)))
-    _keep((tri, xi, V, N, L), ts, tri)
+    if n > 0:
+        _OnStream(scene, tri, stream).run(lib.ezrt_shade_sample_device, integrator, tri, xi, V, N, n, L)
     return L
 
 
@@ -105,12 +90,8 @@ def env_evaluate(scene, L, env_clamp=0.0, want_colour=True, want_pdf=True, strea
     colour = torch.empty(tuple(L.shape), dtype=torch.float32, device=L.device) if want_colour else None
     pdf = torch.empty(tuple(L.shape[:-1]), dtype=torch.float32, device=L.device) if want_pdf else None
     n = L.numel() // 3
-    if n == 0:
-        return colour, pdf
-    h, ts = _stream(L, stream)
-    _call(scene, lib.ezrt_env_eval_device(scene._h, _P(L.data_ptr()), n, float(env_clamp), _P(colour.data_ptr()) if want_colour else None,
-                                          _P(pdf.data_ptr()) if want_pdf else None, _P(h)))
-    _keep((L, colour, pdf), ts, L)
+    if n > 0:
+        _OnStream(scene, L, stream).run(lib.ezrt_env_eval_device, L, n, float(env_clamp), colour, pdf)
     return colour, pdf
 
 
@@ -120,9 +101,6 @@ def env_sample(scene, xi, stream=None):
     _tensor("xi", xi, torch.float32, last=2)
     L = torch.empty(tuple(xi.shape[:-1]) + (3,), dtype=torch.float32, device=xi.device)
     n = xi.numel() // 2
-    if n == 0:
-        return L
-    h, ts = _stream(xi, stream)
-    _call(scene, lib.ezrt_env_sample_device(scene._h, _P(xi.data_ptr()), n, _P(L.data_ptr()), _P(h)))
-    _keep((xi, L), ts, xi)
+    if n > 0:
+        _OnStream(scene, xi, stream).run(lib.ezrt_env_sample_device, xi, n, L)
     return L

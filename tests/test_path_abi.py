@@ -71,5 +71,5 @@ def test_path_module_functions():
     assert par["integrator"].default == _abi.INTEGRATOR_P5_MIS == 51
     assert par["max_bounce"].default == 2 and par["env_clamp"].default == 0.0 and par["stream"].default is None
     # the stream and allocator handling is query.py's own and the tensor checks are shade.py's, not copies
-    assert path._stream is query._stream and path._keep is query._keep and path._call is query._call
+    assert path._OnStream is query._OnStream
     assert path._tensor is shade._tensor

@@ -71,4 +71,4 @@ def test_shade_module_functions():
     assert inspect.signature(shade.evaluate).parameters["want_pdf"].default is True
     assert inspect.signature(shade.env_evaluate).parameters["env_clamp"].default == 0.0
     # the stream and allocator handling is query.py's own, not a copy
-    assert shade._stream is query._stream and shade._keep is query._keep and shade._call is query._call
+    assert shade._OnStream is query._OnStream
