@@ -429,6 +429,34 @@ ISO_SIZES = {
 ISO_BLOCK = 256  # EZRT_ISO_BLOCK: cells per entry of offsets
 
 
+# stream-ordered mesh smoothing on device memory, libezrt_hip.so only (include/ezrt_smooth.h); pointers are device addresses
+SMOOTH_ABI = {
+    # s, tri36, n_rows, edge_class, vertex, star_offsets, star, vert_flags, steps, lambda, mu, flags, tile_rows, out, summary, work,
+    # work_bytes, stream
+    "ezrt_smooth_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+                                + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+}
+# the header's other entry points, in a table of their own as ISO_SIZES: tests/test_mesh_work_bytes.py holds the *_work_bytes of the
+# *_ABI tables to its own list of formulas (tests/test_smooth_abi.py holds this one to its formula)
+SMOOTH_SIZES = {
+    # n_rows: the bytes of `work` (no device work)
+    "ezrt_smooth_work_bytes": (C.c_size_t, [C.c_int]),
+    # tile_rows_max: the limit as compiled (a host pointer; no device work)
+    "ezrt_smooth_limits": (None, [C.c_void_p]),
+}
+SMOOTH_PIN_BORDER = 1
+SMOOTH_STEPS_MAX = 1024
+
+
+def smooth_limits():
+    """tile_rows_max of the loaded HIP library: the rows whose smoothing steps run in LDS, in one launch (include/ezrt_smooth.h).  No
+    device work."""
+    lib = _declare(load_hip(), SMOOTH_SIZES)
+    a = C.c_int(-1)
+    lib.ezrt_smooth_limits(C.byref(a))
+    return a.value
+
+
 # stream-ordered overlap lists on device memory, libezrt_hip.so only (include/ezrt_overlap_list.h); pointers are device addresses
 _LIST = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]  # offsets, capacity, tri_id, n_found, stream
 OVERLAP_LIST_ABI = {
@@ -527,7 +555,7 @@ def load_hip():
         for table in (BUILD_ABI, QUERY_ABI, SURFACE_ABI, SHADE_ABI, PATH_ABI, MULTIHIT_ABI, CLOSEST_POINT_ABI, NEAREST_ABI,
                       INSIDE_ABI, BOX_OVERLAP_ABI, TRI_OVERLAP_ABI, SELF_OVERLAP_ABI, TRI_DISTANCE_ABI, SPHERE_CAST_ABI, SEGMENT_ABI,
                       OBB_OVERLAP_ABI, WINDING_ABI, PLANE_ABI, PLANE_LOOPS_ABI, TOPOLOGY_ABI, WELD_ABI, ORIENT_ABI, BOUNDARY_ABI,
-                      CLIP_ABI, SUBDIVIDE_ABI, DECIMATE_ABI, ISO_ABI, ISO_SIZES, OVERLAP_LIST_ABI,
+                      CLIP_ABI, SUBDIVIDE_ABI, DECIMATE_ABI, ISO_ABI, ISO_SIZES, SMOOTH_ABI, SMOOTH_SIZES, OVERLAP_LIST_ABI,
                       REFIT_ABI):
             _declare(lib, table)
         _hip = lib

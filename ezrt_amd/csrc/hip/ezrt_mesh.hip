@@ -3,7 +3,7 @@
 // normals (ezrt_vertices.h, ezrt_vertex_kernels.h), mesh orientation and rewind (ezrt_orient.h, ezrt_orient_kernels.h), boundary loops
 // and caps (ezrt_boundary.h, ezrt_boundary_kernels.h), plane clipping (ezrt_clip.h, ezrt_clip_kernels.h), subdivision
 // (ezrt_subdivide.h, ezrt_subdiv_kernels.h), decimation (ezrt_decimate.h, ezrt_decimate_kernels.h) and isosurface extraction
-// (ezrt_isosurface.h, ezrt_iso_kernels.h).  What the families share is
+// (ezrt_isosurface.h, ezrt_iso_kernels.h) and smoothing (ezrt_smooth.h, ezrt_smooth_kernels.h).  What the families share is
 // stated once: the prefix sums are scan_small and scan_tiled (ezrt_scan_kernels.h); a `work` buffer is described by ONE layout function
 // over a WorkCarver (ezrt_work_carver.h), which ezrt_*_work_bytes runs over a null pointer and the call over the caller's; the argument
 // checks and the grids are the helpers below.  A translation unit of its own, as ezrt_queries.hip is: none of its kernels is compiled
@@ -17,6 +17,7 @@
 #include "ezrt_subdivide.h"
 #include "ezrt_decimate.h"
 #include "ezrt_isosurface.h"
+#include "ezrt_smooth.h"
 #include "ezrt_work_carver.h"
 #define EZRT_SCAN_TILED 1 // this unit launches the tiled prefix sum too
 #include "ezrt_scan_kernels.h"
@@ -28,6 +29,7 @@
 #include "ezrt_subdiv_kernels.h"
 #include "ezrt_decimate_kernels.h"
 #include "ezrt_iso_kernels.h"
+#include "ezrt_smooth_kernels.h"
 
 using ezi::WorkCarver;
 
@@ -666,6 +668,77 @@ int ezrt_iso_rows_device(EzrtScene* s, const float* values, int nx, int ny, int 
       const dim3 g((unsigned)B), b(ISO_BLOCK);
       if (fill_staged(EZRT_ISO_PER_LANE, out, out)) hipLaunchKernelGGL(iso_fill_kernel<true>, g, b, 0, st, a);
       else hipLaunchKernelGGL(iso_fill_kernel<false>, g, b, 0, st, a);
+    });
+  });
+}
+
+// ---- smoothing on device memory (include/ezrt_smooth.h): a memset of the summary; the plan -- smooth_plan_kernel, the tiled prefix
+// sum (scan_tiled) of the workgroups' counts, smooth_terms_kernel -- over the caller's `work`: counts (one int64 per 256 corners, and
+// one), tiles (one int64 per 2048 counts, and one), the two position buffers (9 n_rows floats each), term (6 n_rows words), rec (9 n_rows
+// words), state (3 n_rows bytes); the steps, one launch each or, where the rows fit tile_rows, one launch of one workgroup for all of
+// them; and one fill launch, the staged instance where tri36 and out are 16-byte aligned, else the per-lane one.  Checked, launched
+// and ordered against a refit by query_call; the scene's records are not read.
+static size_t smooth_layout(void* work, int n_rows, SmoothArgs& a) {
+  const uint64_t H = 3ull * (uint64_t)n_rows, B = (H + SM_BLOCK - 1) / SM_BLOCK;
+  WorkCarver w(work);
+  a.counts = w.take<long long>(B + 1);
+  a.tiles = w.take<long long>(scan_tile_count(B) + 1);
+  a.pos[0] = w.take<float>(3 * H), a.pos[1] = w.take<float>(3 * H);
+  a.term = w.take<uint32_t>(2 * H), a.rec = w.take<uint32_t>(3 * H);
+  a.state = w.take<uint8_t>(H);
+  return w.bytes();
+}
+size_t ezrt_smooth_work_bytes(int n_rows) {
+  SmoothArgs a{};
+  // (a count the call rejects for its size counts as the largest it takes: the function stays monotone)
+  return n_rows <= 0 ? 8 : smooth_layout(nullptr, std::min(n_rows, INT32_MAX / 3), a);
+}
+void ezrt_smooth_limits(int* tile_rows_max) {
+  if (tile_rows_max) *tile_rows_max = SM_TILE_MAX;
+}
+int ezrt_smooth_rows_device(EzrtScene* s, const float* tri36, int n_rows, const uint8_t* edge_class, const int32_t* vertex,
+                            const int32_t* star_offsets, const int32_t* star, const uint8_t* vert_flags, int steps, float lambda, float mu,
+                            int flags, int tile_rows, float* out, int64_t* summary, void* work, size_t work_bytes, void* stream) {
+  return ezi::guarded("ezrt_smooth_rows_device", [&]() -> int {
+    if (!s || !tri36 || !edge_class || !vertex || !star_offsets || !star || !vert_flags || !out || !summary || !work)
+      return fail(EZRT_ERR_INVALID, "NULL argument");
+    if (n_rows < 0) return fail(EZRT_ERR_INVALID, "n_rows < 0");
+    if (n_rows > INT32_MAX / 3) return fail(EZRT_ERR_INVALID, "more than INT32_MAX / 3 rows");
+    if (steps < 1 || steps > EZRT_SMOOTH_STEPS_MAX) return fail(EZRT_ERR_INVALID, "steps %d is outside 1 .. EZRT_SMOOTH_STEPS_MAX", steps);
+    if (!std::isfinite(lambda) || !std::isfinite(mu)) return fail(EZRT_ERR_INVALID, "lambda or mu is not finite");
+    if (flags & ~EZRT_SMOOTH_PIN_BORDER) return fail(EZRT_ERR_INVALID, "flags %d has a bit that is not EZRT_SMOOTH_PIN_BORDER", flags);
+    if (tile_rows < 0) return fail(EZRT_ERR_INVALID, "tile_rows < 0");
+    if (int rc = work_check(work, work_bytes, ezrt_smooth_work_bytes(n_rows), "ezrt_smooth_work_bytes(n_rows)")) return rc;
+    if (n_rows == 0) return 0;
+    const size_t N = (size_t)n_rows, H = 3 * N, i4 = sizeof(int32_t);
+    if (out != tri36) // the same rows exactly: in place
+      if (int rc = overlap_check(tri36, N, out, N)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return query_call(s, {{tri36, N * ROW_BYTES}, {out, N * ROW_BYTES}, {summary, 8 * sizeof(int64_t)}, {work, ezrt_smooth_work_bytes(n_rows)},
+                          {edge_class, H}, {vertex, H * i4}, {star_offsets, (H + 1) * i4}, {star, H * i4}, {vert_flags, H}},
+                      N, st, [&](dim3, dim3) -> int {
+      SmoothArgs a{};
+      a.tri36 = tri36, a.n_rows = (int32_t)n_rows, a.steps = (int32_t)steps, a.flags = (int32_t)flags, a.lambda = lambda, a.mu = mu;
+      a.edge_class = edge_class, a.vertex = vertex, a.star_offsets = star_offsets, a.star = star, a.vert_flags = vert_flags;
+      a.out = out, a.summary = (unsigned long long*)summary;
+      smooth_layout(work, n_rows, a);
+      HIP_TRY(hipMemsetAsync(summary, 0, 8 * sizeof(int64_t), st));
+      const uint64_t B = (H + SM_BLOCK - 1) / SM_BLOCK;
+      const dim3 b(SM_BLOCK), gh((unsigned)B);
+      hipLaunchKernelGGL(smooth_plan_kernel, gh, b, 0, st, a);
+      scan_tiled(st, a.counts, a.tiles, scan_tile_count(B), nullptr, (long long)B); // the counts, in place; the total lands in counts[B]
+      hipLaunchKernelGGL(smooth_terms_kernel, gh, b, 0, st, a);
+      const int tile = tile_rows == 0 || tile_rows > SM_TILE_MAX ? SM_TILE_MAX : tile_rows;
+      if (n_rows <= tile) {
+        hipLaunchKernelGGL(smooth_steps_lds_kernel, dim3(1), dim3(SM_LDS_BLOCK), 0, st, a);
+      } else {
+        const dim3 gs((unsigned)std::min<uint64_t>(B, SM_GRID_MAX));
+        for (int j = 0; j < steps; j++) hipLaunchKernelGGL(smooth_step_kernel, gs, b, 0, st, a, (int32_t)j); // steps are separated by launches
+      }
+      if (fill_staged(false, tri36, out))
+        hipLaunchKernelGGL(smooth_fill_kernel<true>, dim3((unsigned)std::min<uint64_t>((N + SM_FILL_TILE - 1) / SM_FILL_TILE, SM_GRID_MAX)), b, 0, st, a);
+      else hipLaunchKernelGGL(smooth_fill_kernel<false>, mesh_blocks(N, SM_BLOCK), b, 0, st, a);
+      return 0;
     });
   });
 }

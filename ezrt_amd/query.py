@@ -3,7 +3,7 @@ include/ezrt_closest_point.h, include/ezrt_nearest.h, include/ezrt_inside.h, inc
 include/ezrt_tri_overlap.h, include/ezrt_self_overlap.h, include/ezrt_tri_distance.h, include/ezrt_sphere_cast.h,
 include/ezrt_segment.h, include/ezrt_obb_overlap.h, include/ezrt_winding.h, include/ezrt_plane.h, include/ezrt_plane_loops.h,
 include/ezrt_overlap_list.h, include/ezrt_topology.h, include/ezrt_vertices.h, include/ezrt_orient.h, include/ezrt_boundary.h,
-include/ezrt_clip.h, include/ezrt_subdivide.h).
+include/ezrt_clip.h, include/ezrt_subdivide.h, include/ezrt_smooth.h).
 
     tri, t = query.closest(scene, rays)               # the reference's closest hit of every ray
     tri, t = query.closest(scene, rays, t_max)        # ... if it lies below t_max, else a miss
@@ -59,6 +59,7 @@ include/ezrt_clip.h, include/ezrt_subdivide.h).
     clip = query.clip_rows(scene, tri36, plane)                               # the rows of tri36 on the side a x + b y + c z >= d of a plane
     seg = query.cut_segments(clip)                                            # ... the edges the cut made, start to end (include/ezrt_clip.h)
     sub = query.subdivide_rows(scene, tri36, "loop", topo, weld)              # four rows per row, by midpoints or Loop's scheme (include/ezrt_subdivide.h)
+    fair = query.smooth_rows(scene, tri36, topo, weld, steps=6, lam=0.5, mu=-0.53)   # Laplacian / Taubin fairing, many steps in one call (include/ezrt_smooth.h)
 
 `scene` is a `trace.Scene` of the HIP library, `rays` a contiguous float32 GPU tensor of shape [..., 6] (origin, direction) and
 `t_max` (optional) a float32 GPU tensor of shape rays.shape[:-1]; `points` is a contiguous float32 GPU tensor of shape [..., 3] and
@@ -1723,3 +1724,7 @@ def capsule_overlap_list(scene, segs, radius, capacity=None, check=False, stream
     _tensor("radius", radius, torch.float32, segs.shape[:-1], device=segs.device)
     _scene_lib(scene, _abi.SEGMENT_ABI)
     return _overlap_list(scene, "capsule", (segs, radius), n, segs.device, capacity, check, stream)
+
+
+# the mesh smoothing has a module of its own (ezrt_amd/smooth.py) and is reached from here like every other mesh call
+from .smooth import SmoothRows, smooth_rows  # noqa: E402,F401
